@@ -2,6 +2,7 @@
 """Horn-Schunck Jacobi throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--weak]
+                    [--dump-outputs DIR] [--full]
 
 One step = one pass of the hot path: the Horn-Schunck iteration loop of
 ImageRegistrationOpticalFlow::estimate_motion_at_current_resolution
@@ -34,7 +35,21 @@ run.  The timed region is exactly K loops of 1000 iterations, each followed
 by the read-back of its Logger sums (one host synchronisation per loop, as the
 reference returns to its caller after every loop).
 
-After the timed region (N = 1 on config 2's grid, rank 0) the JSON line's
+A plain run does only what `value` needs: set-up, warm-up, the K timed steps,
+the output dump when --dump-outputs is given, the JSON line.  --dump-outputs DIR
+writes what the last timed step left for its caller as DIR/<name>.npy: `motion`
+(float64, the slab's [dimx, rows, 2] motion, or a fixed seeded sample of its
+pixels as [k, 2] once the whole field would pass the dump's byte budget) and
+`errors` (float32, the loop's Logger errors); with N > 1 every rank writes
+`motion_rank<r>` and rank 0 `errors`.  The inputs are the same from run to run,
+so two builds can be compared array for array.
+
+Everything else runs only with --full, after the timed region and the dump: the
+kernel's isolated back-to-back launch time (`roofline.isolated_launch_us`), the
+convergence-on loop (`default_semantics`) and the CPU baseline (`cpu_baseline`);
+a plain run leaves these three null.
+
+With --full (N = 1 on config 2's grid, rank 0) the JSON line's
 `default_semantics` object records the default convergence-on loop at 4096^2 —
 the reference's Logger and break, not part of `value`: iterations executed
 against the reference fixtures' 102 / 397, the motion's match, us per
@@ -72,6 +87,9 @@ ALPHA = 0.1
 KERNEL = {"image": "of2d::hs::jacobi3_kernel<0,4,true,4,4,1,true,true> (gradients from Iaux)",
           "field": "of2d::hs::jacobi3_kernel<0,4,true,4,4,1,true,false> (gradients read from dI)"}
 TRAFFIC_PROFILE = os.path.join("profiles", "hs_traffic.json")
+# --dump-outputs: bytes a run writes at most, every rank and array together
+DUMP_BUDGET = 48 << 20
+DUMP_SEED = 0
 
 
 def parse_args(argv=None):
@@ -90,19 +108,26 @@ def parse_args(argv=None):
     ap.add_argument("--weak", action="store_true",
                     help="weak scaling: each rank owns G rows of a G x (G N) grid")
     ap.add_argument("--size", type=int, default=0, help=argparse.SUPPRESS)  # old name of --grid
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's motion and Logger "
+                         "errors as DIR/<name>.npy (a fixed seeded sample of a large motion)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the isolated kernel launches, "
+                         "the convergence-on loop (default_semantics) and the CPU baseline")
     ap.add_argument("--cpu-iters", type=int, default=20)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the all-cores CPU baseline (default: OMP_NUM_THREADS, "
                          "else every CPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--gradients", choices=["auto", "image", "field"], default="auto",
                     help="triple kernel: derive dI from Iaux in the kernel (image, 24 B/px "
                          "per launch) or read the stored field dI (field, 28 B/px); auto "
                          "(default): image once dI + It exceed the 256 MB MALL")
     ap.add_argument("--timing-launches", type=int, default=200)
     ap.add_argument("--no-default-semantics", action="store_true",
-                    help="skip the convergence-on (reference Logger) measurement after the "
-                         "timed region")
+                    help="with --full: skip the convergence-on (reference Logger) measurement "
+                         "after the timed region")
     ap.add_argument("--rccl", action="store_true",
                     help="N = 1: run the Logger all-reduces through a one-rank RCCL communicator")
     ap.add_argument("--self-halo", action="store_true",
@@ -242,6 +267,35 @@ def halo_summary(per_rank: list) -> dict | None:
             "per_rank": per_rank}
 
 
+def dump_arrays(motion: np.ndarray, errors: np.ndarray, rank: int = 0, world: int = 1,
+                budget: int = DUMP_BUDGET) -> dict:
+    """name -> array of --dump-outputs for one rank: the slab's motion
+    ([dimx, rows, 2] float64) whole when the rank's share of `budget` bytes
+    holds it, else the [k, 2] motion of k pixels drawn once with DUMP_SEED
+    (sorted column-major pixel indices, the same in every run of the same
+    grid), and on rank 0 the Logger errors (float32)."""
+    motion = np.asarray(motion, np.float64)
+    errors = np.asarray(errors, np.float32)
+    out = {}
+    share = budget // world
+    if rank == 0:
+        out["errors"] = errors
+        share -= errors.nbytes
+    pixels = motion.shape[0] * motion.shape[1]
+    k = max(share // 16, 1)
+    if pixels > k:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, size=k, replace=False))
+        motion = np.ascontiguousarray(motion.reshape((pixels, 2), order="F")[idx])
+    out["motion" if world == 1 else f"motion_rank{rank}"] = motion
+    return out
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a, allow_pickle=False)
+
+
 def load_traffic(dimx: int, rows: int, gradients: str = "field"):
     """PMC traffic per launch from the committed profile, only for the grid it
     was measured on (it is not measured inside this run)."""
@@ -318,7 +372,7 @@ def make_record(*, world, wl, steps, warmup, elapsed, gpu_ms, avg_us, iso_us, px
                                   "back-to-back triple launches inside the timed loops "
                                   f"({avg_n} launches)"),
             "loop_us_per_3_iterations": round(loop_us, 3) if loop_us else None,
-            "isolated_launch_us": round(iso_us, 3),
+            "isolated_launch_us": round(iso_us, 3) if iso_us is not None else None,
             "bytes_per_launch": bpl * px_rank,
             "bytes_per_px_launch": bpl,
             "traffic": (traffic or {}).get("bytes_per_launch"),
@@ -439,8 +493,10 @@ def main():
     avg_us = tri_us / tri_n if tri_n else gpu_ms * 1000.0 * ITERS_PER_LAUNCH / (args.steps * ips)
     # per iteration over the whole loop (reductions and tail included)
     loop_us = gpu_ms * 1000.0 * ITERS_PER_LAUNCH / (args.steps * ips)
+    if args.dump_outputs:  # what the last timed step left for its caller
+        dump_outputs(args.dump_outputs, dump_arrays(solver.motion(), solver.errors(), rank, world))
     # and back-to-back launches of the kernel alone, after the run
-    iso_us = solver.time_kernel(args.timing_launches)
+    iso_us = solver.time_kernel(args.timing_launches) if args.full else None
     rows = solver.row_end - solver.row_begin
     px_rank = dimx * rows
 
@@ -449,13 +505,13 @@ def main():
         semantics = None
         # the convergence-on loop at config 2's grid, only when that is the
         # timed grid; a failure there is recorded and never costs the line
-        if (world == 1 and not args.no_default_semantics
+        if (args.full and world == 1 and not args.no_default_semantics
                 and (dimx, dimy) == (4096, 4096)):
             try:
                 semantics = default_semantics()
             except Exception as e:  # noqa: BLE001
                 semantics = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the same grid; iterations scaled to keep the sample at ~15-30 s
             cpu_it = max(1, int(args.cpu_iters * (4096.0 / dimx) ** 2))
             cpu = cpu_baseline(dimx, cpu_it, cpu_threads(args))

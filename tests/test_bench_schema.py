@@ -111,3 +111,52 @@ def test_traffic_only_for_its_grid_and_kernel():
     assert t is not None and t["grid"] == [4096, 4096]
     assert bench.load_traffic(4096, 4096, "image") is None
     assert bench.load_traffic(16384, 8192, "field") is None
+
+
+def test_full_flag_and_plain_record():
+    """A plain run measures only the headline: --full is off by default, and
+    the figures behind it stay in the line as nulls."""
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    assert bench.parse_args([]).dump_outputs is None
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    wl = bench.workload(bench.parse_args([]), 1)
+    r = bench.make_record(world=1, wl=wl, steps=20, warmup=5, elapsed=0.6, gpu_ms=580.0,
+                          avg_us=87.0, iso_us=None, px_rank=4096 * 4096, info={}, traffic=None,
+                          cpu=None, rows_per_rank=4096, iters_per_step=1000, gradients="field")
+    assert CONTRACT <= set(r)
+    assert r["roofline"]["isolated_launch_us"] is None
+    assert r["cpu_baseline"] is None and r["default_semantics"] is None
+    assert r["ms_per_step"] == pytest.approx(30.0, rel=1e-6) and r["value"] > 0
+    json.loads(json.dumps(r))
+
+
+def test_dump_arrays_whole_sample_and_budget(tmp_path):
+    """--dump-outputs: a motion within the budget goes out whole, a larger one
+    as the same seeded pixel sample in every run; float32 / float64 only."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    m = rng.standard_normal((37, 23, 2))
+    e = rng.standard_normal(11).astype(np.float32)
+    whole = bench.dump_arrays(m, e)
+    assert set(whole) == {"motion", "errors"}
+    assert whole["motion"].dtype == np.float64 and np.array_equal(whole["motion"], m)
+    assert whole["errors"].dtype == np.float32 and np.array_equal(whole["errors"], e)
+    budget = e.nbytes + 100 * 16
+    a = bench.dump_arrays(m, e, budget=budget)
+    b = bench.dump_arrays(m.copy(), e, budget=budget)
+    assert a["motion"].shape == (100, 2) and np.array_equal(a["motion"], b["motion"])
+    assert sum(v.nbytes for v in a.values()) <= budget
+    # every sampled row is a pixel of the field, in column-major pixel order
+    flat = m.reshape((37 * 23, 2), order="F")
+    pos = [int(np.flatnonzero((flat == row).all(axis=1))[0]) for row in a["motion"]]
+    assert pos == sorted(set(pos))
+    # N > 1: one motion per rank, the errors once, the budget shared
+    r1 = bench.dump_arrays(m, e, rank=1, world=2, budget=2 * budget)
+    assert set(r1) == {"motion_rank1"} and r1["motion_rank1"].nbytes <= budget
+    assert bench.DUMP_BUDGET <= 64 * 10 ** 6
+    pix = 4096 * 4096
+    assert bench.DUMP_BUDGET // 16 < pix  # config 2's motion is sampled
+    bench.dump_outputs(str(tmp_path / "out"), a)
+    got = np.load(tmp_path / "out" / "motion.npy", allow_pickle=False)
+    assert got.dtype == np.float64 and np.array_equal(got, a["motion"])
+    assert np.load(tmp_path / "out" / "errors.npy").dtype == np.float32

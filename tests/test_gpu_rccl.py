@@ -192,7 +192,7 @@ def test_bench_under_torch_distributed_run():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "99", "--warmup", "3",
-           "--size", "1024", "--no-cpu-baseline", "--rccl", "--self-halo",
+           "--size", "1024", "--full", "--no-cpu-baseline", "--rccl", "--self-halo",
            "--timing-launches", "5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -44,8 +44,8 @@ for s in "$@"; do
         sntests) run sntests 600 $PT tests/test_gpu_seqnorm.py tests/test_gpu_convergence.py ;;
         slabtests) run slabtests 900 $PT tests/test_gpu_slab_local.py tests/test_gpu_rccl.py tests/test_gpu_ranks.py ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 600 python bench.py ;;
-        prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/${tag}_prof" -o k -- python3 "$R/bench.py" --no-cpu-baseline ;;
+        bench) run bench 600 python bench.py --full ;;
+        prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/${tag}_prof" -o k -- python3 "$R/bench.py" --full --no-cpu-baseline ;;
         benchdrv) run benchdrv 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
         profdrv) run profdrv 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/${tag}_profdrv" -o k -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-default-semantics ;;
         conv) run conv 600 python -u tools/time_convergence.py 4096 3 ;;

@@ -15,8 +15,8 @@ if [ -n "$TF" ] && [ "$TF" != "-" ]; then
   tail -n 1 $OUT/tests_B.log
 fi
 for r in $(seq $N); do
-  timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline > $OUT/A$r.log 2>&1 || exit $?
-  OF2D_LIB_PATH=$B timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline > $OUT/B$r.log 2>&1 || exit $?
+  timeout -k 10 300 python bench.py $ARGS --full --no-cpu-baseline > $OUT/A$r.log 2>&1 || exit $?
+  OF2D_LIB_PATH=$B timeout -k 10 300 python bench.py $ARGS --full --no-cpu-baseline > $OUT/B$r.log 2>&1 || exit $?
   for v in A B; do
     python3 -c "import json,sys; d=json.loads([l for l in open('$OUT/$v$r.log') if l.startswith('{')][-1]); print('$v$r', d['value'], d['roofline']['avg_launch_us'], d['roofline']['isolated_launch_us'], d['roofline']['loop_us_per_3_iterations'])"
   done

@@ -13,7 +13,7 @@ pass() {  # pass <counter> <tag> <cmd...>
 }
 pass FETCH_SIZE hf "$R/tools/hs_variants" 4096 42 triple || exit $?
 pass WRITE_SIZE hw "$R/tools/hs_variants" 4096 42 triple || exit $?
-B="python3 $R/bench.py --steps 33 --warmup 0 --no-cpu-baseline --timing-launches 20"
+B="python3 $R/bench.py --steps 33 --warmup 0 --full --no-cpu-baseline --timing-launches 20"
 pass FETCH_SIZE bf $B || exit $?
 pass WRITE_SIZE bw $B || exit $?
 csv() { find $O/$1 -name '*counter_collection.csv' | head -1; }

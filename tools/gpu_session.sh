@@ -30,8 +30,8 @@ for s in "$@"; do
         conv) step conv 600 python -u tools/time_convergence.py 4096 3 || exit $? ;;
         convprof) step convprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/${tag}_convprof" -o conv -- python3 -u "$R/tools/time_convergence.py" 4096 1 || exit $? ;;
         smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-        bench) step bench 600 python bench.py || exit $? ;;
-        prof) step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/${tag}_prof" -o hs -- python3 "$R/bench.py" --no-cpu-baseline || exit $? ;;
+        bench) step bench 600 python bench.py --full || exit $? ;;
+        prof) step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/${tag}_prof" -o hs -- python3 "$R/bench.py" --full --no-cpu-baseline || exit $? ;;
         cfgs) step cfgs 900 python -u bench_configs.py || exit $? ;;
         cfg4prof) step cfg4prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/${tag}_cfg4prof" -o k -- python3 -u "$R/bench_configs.py" --configs 4 --no-cpu --iters 50 || exit $? ;;
         cfg3prof) step cfg3prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/${tag}_cfg3prof" -o k -- python3 -u "$R/bench_configs.py" --configs 3 --no-cpu --iters 50 || exit $? ;;
