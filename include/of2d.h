@@ -111,8 +111,26 @@ int of2d_last_errors(const of2d_ctx *ctx, float *out, int cap);
  *   ImageRegistrationOpticalFlow.cpp:131-134 falls on the reference's
  *   iteration at every size; 1 sums the magnitudes in fp64 (faster: the fused
  *   multi-iteration kernels stay on; at >= 4096^2 the break can move by a few
- *   iterations).  fixed_iters runs take no break and use the fp64 sums. */
+ *   iterations).  fixed_iters runs take no break and use the fp64 sums.
+ *   "curvature_dct" (0 = default / 1; anything else is refused): how
+ *   Curvature evaluates its REDFT10 / REDFT01.  0: as fp64 GEMMs against dense
+ *   cosine matrices, O(n^3) per iteration and n^2 doubles of tables per axis
+ *   and direction.  1: as fast O(n^2 log n) line transforms on every axis of a
+ *   level whose length is a power of two in [OF2D_DCT_NMIN, OF2D_DCT_NMAX];
+ *   any other axis keeps its GEMM (a 64 x 37 level runs axis x fast and axis y
+ *   by GEMM), and no cosine matrix is built for a fast axis.  The two agree to
+ *   fp64 rounding (a different summation order); of2d_curvature_paths tells
+ *   what ran.  May be changed between of2d_estimate calls. */
 int of2d_set_option(of2d_ctx *ctx, const char *key, double value);
+/* line lengths the fast transforms of "curvature_dct" take (powers of two):
+ * the longest is the longest x | y line pair that fits a compute unit's LDS */
+#define OF2D_DCT_NMIN 8
+#define OF2D_DCT_NMAX 8192
+/* the Curvature loops of the last of2d_estimate, one per (level, refine) in
+ * execution order: four ints {dimx, dimy, fast_x, fast_y} each (the level's
+ * size and, per axis, 1 when it ran the fast transforms, 0 the GEMMs), up to
+ * cap ints into out; returns the number of loops (0 for another solver) */
+int of2d_curvature_paths(const of2d_ctx *ctx, int *out, int cap);
 
 /* ---- gateway: the process-global singleton of WrapperOpticalFlow2d.cpp:13.
  * Mode is keyed on (nlhs, nrhs, singleton present) exactly like mexFunction:
@@ -265,6 +283,23 @@ int of2d_motion_norms(const float *cur, const float *prev, int dimx, int dimy, i
  * reference: a test entry for the batched device norms. */
 int of2d_motion_norms_chain(const float *u, int dimx, int dimy, int niter, int batch,
                             float *sums, int *stats);
+
+/* ---- kernel-level test entry: Curvature's 2-D transforms ----
+ * The separable REDFT10 (kind 10) or REDFT01 (kind 1) of a dense host array a
+ * (double, idx = i + j*dimx), in place: exactly the device transforms one
+ * Curvature iteration runs at a level of that size (axis y, then axis x; no
+ * eigenvalues).  method 0 runs the GEMMs, 1 the fast line transforms on every
+ * axis that qualifies ("curvature_dct") and the GEMM on any other; paths[0],
+ * paths[1] receive what axis x and axis y ran (1 fast, 0 GEMM). */
+int of2d_dct2d(double *a, int dimx, int dimy, int kind, int method, int *paths);
+/* average duration (microseconds, HIP events around nlaunch back-to-back
+ * launches after one untimed launch) of the fast path's passes over the plane
+ * pair of a dimx x dimy level (both lengths must qualify): us[0] the forward
+ * line pass along x with the eigenvalues, us[1] the inverse line pass along x,
+ * us[2] one transposition, us[3] the forward line pass along y on the
+ * transposed copy.  Every pass reads and writes 16 B per pixel.  A timing
+ * entry for tools/curvature_bench.py, not a result. */
+int of2d_dct_time_passes(int dimx, int dimy, int nlaunch, double *us);
 
 /* ---- library info ---- */
 const char *of2d_version(void);

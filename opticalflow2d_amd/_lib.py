@@ -43,6 +43,9 @@ SIGNATURES = {
     "of2d_iterations_executed": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "of2d_last_errors": (C.c_int, [C.c_void_p, _f32p, C.c_int]),
     "of2d_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "of2d_curvature_paths": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
+    "of2d_dct2d": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p]),
+    "of2d_dct_time_passes": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
     "of2d_gateway": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     "of2d_gateway_output_numel": (C.c_size_t, [C.c_int, C.c_int]),
     "of2d_gateway_output_dims": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t),

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "of2d_host.h"
+#include "of2d_solvers.h"
 
 struct of2d_ctx {
     std::unique_ptr<of2d::Registration> reg;
@@ -152,6 +153,86 @@ int of2d_last_errors(const of2d_ctx *ctx, float *out, int cap) {
 int of2d_set_option(of2d_ctx *ctx, const char *key, double value) {
     if (!ctx || !key) return OF2D_ERR_INVALID_ARGUMENT;
     return guarded(ctx->err, [&] { ctx->reg->set_option(key, value); });
+}
+
+int of2d_curvature_paths(const of2d_ctx *ctx, int *out, int cap) {
+    if (!ctx) return -1;
+    const auto &v = ctx->reg->curvature_paths();
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size() / 4;
+}
+
+static_assert(OF2D_DCT_NMIN == of2d::kDctMinN && OF2D_DCT_NMAX == of2d::kDctMaxN,
+              "include/of2d.h documents the fast transform's lengths");
+
+int of2d_dct2d(double *a, int dimx, int dimy, int kind, int method, int *paths) {
+    if (!a || !paths || dimx <= 0 || dimy <= 0 || (kind != 10 && kind != 1) ||
+        (method != 0 && method != 1))
+        return OF2D_ERR_INVALID_ARGUMENT;
+    std::string err;
+    int rc = guarded(err, [&] {
+        // a level of the solver with nothing but Curvature's buffers and tables
+        of2d::Level L;
+        L.dx = dimx;
+        L.dy = dimy;
+        L.P = of2d::pitch_for(dimx);
+        of2d::solvers::alloc_level(L, OF2D_REG_CURVATURE);
+        of2d::solvers::build_curvature(L, 0.0f, 0.0f, method, nullptr);
+        paths[0] = L.cpath & 1;
+        paths[1] = (L.cpath >> 1) & 1;
+        const size_t row = (size_t)dimx * sizeof(double), pitch = (size_t)L.P * sizeof(double);
+        OF2D_HIP(hipMemcpy2D(L.cbuf[0].p, pitch, a, row, row, dimy, hipMemcpyHostToDevice));
+        const double *res = of2d::solvers::curvature_dct2d(L, kind == 1, L.cbuf[0].p,
+                                                           L.cbuf[1].p, nullptr, nullptr);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy2D(a, row, res, pitch, row, dimy, hipMemcpyDeviceToHost));
+    });
+    if (rc != OF2D_OK) g_gateway_err = err;
+    return rc;
+}
+
+int of2d_dct_time_passes(int dimx, int dimy, int nlaunch, double *us) {
+    if (!us || nlaunch <= 0 || !of2d::dct_fast_length(dimx) || !of2d::dct_fast_length(dimy))
+        return OF2D_ERR_INVALID_ARGUMENT;
+    std::string err;
+    int rc = guarded(err, [&] {
+        of2d::Level L;
+        L.dx = dimx;
+        L.dy = dimy;
+        L.P = of2d::pitch_for(dimx);
+        of2d::solvers::alloc_level(L, OF2D_REG_CURVATURE);
+        of2d::solvers::build_curvature(L, 0.0f, 0.0f, 1, nullptr);
+        const int P = L.P, Pt = of2d::pitch_for(dimy);
+        const long plane = (long)P * dimy, planeT = (long)Pt * dimx;
+        double *X = L.cbuf[0].p, *T = L.cbuf[1].p;
+        hipEvent_t e0, e1;
+        OF2D_HIP(hipEventCreate(&e0));
+        OF2D_HIP(hipEventCreate(&e1));
+        // the buffers hold zeros: the transforms' cost does not depend on the data
+        for (int which = 0; which < 4; which++) {
+            for (int k = -1; k < nlaunch; k++) {  // k = -1: one untimed launch
+                if (k == 0) OF2D_HIP(hipEventRecord(e0, nullptr));
+                if (which == 0)
+                    of2d::launch_dct_lines(X, plane, P, dimy, dimx, 0, L.ctwx.p, L.cE.p, nullptr);
+                else if (which == 1)
+                    of2d::launch_dct_lines(X, plane, P, dimy, dimx, 1, L.ctwx.p, nullptr, nullptr);
+                else if (which == 2)
+                    of2d::launch_transpose_pair(X, P, plane, T, Pt, planeT, dimx, dimy, nullptr);
+                else
+                    of2d::launch_dct_lines(T, planeT, Pt, dimx, dimy, 0, L.ctwy.p, nullptr,
+                                           nullptr);
+            }
+            OF2D_HIP(hipEventRecord(e1, nullptr));
+            OF2D_HIP(hipEventSynchronize(e1));
+            float ms = 0.0f;
+            OF2D_HIP(hipEventElapsedTime(&ms, e0, e1));
+            us[which] = 1000.0 * (double)ms / nlaunch;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    });
+    if (rc != OF2D_OK) g_gateway_err = err;
+    return rc;
 }
 
 int of2d_motion_norms(const float *cur, const float *prev, int dimx, int dimy, int npairs,

@@ -420,6 +420,24 @@ int curv_nblocks(int dimx, int dimy);
 void launch_curv_construct(const double *Z, long plane, const float2 *u, float2 *out, float div,
                            int dimx, int dimy, int P, double *partial, hipStream_t st);
 
+// Fast line transforms (dct_kernels.hip): lengths that are a power of two in
+// [kDctMinN, kDctMaxN].  kDctMaxN is the longest line pair (16 B per point)
+// that fits the 160 KiB of LDS of a CU: 8192 points are 128 KiB.
+constexpr int kDctMinN = 8;
+constexpr int kDctMaxN = 8192;
+bool dct_fast_length(int n);
+// the twiddles of length n as 2n (re, im) pairs: exp(-2 pi i m / n), then
+// exp(-i pi k / (2n)), evaluated in fp64 on the host
+std::vector<double> dct_table(int n);
+// kind 0: REDFT10 (times E[k + line * P] when E != nullptr), 1: REDFT01, of
+// lines [0, nlines) of length n, in place: element k of line l at X[l * P + k]
+// and X[plane + l * P + k]; tw is dct_table(n) on the device
+void launch_dct_lines(double *X, long plane, int P, int nlines, int n, int kind, const double *tw,
+                      const double *E, hipStream_t st);
+// D[j + i * Pd] = S[i + j * Ps] for i < n0, j < n1, both planes
+void launch_transpose_pair(const double *S, long Ps, long planeS, double *D, long Pd, long planeD,
+                           int n0, int n1, hipStream_t st);
+
 // ---------------------------------------------------------------- Fluid / Elastic
 int sor_nstrips(int dimx);
 // The SOR working array vb is stored skewed along the Gauss-Seidel wavefront:

@@ -95,6 +95,11 @@ struct DevArray {
         OF2D_HIP(hipMemset(p, 0, sizeof(T) * (count ? count : 1)));
         OF2D_HIP(hipDeviceSynchronize());  // see Field::alloc
     }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
 };
 
 // the Fluid loop's report ring (iterations enqueued ahead of the host's read)
@@ -168,6 +173,8 @@ struct Level {
     DevArray<double> cbuf[2];              // Curvature: two x|y double plane pairs (pitch P)
     DevArray<double> cC1T, cC0, cD1T, cD0;  // Curvature: REDFT10 / REDFT01 matrices
     DevArray<double> cE;                    // Curvature: eigenvalues (pitch P)
+    DevArray<double> ctwx, ctwy;            // Curvature: dct_table of a fast axis
+    int cpath = -1;  // Curvature tables built for: bit 0 axis x fast, bit 1 axis y fast (-1: none)
     Field<float4> vb;                   // SOR working array {v, b} (Fluid: persistent velocity)
     DevArray<unsigned long long> sorH;  // SOR strip hand-off granules
     DevArray<unsigned> sorTicket;       // SOR strip ticket (multiple of nstrips between sweeps);
@@ -189,6 +196,8 @@ class Registration {
     void set_option(const std::string &key, double v);
     const std::vector<int> &iterations() const { return iters_; }
     const std::vector<float> &last_errors() const { return last_err_; }
+    // {dx, dy, fast_x, fast_y} per Curvature loop of the last estimate()
+    const std::vector<int> &curvature_paths() const { return cpaths_; }
     int dimx() const { return dimx_; }
     int dimy() const { return dimy_; }
 
@@ -306,6 +315,8 @@ class Registration {
     HostScratch hs_;
     std::vector<int> iters_;
     std::vector<float> last_err_;
+    int curv_dct_ = 0;  // option "curvature_dct"
+    std::vector<int> cpaths_;
     // Demons kernels (Kernel::set_gaussian, src/Kernel.cpp:45-73)
     std::vector<double> kdiff_, kfluid_;
     std::shared_ptr<DemonsKernels> demons_k_;

@@ -199,6 +199,10 @@ void Registration::set_option(const std::string &key, double v) {
         gi_ = v < 0 ? -1 : (v != 0 ? 1 : 0);
     else if (key == "slab_split")
         split_ = v < 0 ? -1 : (v != 0 ? 1 : 0);
+    else if (key == "curvature_dct") {
+        if (v != 0 && v != 1) throw std::invalid_argument("option 'curvature_dct' must be 0 or 1");
+        curv_dct_ = (int)v;
+    }
     else if (key == "device") {
         if (ready_) throw std::invalid_argument("option 'device' must be set before first use");
         device_ = (int)v;
@@ -348,6 +352,7 @@ void Registration::estimate() {
     DeviceScope scope;  // the caller's device again on return
     ensure_device();
     iters_.clear();
+    cpaths_.clear();
     OF2D_HIP(hipMemsetAsync(d_status_, 0, 64 * sizeof(unsigned), st_));
     Level &L0 = lv_[0];
     for (int s = nscales_; s >= 0; s--) {

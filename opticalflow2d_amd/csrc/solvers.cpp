@@ -34,10 +34,13 @@ void alloc_level(Level &L, int reg) {
             L.vb.alloc(L.dx, sor_rows(L.dx, L.dy));  // skewed v | b rows; Fluid: v is the velocity
             if (reg == 5) L.increment.alloc(L.dx, L.dy);
             break;
-        case 1:  // OpticalFlowCurvature.cpp:36-56 (the force is fused into the rhs kernel)
-            L.cbuf[0].alloc(2 * (size_t)L.P * L.dy);
-            L.cbuf[1].alloc(2 * (size_t)L.P * L.dy);
+        case 1: {  // OpticalFlowCurvature.cpp:36-56 (the force is fused into the rhs kernel)
+            // either buffer may hold the transposed copy of a fast axis-y pass
+            const size_t plane = std::max((size_t)L.P * L.dy, (size_t)pitch_for(L.dy) * L.dx);
+            L.cbuf[0].alloc(2 * plane);
+            L.cbuf[1].alloc(2 * plane);
             break;
+        }
         default:
             break;
     }
@@ -326,14 +329,17 @@ int Registration::loop_elastic(Level &L, int niter, int &final_buf) {
 }
 
 // Curvature (OpticalFlowCurvature.cpp:144-167) inside the ImageRegistrationOpticalFlow
-// loop.  The transform matrices and eigenvalues depend only on the level's
+// loop.  The transform tables and eigenvalues depend only on the level's
 // dimensions and the parameters, so they are built once per level on the host
 // in double (the reference's eigenvalue expression, OpticalFlowCurvature.cpp:6-30;
-// the REDFT10 / REDFT01 definitions for the transforms) and uploaded.
-namespace {
-void build_curvature(Level &L, float alpha, float tau, hipStream_t st) {
-    if (L.cE.p) return;
+// the REDFT10 / REDFT01 definitions for the transforms) and uploaded.  An axis
+// that runs the fast line transforms gets its twiddles and no cosine matrices.
+namespace solvers {
+void build_curvature(Level &L, float alpha, float tau, int dct, hipStream_t st) {
     const int n0 = L.dx, n1 = L.dy, P = L.P;
+    const bool fx = dct && dct_fast_length(n0), fy = dct && dct_fast_length(n1);
+    const int path = (fx ? 1 : 0) | (fy ? 2 : 0);
+    if (L.cE.p && L.cpath == path) return;
     const double PI_ = 3.14159265;  // OpticalFlowCurvature.cpp:4
     std::vector<double> h;
     auto upload = [&](DevArray<double> &d) {
@@ -350,40 +356,89 @@ void build_curvature(Level &L, float alpha, float tau, hipStream_t st) {
     auto c01 = [](int k, int j, int n) {
         return j == 0 ? 1.0 : 2.0 * std::cos(M_PI * (double)j * ((double)k + 0.5) / (double)n);
     };
-    // right factors (axis y), column-major n1 x n1: M^T[j][q] = M[q][j]
-    h.assign((size_t)n1 * n1, 0.0);
-    for (int q = 0; q < n1; q++)
-        for (int j = 0; j < n1; j++) h[j + (size_t)q * n1] = c10(q, j, n1);
-    upload(L.cC1T);
-    for (int q = 0; q < n1; q++)
-        for (int j = 0; j < n1; j++) h[j + (size_t)q * n1] = c01(q, j, n1);
-    upload(L.cD1T);
-    // left factors (axis x), column-major n0 x n0 with leading dimension P
-    h.assign((size_t)P * n0, 0.0);
-    for (int i = 0; i < n0; i++)
-        for (int k = 0; k < n0; k++) h[k + (size_t)i * P] = c10(k, i, n0);
-    upload(L.cC0);
-    for (int i = 0; i < n0; i++)
-        for (int k = 0; k < n0; k++) h[k + (size_t)i * P] = c01(k, i, n0);
-    upload(L.cD0);
-    // eigenvalues 1 / (1 + tau alpha (-4 + 2 cos(p pi / nx) + 2 cos(q pi / ny))^2)
-    h.assign((size_t)P * n1, 0.0);
-    const float ta = tau * alpha;
-    for (int p = 0; p < n0; p++)
-        for (int q = 0; q < n1; q++) {
-            const double lam = -4 + 2 * std::cos((unsigned)p * PI_ / (unsigned)n0) +
-                               2 * std::cos((unsigned)q * PI_ / (unsigned)n1);
-            h[p + (size_t)q * P] = 1.0f / (1.0f + ta * std::pow(lam, 2));
-        }
-    upload(L.cE);
+    if (fy) {
+        L.cC1T.release();
+        L.cD1T.release();
+        h = dct_table(n1);
+        upload(L.ctwy);
+    } else {
+        L.ctwy.release();
+        // right factors (axis y), column-major n1 x n1: M^T[j][q] = M[q][j]
+        h.assign((size_t)n1 * n1, 0.0);
+        for (int q = 0; q < n1; q++)
+            for (int j = 0; j < n1; j++) h[j + (size_t)q * n1] = c10(q, j, n1);
+        upload(L.cC1T);
+        for (int q = 0; q < n1; q++)
+            for (int j = 0; j < n1; j++) h[j + (size_t)q * n1] = c01(q, j, n1);
+        upload(L.cD1T);
+    }
+    if (fx) {
+        L.cC0.release();
+        L.cD0.release();
+        h = dct_table(n0);
+        upload(L.ctwx);
+    } else {
+        L.ctwx.release();
+        // left factors (axis x), column-major n0 x n0 with leading dimension P
+        h.assign((size_t)P * n0, 0.0);
+        for (int i = 0; i < n0; i++)
+            for (int k = 0; k < n0; k++) h[k + (size_t)i * P] = c10(k, i, n0);
+        upload(L.cC0);
+        for (int i = 0; i < n0; i++)
+            for (int k = 0; k < n0; k++) h[k + (size_t)i * P] = c01(k, i, n0);
+        upload(L.cD0);
+    }
+    if (!L.cE.p) {
+        // eigenvalues 1 / (1 + tau alpha (-4 + 2 cos(p pi / nx) + 2 cos(q pi / ny))^2)
+        h.assign((size_t)P * n1, 0.0);
+        const float ta = tau * alpha;
+        for (int p = 0; p < n0; p++)
+            for (int q = 0; q < n1; q++) {
+                const double lam = -4 + 2 * std::cos((unsigned)p * PI_ / (unsigned)n0) +
+                                   2 * std::cos((unsigned)q * PI_ / (unsigned)n1);
+                h[p + (size_t)q * P] = 1.0f / (1.0f + ta * std::pow(lam, 2));
+            }
+        upload(L.cE);
+    }
+    L.cpath = path;
 }
-}  // namespace
+
+double *curvature_dct2d(const Level &L, bool inverse, double *cur, double *other, const double *E,
+                        hipStream_t st) {
+    const int n0 = L.dx, n1 = L.dy, P = L.P;
+    const long plane = (long)P * n1;
+    const int kind = inverse ? 1 : 0;
+    // axis y
+    if (L.cpath & 2) {
+        // lines along y are contiguous in the transposed copy (pitch Pt, n0 lines)
+        const int Pt = pitch_for(n1);
+        const long planeT = (long)Pt * n0;
+        launch_transpose_pair(cur, P, plane, other, Pt, planeT, n0, n1, st);
+        launch_dct_lines(other, planeT, Pt, n0, n1, kind, L.ctwy.p, nullptr, st);
+        launch_transpose_pair(other, Pt, planeT, cur, P, plane, n1, n0, st);
+    } else {
+        launch_dgemm(n0, n1, n1, cur, P, plane, inverse ? L.cD1T.p : L.cC1T.p, n1, 0, other, P,
+                     plane, nullptr, 0, 2, st);
+        std::swap(cur, other);
+    }
+    // axis x (the forward pass multiplies by the eigenvalues)
+    if (L.cpath & 1) {
+        launch_dct_lines(cur, plane, P, n1, n0, kind, L.ctwx.p, E, st);
+    } else {
+        launch_dgemm(n0, n1, n0, inverse ? L.cD0.p : L.cC0.p, P, 0, cur, P, plane, other, P, plane,
+                     E, P, 2, st);
+        std::swap(cur, other);
+    }
+    return cur;
+}
+}  // namespace solvers
 
 int Registration::loop_curvature(Level &L, int niter, int &final_buf) {
     const float alpha = params_[0];
     const float tau = params_.size() == 1 ? 1.0f : params_[1];  // OpticalFlowCurvature.h:8
-    build_curvature(L, alpha, tau, st_);
+    solvers::build_curvature(L, alpha, tau, curv_dct_, st_);
     const int n0 = L.dx, n1 = L.dy, P = L.P;
+    cpaths_.insert(cpaths_.end(), {n0, n1, L.cpath & 1, (L.cpath >> 1) & 1});
     const long plane = (long)P * n1;
     const float div = 4.0f * (float)((unsigned)n0 * (unsigned)n1);  // 4.0f*sizein
     double *X = L.cbuf[0].p, *T = L.cbuf[1].p;
@@ -392,14 +447,10 @@ int Registration::loop_curvature(Level &L, int niter, int &final_buf) {
         [&](const float2 *src, float2 *dst, double *partial) {
             launch_curv_rhs(src, L.dI.p, L.It.p, tau, n0, n1, P, X, plane, st_);
             // forward REDFT10 x REDFT10 (axis y, then axis x with the eigenvalues)
-            launch_dgemm(n0, n1, n1, X, P, plane, L.cC1T.p, n1, 0, T, P, plane, nullptr, 0, 2,
-                         st_);
-            launch_dgemm(n0, n1, n0, L.cC0.p, P, 0, T, P, plane, X, P, plane, L.cE.p, P, 2, st_);
+            double *Y = solvers::curvature_dct2d(L, false, X, T, L.cE.p, st_);
             // inverse REDFT01 x REDFT01
-            launch_dgemm(n0, n1, n1, X, P, plane, L.cD1T.p, n1, 0, T, P, plane, nullptr, 0, 2,
-                         st_);
-            launch_dgemm(n0, n1, n0, L.cD0.p, P, 0, T, P, plane, X, P, plane, nullptr, 0, 2, st_);
-            launch_curv_construct(X, plane, src, dst, div, n0, n1, P, partial, st_);
+            double *Z = solvers::curvature_dct2d(L, true, Y, Y == X ? T : X, nullptr, st_);
+            launch_curv_construct(Z, plane, src, dst, div, n0, n1, P, partial, st_);
         },
         final_buf);
 }

@@ -174,6 +174,30 @@ def motion_norms_chain(u, dims: Sequence[int], batch: int = 3):
     return sums.reshape(niter, 2), res.reshape(niter, 8)
 
 
+# ------------------------------------------------------------------ Curvature transforms
+#: line lengths the fast transforms take (powers of two; include/of2d.h)
+DCT_NMIN, DCT_NMAX = 8, 8192
+
+
+def dct2d(a, kind: int, method: int = 1):
+    """Curvature's separable REDFT10 (``kind=10``) or REDFT01 (``kind=1``) of
+    ``a`` (``[dimx, dimy]``), on the device, as one solver iteration runs it:
+    axis y, then axis x, no eigenvalues (include/of2d.h of2d_dct2d).
+    ``method`` 0 takes the GEMMs, 1 the fast line transforms on every axis
+    whose length qualifies.  Returns ``(result [dimx, dimy], (fast_x,
+    fast_y))``."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("a must be [dimx, dimy]")
+    dimx, dimy = a.shape
+    buf = np.ascontiguousarray(a.reshape(-1, order="F")).copy()
+    paths = np.zeros(2, np.int32)
+    L = _lib.lib()
+    check(L.of2d_dct2d(buf, dimx, dimy, int(kind), int(method), paths),
+          L.of2d_gateway_last_error().decode())
+    return buf.reshape((dimx, dimy), order="F"), (int(paths[0]), int(paths[1]))
+
+
 # ------------------------------------------------------------------ object API
 class ImageRegistration:
     """Handle on one registration context (of2d_create ... of2d_destroy).
@@ -182,7 +206,8 @@ class ImageRegistration:
     values, finest level first), ``nscales``, ``reg``, ``params`` (nparams
     floats), ``nrefine``, ``verbose``.  Extra keyword options map to
     ``of2d_set_option`` (``fixed_iters``, ``chunk``, ``device``,
-    ``hs_gradients_from_image``, ``logger_fp64``, ``ngpus``).
+    ``hs_gradients_from_image``, ``logger_fp64``, ``ngpus``,
+    ``curvature_dct``).
     """
 
     def __init__(self, dims: Sequence[int], niter: Sequence[int], nscales: int, reg: int,
@@ -246,6 +271,13 @@ class ImageRegistration:
         n = _lib.lib().of2d_last_errors(self._h, buf, buf.size)
         return buf[: max(n, 0)].copy()
 
+    def curvature_paths(self) -> list:
+        """``(dimx, dimy, fast_x, fast_y)`` per Curvature loop of the last
+        estimate, in execution order (of2d_curvature_paths)."""
+        buf = np.zeros(4 * 1024, np.int32)
+        n = _lib.lib().of2d_curvature_paths(self._h, buf, buf.size)
+        return [tuple(int(v) for v in buf[4 * k: 4 * k + 4]) for k in range(max(n, 0))]
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _lib.lib().of2d_destroy(self._h)
@@ -265,4 +297,4 @@ class ImageRegistration:
 
 
 __all__ = ["Regularisation", "Verbose", "MotionAccumulation", "OpticalFlow2d",
-           "ImageRegistration", "set_print_sink", "Of2dError", "motion_norms"]
+           "ImageRegistration", "set_print_sink", "Of2dError", "motion_norms", "dct2d"]
