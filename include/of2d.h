@@ -301,6 +301,66 @@ int of2d_dct2d(double *a, int dimx, int dimy, int kind, int method, int *paths);
  * entry for tools/curvature_bench.py, not a result. */
 int of2d_dct_time_passes(int dimx, int dimy, int nlaunch, double *us);
 
+/* ---- test and diagnostic entries: one launch of a field / Demons primitive ----
+ * Each entry uploads dense host arrays into pitched device fields, makes one
+ * call of the launch function the solvers call, and copies the result back.
+ * Images are float [dimx*dimy], idx = i + j*dimx; motion fields are float
+ * [dimx*dimy*2], x and y interleaved per pixel (coord2d).  Errors are reported
+ * as by of2d_dct2d (of2d_gateway_last_error).  Not in the reference. */
+/* Image::warp2d of src by u */
+int of2d_prim_warp(const float *src, const float *u, int dimx, int dimy, float *out);
+/* Motion::accumulate: out(x) = v(x) + m_old(x + v(x)) */
+int of2d_prim_accumulate(const float *m_old, const float *v, int dimx, int dimy, float *out);
+/* Fluid's regrid: m_new = accumulate(m_old, est), est0 = 0 (the device buffer
+ * holds est before the launch), Iaux = warp2d(Imov, m_new) */
+int of2d_prim_regrid(const float *m_old, const float *est, const float *Imov, int dimx, int dimy,
+                     float *m_new, float *est0, float *Iaux);
+/* accumulate onto a zero motion, for rows [row0, row0 + nrows) of a dimy-row
+ * grid: v and out hold those nrows rows only */
+int of2d_prim_compose_zero(const float *v, int dimx, int nrows, int row0, int dimy, float *out);
+/* Field::operator+= */
+int of2d_prim_add_motion(const float *a, const float *b, int dimx, int dimy, float *out);
+/* what 0: Image::downSample, 1: Motion::downSample, 2: Motion::upSample from
+ * dxi x dyi to dxo x dyo.  out is in/out: a pixel with no valid tap keeps the
+ * value the caller put there. */
+int of2d_prim_resample(int what, const float *in, int dxi, int dyi, float *out, int dxo, int dyo);
+/* IterativeSolver::set_derivatives in the slab form: dI and It of rows [row0,
+ * row0 + nrows) of the dimx x dimy images Iref and Iaux (whole images in, nrows
+ * rows out; the device slab holds those rows and one ghost row either side) */
+int of2d_prim_gradients(const float *Iref, const float *Iaux, int dimx, int dimy, int row0,
+                        int nrows, float *dI, float *It);
+/* Demons' correspondence force of Imov warped by u against Iref; *status
+ * receives the kernels' status word (bit 0: a zero denominator) */
+int of2d_prim_demons_force(const float *Iref, const float *Imov, const float *u, int dimx,
+                           int dimy, float sigma_i, float sigma_x, float *corr,
+                           unsigned *status);
+/* corr smoothed by the kw x kw Gaussian of `sigma` (Kernel::set_gaussian), then
+ * mode 0: accumulate(u, .), 1: u + ., 2: u, 3: the smoothed corr itself.
+ * *wfull (optional): the kernel's full weight sum as the launch receives it. */
+int of2d_prim_smooth_compose(const float *corr, const float *u, int dimx, int dimy, int kw,
+                             float sigma, int mode, float *out, double *wfull);
+/* out = umid smoothed; sums (optional, double[2]): the fp64 Logger sums
+ * sum |out - prev|, sum |prev| of the launch's block partials.  Without sums
+ * the launch is the one of the default Logger mode (no partials). */
+int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int dimy, int kw,
+                          float sigma, float *out, double *sums);
+/* one Demons correction update (force, sigma_fluid smoothing, motion update by
+ * `mode` as of2d_prim_smooth_compose): the fused kernel where the solver
+ * would take it, the unfused pair elsewhere */
+int of2d_prim_demons_update(const float *Iref, const float *Imov, const float *u, int dimx,
+                            int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
+                            int mode, float *out, unsigned *status);
+/* Motion::exp of f, in place, with the squaring bound the diffeomorphic loop
+ * derives from sigma_i / sigma_x (32 when their ratio is 0 or not finite);
+ * *nsq: the squarings the device counted, *status bit 1: above the bound */
+int of2d_prim_motion_exp(float *f, int dimx, int dimy, float sigma_i, float sigma_x, int *nsq,
+                         unsigned *status);
+/* the boundary copies: Image::set_image, Image::copy_image_to_input,
+ * Motion::copy_motion_to_input (planar double [2*dimx*dimy], x plane first) */
+int of2d_prim_d2f(const double *in, int dimx, int dimy, float *out);
+int of2d_prim_f2d(const float *in, int dimx, int dimy, double *out);
+int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out);
+
 /* ---- library info ---- */
 const char *of2d_version(void);
 int of2d_device_count(int *count);

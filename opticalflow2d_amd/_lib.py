@@ -78,6 +78,28 @@ SIGNATURES = {
                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "of2d_motion_norms": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
     "of2d_motion_norms_chain": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
+    "of2d_prim_warp": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_accumulate": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_regrid": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p]),
+    "of2d_prim_compose_zero": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_add_motion": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_resample": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int]),
+    "of2d_prim_gradients": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p,
+                                      _f32p]),
+    "of2d_prim_demons_force": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
+                                         C.c_float, _f32p, C.POINTER(C.c_uint)]),
+    "of2d_prim_smooth_compose": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.c_int, _f32p, C.POINTER(C.c_double)]),
+    "of2d_prim_smooth_norm": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        _f32p, C.POINTER(C.c_double)]),
+    "of2d_prim_demons_update": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
+                                          C.c_float, C.c_int, C.c_float, C.c_int, _f32p,
+                                          C.POINTER(C.c_uint)]),
+    "of2d_prim_motion_exp": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                       C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
+    "of2d_prim_d2f": (C.c_int, [_f64p, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_f2d": (C.c_int, [_f32p, C.c_int, C.c_int, _f64p]),
+    "of2d_prim_motion_to_planar": (C.c_int, [_f32p, C.c_int, C.c_int, _f64p]),
     "of2d_version": (C.c_char_p, []),
     "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }

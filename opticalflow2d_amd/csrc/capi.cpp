@@ -320,6 +320,322 @@ int of2d_motion_norms_chain(const float *u, int dimx, int dimy, int niter, int b
     return rc;
 }
 
+// ------------------------------------------------------------------ primitives
+// One launch of the function the solvers call, on host arrays: dense float
+// images (idx = i + j*dimx) and interleaved float2 motion fields.
+}  // extern "C"
+
+namespace {
+// a zeroed pitched field holding the dense host array (none: zeros)
+template <class T>
+void upload(of2d::Field<T> &f, const float *host, int dimx, int dimy) {
+    f.alloc(dimx, dimy);
+    const size_t row = (size_t)dimx * sizeof(T);
+    if (host)
+        OF2D_HIP(hipMemcpy2D(f.p, (size_t)f.P * sizeof(T), host, row, row, dimy,
+                             hipMemcpyHostToDevice));
+}
+template <class T>
+void download(float *host, const T *p, int P, int dimx, int dimy) {
+    const size_t row = (size_t)dimx * sizeof(T);
+    OF2D_HIP(hipStreamSynchronize(nullptr));
+    OF2D_HIP(hipMemcpy2D(host, row, p, (size_t)P * sizeof(T), row, dimy, hipMemcpyDeviceToHost));
+}
+// the status word of a context (kStatus* bits), zeroed
+struct StatusWord {
+    of2d::DevArray<unsigned> w;
+    StatusWord() { w.alloc(64); }
+    unsigned read() {
+        unsigned v = 0;
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(&v, w.p, sizeof v, hipMemcpyDeviceToHost));
+        return v;
+    }
+};
+// a Gaussian of the product on the device, as Registration::loop_demons holds
+// kfluid_ / kdiff_: float and double weights, the full weight sum
+struct DeviceGaussian {
+    of2d::DevArray<float> kf;
+    of2d::DevArray<double> kd;
+    double wfull = 0;
+    DeviceGaussian(int kw, float sigma) {
+        const std::vector<double> k = of2d::gaussian_kernel(kw, sigma);
+        std::vector<float> f(k.size());
+        for (size_t t = 0; t < k.size(); t++) f[t] = (float)k[t];
+        kf.alloc(k.size());
+        kd.alloc(k.size());
+        OF2D_HIP(hipMemcpy(kf.p, f.data(), sizeof(float) * f.size(), hipMemcpyHostToDevice));
+        OF2D_HIP(hipMemcpy(kd.p, k.data(), sizeof(double) * k.size(), hipMemcpyHostToDevice));
+        wfull = of2d::full_weight(k, kw);
+    }
+};
+template <class F>
+int prim(bool args_ok, F &&f) {
+    if (!args_ok) return OF2D_ERR_INVALID_ARGUMENT;
+    std::string err;
+    const int rc = guarded(err, f);
+    if (rc != OF2D_OK) g_gateway_err = err;
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int of2d_prim_warp(const float *src, const float *u, int dimx, int dimy, float *out) {
+    return prim(src && u && out && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float> s, d;
+        of2d::Field<float2> m;
+        upload(s, src, dimx, dimy);
+        upload(m, u, dimx, dimy);
+        upload(d, nullptr, dimx, dimy);
+        of2d::launch_warp(s.p, m.p, d.p, dimx, dimy, s.P, nullptr);
+        download(out, d.p, d.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_accumulate(const float *m_old, const float *v, int dimx, int dimy, float *out) {
+    return prim(m_old && v && out && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> mo, c, mn;
+        upload(mo, m_old, dimx, dimy);
+        upload(c, v, dimx, dimy);
+        upload(mn, nullptr, dimx, dimy);
+        of2d::launch_accumulate(mo.p, c.p, mn.p, dimx, dimy, mo.P, nullptr);
+        download(out, mn.p, mn.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_regrid(const float *m_old, const float *est, const float *Imov, int dimx, int dimy,
+                     float *m_new, float *est0, float *Iaux) {
+    return prim(m_old && est && Imov && m_new && est0 && Iaux && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> mo, e, e0, mn;
+        of2d::Field<float> im, ia;
+        upload(mo, m_old, dimx, dimy);
+        upload(e, est, dimx, dimy);
+        upload(e0, est, dimx, dimy);  // not zero: the launch has to clear it
+        upload(mn, nullptr, dimx, dimy);
+        upload(im, Imov, dimx, dimy);
+        upload(ia, nullptr, dimx, dimy);
+        of2d::launch_regrid(mo.p, e.p, e0.p, mn.p, im.p, ia.p, dimx, dimy, mo.P, nullptr);
+        download(m_new, mn.p, mn.P, dimx, dimy);
+        download(est0, e0.p, e0.P, dimx, dimy);
+        download(Iaux, ia.p, ia.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_compose_zero(const float *v, int dimx, int nrows, int row0, int dimy, float *out) {
+    return prim(v && out && dimx > 0 && nrows > 0 && row0 >= 0 && row0 + nrows <= dimy, [&] {
+        of2d::Field<float2> c, o;
+        upload(c, v, dimx, nrows);
+        upload(o, nullptr, dimx, nrows);
+        of2d::launch_compose_zero(c.p, o.p, dimx, nrows, c.P, row0, dimy, nullptr);
+        download(out, o.p, o.P, dimx, nrows);
+    });
+}
+
+int of2d_prim_add_motion(const float *a, const float *b, int dimx, int dimy, float *out) {
+    return prim(a && b && out && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> x, y, o;
+        upload(x, a, dimx, dimy);
+        upload(y, b, dimx, dimy);
+        upload(o, nullptr, dimx, dimy);
+        of2d::launch_add_motion(x.p, y.p, o.p, dimx, dimy, x.P, nullptr);
+        download(out, o.p, o.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_resample(int what, const float *in, int dxi, int dyi, float *out, int dxo, int dyo) {
+    return prim(in && out && dxi > 0 && dyi > 0 && what >= 0 && what <= 2, [&] {
+        // the launches refuse the sizes the reference refuses, before any field
+        if (what == 0) {
+            of2d::Field<float> a, o;
+            if (dxo > 0 && dyo > 0) {
+                upload(a, in, dxi, dyi);
+                upload(o, out, dxo, dyo);
+            }
+            of2d::launch_downsample_image(a.p, dxi, dyi, a.P, o.p, dxo, dyo, o.P, nullptr);
+            download(out, o.p, o.P, dxo, dyo);
+            return;
+        }
+        of2d::Field<float2> a, o;
+        if (dxo > 0 && dyo > 0) {
+            upload(a, in, dxi, dyi);
+            upload(o, out, dxo, dyo);
+        }
+        if (what == 1)
+            of2d::launch_downsample_motion(a.p, dxi, dyi, a.P, o.p, dxo, dyo, o.P, nullptr);
+        else
+            of2d::launch_upsample_motion(a.p, dxi, dyi, a.P, o.p, dxo, dyo, o.P, nullptr);
+        download(out, o.p, o.P, dxo, dyo);
+    });
+}
+
+int of2d_prim_gradients(const float *Iref, const float *Iaux, int dimx, int dimy, int row0,
+                        int nrows, float *dI, float *It) {
+    return prim(Iref && Iaux && dI && It && dimx > 0 && nrows > 0 && row0 >= 0 &&
+                    row0 + nrows <= dimy,
+                [&] {
+                    // the slab's rows, and in its ghost j-lines the neighbours' image rows
+                    of2d::Field<float> r, a, t;
+                    of2d::Field<float2> g;
+                    upload(r, Iref + (size_t)row0 * dimx, dimx, nrows);
+                    upload(a, nullptr, dimx, nrows);
+                    upload(g, nullptr, dimx, nrows);
+                    upload(t, nullptr, dimx, nrows);
+                    const int lo = row0 > 0 ? row0 - 1 : row0;
+                    const int hi = row0 + nrows < dimy ? row0 + nrows + 1 : row0 + nrows;
+                    const size_t row = (size_t)dimx * sizeof(float);
+                    OF2D_HIP(hipMemcpy2D(a.p + (long)(lo - row0) * a.P, (size_t)a.P * sizeof(float),
+                                         Iaux + (size_t)lo * dimx, row, row, hi - lo,
+                                         hipMemcpyHostToDevice));
+                    of2d::launch_gradients_rows(r.p, a.p, g.p, t.p, dimx, nrows, r.P, row0, dimy,
+                                                nullptr);
+                    download(dI, g.p, g.P, dimx, nrows);
+                    download(It, t.p, t.P, dimx, nrows);
+                });
+}
+
+int of2d_prim_demons_force(const float *Iref, const float *Imov, const float *u, int dimx,
+                           int dimy, float sigma_i, float sigma_x, float *corr,
+                           unsigned *status) {
+    return prim(Iref && Imov && u && corr && status && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float> r, m;
+        of2d::Field<float2> f, c;
+        upload(r, Iref, dimx, dimy);
+        upload(m, Imov, dimx, dimy);
+        upload(f, u, dimx, dimy);
+        upload(c, nullptr, dimx, dimy);
+        StatusWord st;
+        // Demons.cpp:48-49
+        of2d::launch_demons_force(r.p, m.p, f.p, c.p, dimx, dimy, r.P, sigma_i * sigma_i,
+                                  sigma_x * sigma_x, st.w.p, nullptr);
+        download(corr, c.p, c.P, dimx, dimy);
+        *status = st.read();
+    });
+}
+
+int of2d_prim_smooth_compose(const float *corr, const float *u, int dimx, int dimy, int kw,
+                             float sigma, int mode, float *out, double *wfull) {
+    return prim(corr && u && out && dimx > 0 && dimy > 0 && kw >= 1 && mode >= 0 && mode <= 3,
+                [&] {
+                    of2d::Field<float2> c, f, o;
+                    upload(c, corr, dimx, dimy);
+                    upload(f, u, dimx, dimy);
+                    upload(o, nullptr, dimx, dimy);
+                    DeviceGaussian g(kw, sigma);
+                    if (wfull) *wfull = g.wfull;
+                    of2d::launch_smooth_compose(c.p, f.p, o.p, dimx, dimy, c.P, g.kf.p, g.kd.p, kw,
+                                                g.wfull, mode, nullptr);
+                    download(out, o.p, o.P, dimx, dimy);
+                });
+}
+
+int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int dimy, int kw,
+                          float sigma, float *out, double *sums) {
+    return prim(umid && prev && out && dimx > 0 && dimy > 0 && kw >= 1, [&] {
+        of2d::Field<float2> m, p, o;
+        upload(m, umid, dimx, dimy);
+        upload(p, prev, dimx, dimy);
+        upload(o, nullptr, dimx, dimy);
+        DeviceGaussian g(kw, sigma);
+        const int nb = of2d::conv_nblocks(dimx, dimy);
+        of2d::DevArray<double> part, red;
+        part.alloc(2 * (size_t)nb);
+        red.alloc(2);
+        // sums: the Logger partials reduced as the fp64 Logger mode reduces
+        // them; none: the launch of the default mode, without partials
+        of2d::launch_smooth_norm(m.p, p.p, o.p, dimx, dimy, m.P, g.kf.p, g.kd.p, kw, g.wfull,
+                                 sums ? part.p : nullptr, nullptr);
+        if (sums) {
+            of2d::launch_reduce_partials(part.p, nb, 1, red.p, nullptr);
+            OF2D_HIP(hipStreamSynchronize(nullptr));
+            OF2D_HIP(hipMemcpy(sums, red.p, 2 * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        download(out, o.p, o.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_demons_update(const float *Iref, const float *Imov, const float *u, int dimx,
+                            int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
+                            int mode, float *out, unsigned *status) {
+    return prim(Iref && Imov && u && out && status && dimx > 0 && dimy > 0 && kw >= 1 &&
+                    mode >= 0 && mode <= 3,
+                [&] {
+                    of2d::Field<float> r, m;
+                    of2d::Field<float2> f, c, o;
+                    upload(r, Iref, dimx, dimy);
+                    upload(m, Imov, dimx, dimy);
+                    upload(f, u, dimx, dimy);
+                    upload(c, nullptr, dimx, dimy);
+                    upload(o, nullptr, dimx, dimy);
+                    DeviceGaussian g(kw, sigma_fluid);
+                    StatusWord st;
+                    of2d::launch_demons_update(r.p, m.p, f.p, c.p, o.p, dimx, dimy, r.P,
+                                               sigma_i * sigma_i, sigma_x * sigma_x, g.kf.p,
+                                               g.kd.p, kw, g.wfull, mode, st.w.p, nullptr);
+                    download(out, o.p, o.P, dimx, dimy);
+                    *status = st.read();
+                });
+}
+
+int of2d_prim_motion_exp(float *f, int dimx, int dimy, float sigma_i, float sigma_x, int *nsq,
+                         unsigned *status) {
+    return prim(f && nsq && status && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> a, b;
+        upload(a, f, dimx, dimy);
+        upload(b, nullptr, dimx, dimy);
+        constexpr int nparts = 256;  // Registration::loop_demons
+        of2d::DevArray<float> part, maxabs;
+        of2d::DevArray<int> n;
+        part.alloc(nparts);
+        maxabs.alloc(1);
+        n.alloc(1);
+        StatusWord st;
+        float2 *res = nullptr;
+        of2d::launch_motion_exp(a.p, b.p, dimx, dimy, a.P,
+                                of2d::exp_squarings_bound(sigma_i * sigma_i, sigma_x * sigma_x),
+                                part.p, nparts, n.p, maxabs.p, st.w.p, &res, nullptr);
+        download(f, res, a.P, dimx, dimy);
+        OF2D_HIP(hipMemcpy(nsq, n.p, sizeof(int), hipMemcpyDeviceToHost));
+        *status = st.read();
+    });
+}
+
+int of2d_prim_d2f(const double *in, int dimx, int dimy, float *out) {
+    return prim(in && out && dimx > 0 && dimy > 0, [&] {
+        of2d::DevArray<double> d;
+        d.alloc((size_t)dimx * dimy);
+        OF2D_HIP(hipMemcpy(d.p, in, sizeof(double) * d.n, hipMemcpyHostToDevice));
+        of2d::Field<float> o;
+        upload(o, nullptr, dimx, dimy);
+        of2d::launch_d2f(d.p, dimx, dimy, o.p, o.P, 0, nullptr);
+        download(out, o.p, o.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_f2d(const float *in, int dimx, int dimy, double *out) {
+    return prim(in && out && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float> a;
+        upload(a, in, dimx, dimy);
+        of2d::DevArray<double> d;
+        d.alloc((size_t)dimx * dimy);
+        of2d::launch_f2d(a.p, a.P, dimx, dimy, d.p, nullptr);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(out, d.p, sizeof(double) * d.n, hipMemcpyDeviceToHost));
+    });
+}
+
+int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out) {
+    return prim(m && out && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> a;
+        upload(a, m, dimx, dimy);
+        of2d::DevArray<double> d;
+        d.alloc(2 * (size_t)dimx * dimy);
+        of2d::launch_motion_to_planar(a.p, a.P, dimx, dimy, d.p, nullptr);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(out, d.p, sizeof(double) * d.n, hipMemcpyDeviceToHost));
+    });
+}
+
 // ------------------------------------------------------------------ gateway
 // static ImageRegistration *myImageRegistration (WrapperOpticalFlow2d.cpp:13)
 static of2d_ctx *g_single = nullptr;

@@ -689,10 +689,11 @@ __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_k
 // sum ||prev|| per block (fixed order).  The partials feed the fp64 Logger
 // mode only (fixed iterations, logger_fp64; the default mode takes the
 // reference's float sums from seqnorm_kernels.hip and launches NORM = false):
-// an approximation of Motion::norm's float running sum at any precision, so
-// the magnitudes take the hardware square root (<= 1 ulp) rather than the
-// correctly rounded sequence.  The R previous-motion loads of a thread are
-// issued together after the convolution, whose registers they reuse.
+// Motion::norm's magnitudes in fp64 as the reference takes them, summed as an
+// fp64 tree instead of its float running sum (the fp64 sum of the same terms
+// to ~1e-16 relative, tests/test_gpu_primitives.py).  The R previous-motion
+// loads of a thread are issued together after the convolution, whose
+// registers they reuse.
 template <int KW, int R = kCr, bool PK = true, bool W1 = false, bool NORM = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KW == 7 ? 7 : 8))) void smooth_norm_kernel(const float2 *__restrict__ umid,
                                                           const float2 *__restrict__ prev,
@@ -731,9 +732,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KW == 7 ? 7
             if (!conv_all && !has[k]) v = umid[idx];
             out[idx] = v;
             if (NORM) {
-                const float ex = v.x - pv[k].x, ey = v.y - pv[k].y;
-                sd += (double)__builtin_amdgcn_sqrtf(ex * ex + ey * ey);
-                sp += (double)__builtin_amdgcn_sqrtf(pv[k].x * pv[k].x + pv[k].y * pv[k].y);
+                // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
+                const double ex = (double)(v.x - pv[k].x), ey = (double)(v.y - pv[k].y);
+                const double qx = (double)pv[k].x, qy = (double)pv[k].y;
+                sd += sqrt(ex * ex + ey * ey);
+                sp += sqrt(qx * qx + qy * qy);
             }
         }
     }

@@ -329,5 +329,10 @@ bool valid_regularisation_parameters(int reg, unsigned nparams);
 
 // Kernel::set_gaussian (src/Kernel.cpp:45-73): expf in float, normalised in double
 std::vector<double> gaussian_kernel(int kw, float sigma);
+// the weight sum of a pixel whose taps are all valid, in the reference's
+// summation order (Field.tpp:242-256)
+double full_weight(const std::vector<double> &k, int kw);
+// launch_motion_exp's bound on the squaring count for Demons' parameters
+int exp_squarings_bound(float sigma_isq, float sigma_xsq);
 
 }  // namespace of2d

@@ -69,12 +69,25 @@ struct DemonsKernels {
     }
 };
 
-static double full_weight(const std::vector<double> &k, int kw) {
+double full_weight(const std::vector<double> &k, int kw) {
     const int c = (kw - 1) / 2;
     double w = 0.0;
     for (int ii = -c; ii <= c; ii++)
         for (int jj = -c; jj <= c; jj++) w += k[(ii + c) + (jj + c) * kw];
     return w;
+}
+
+// scaling-and-squaring bound: |c| <= 1/(2 sqrt(k)), k = sigma_i^2/sigma_x^2 (AM-GM on
+// Demons.cpp:57's denominator), smoothing keeps the bound, maxabs <= sqrt(2)|c|
+int exp_squarings_bound(float sigma_isq, float sigma_xsq) {
+    int nsq_max = 32;
+    const double k = (double)sigma_isq / (double)sigma_xsq;
+    if (k > 0 && std::isfinite(k)) {
+        const double ma = std::sqrt(2.0) / (2.0 * std::sqrt(k));
+        nsq_max = std::max(0, (int)std::ceil(1.0 + std::log2(ma)) + 2);
+        nsq_max = std::min(nsq_max, 32);
+    }
+    return nsq_max;
 }
 
 // ImageRegistrationDemons::estimate_motion_at_current_resolution loop body
@@ -112,17 +125,7 @@ int Registration::loop_demons(Level &L, int niter, int &final_buf) {
         const int accum = (int)params_[5];  // static_cast<MotionAccumulation>((int) regparams[5])
         mode = accum == 0 ? 0 : (accum == 1 ? 1 : 2);
     }
-    // scaling-and-squaring bound: |c| <= 1/(2 sqrt(k)), k = sigma_i^2/sigma_x^2 (AM-GM on
-    // Demons.cpp:57's denominator), smoothing keeps the bound, maxabs <= sqrt(2)|c|
-    int nsq_max = 32;
-    if (diffeo) {
-        const double k = (double)sigma_isq / (double)sigma_xsq;
-        if (k > 0 && std::isfinite(k)) {
-            const double ma = std::sqrt(2.0) / (2.0 * std::sqrt(k));
-            nsq_max = std::max(0, (int)std::ceil(1.0 + std::log2(ma)) + 2);
-            nsq_max = std::min(nsq_max, 32);
-        }
-    }
+    const int nsq_max = diffeo ? exp_squarings_bound(sigma_isq, sigma_xsq) : 32;
     const int nb = conv_nblocks(L.dx, L.dy);
     const int nparts = 256;
     // the default Logger mode sums the reference's float norms itself

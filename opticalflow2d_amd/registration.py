@@ -198,6 +198,185 @@ def dct2d(a, kind: int, method: int = 1):
     return buf.reshape((dimx, dimy), order="F"), (int(paths[0]), int(paths[1]))
 
 
+# ------------------------------------------------------------------ primitives
+class prim:
+    """One launch each of the field and Demons primitives the solvers call
+    (include/of2d.h, "test and diagnostic entries").  Arrays are float32 in the
+    C-ABI's own layout: an image is ``[dimy, dimx]`` and a motion field
+    ``[dimy, dimx, 2]`` in C order (idx = i + j*dimx, x and y interleaved).
+    Results are new arrays; bits are never touched on the way."""
+
+    @staticmethod
+    def _f(a, shape=None):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if shape is not None and a.shape != tuple(shape):
+            raise ValueError(f"array is {a.shape}, expected {tuple(shape)}")
+        return a
+
+    @staticmethod
+    def _call(name, *args):
+        L = _lib.lib()
+        check(getattr(L, name)(*args), L.of2d_gateway_last_error().decode())
+
+    @classmethod
+    def warp(cls, src, u):
+        src = cls._f(src)
+        dimy, dimx = src.shape
+        out = np.zeros_like(src)
+        cls._call("of2d_prim_warp", src, cls._f(u, (dimy, dimx, 2)), dimx, dimy, out)
+        return out
+
+    @classmethod
+    def accumulate(cls, m_old, v):
+        m_old = cls._f(m_old)
+        dimy, dimx, _ = m_old.shape
+        out = np.zeros_like(m_old)
+        cls._call("of2d_prim_accumulate", m_old, cls._f(v, m_old.shape), dimx, dimy, out)
+        return out
+
+    @classmethod
+    def regrid(cls, m_old, est, Imov):
+        """Returns ``(m_new, est0, Iaux)``."""
+        m_old = cls._f(m_old)
+        dimy, dimx, _ = m_old.shape
+        m_new, est0 = np.zeros_like(m_old), np.zeros_like(m_old)
+        Iaux = np.zeros((dimy, dimx), np.float32)
+        cls._call("of2d_prim_regrid", m_old, cls._f(est, m_old.shape),
+                  cls._f(Imov, (dimy, dimx)), dimx, dimy, m_new, est0, Iaux)
+        return m_new, est0, Iaux
+
+    @classmethod
+    def compose_zero(cls, v, row0=0, dimy=None):
+        """``v`` holds rows ``[row0, row0 + nrows)`` of a ``dimy``-row grid."""
+        v = cls._f(v)
+        nrows, dimx, _ = v.shape
+        out = np.zeros_like(v)
+        cls._call("of2d_prim_compose_zero", v, dimx, nrows, int(row0),
+                  nrows if dimy is None else int(dimy), out)
+        return out
+
+    @classmethod
+    def add_motion(cls, a, b):
+        a = cls._f(a)
+        dimy, dimx, _ = a.shape
+        out = np.zeros_like(a)
+        cls._call("of2d_prim_add_motion", a, cls._f(b, a.shape), dimx, dimy, out)
+        return out
+
+    @classmethod
+    def _resample(cls, what, a, out):
+        a, out = cls._f(a), cls._f(out).copy()
+        cls._call("of2d_prim_resample", what, a, a.shape[1], a.shape[0], out, out.shape[1],
+                  out.shape[0])
+        return out
+
+    @classmethod
+    def downsample_image(cls, a, out):
+        """``out`` is the target's content before the call (kept where no tap
+        is valid); the result is a copy."""
+        return cls._resample(0, a, out)
+
+    @classmethod
+    def downsample_motion(cls, a, out):
+        return cls._resample(1, a, out)
+
+    @classmethod
+    def upsample_motion(cls, a, out):
+        return cls._resample(2, a, out)
+
+    @classmethod
+    def gradients(cls, Iref, Iaux, row0=0, nrows=None):
+        """``(dI [nrows, dimx, 2], It [nrows, dimx])`` of rows ``[row0, row0 +
+        nrows)`` of the whole images, by the slab form of the launch."""
+        Iref = cls._f(Iref)
+        dimy, dimx = Iref.shape
+        nrows = dimy - row0 if nrows is None else int(nrows)
+        dI = np.zeros((max(nrows, 0), dimx, 2), np.float32)
+        It = np.zeros((max(nrows, 0), dimx), np.float32)
+        cls._call("of2d_prim_gradients", Iref, cls._f(Iaux, Iref.shape), dimx, dimy, int(row0),
+                  nrows, dI, It)
+        return dI, It
+
+    @classmethod
+    def demons_force(cls, Iref, Imov, u, sigma_i, sigma_x):
+        """Returns ``(corr, status)``."""
+        Iref = cls._f(Iref)
+        dimy, dimx = Iref.shape
+        out = np.zeros((dimy, dimx, 2), np.float32)
+        st = C.c_uint(0)
+        cls._call("of2d_prim_demons_force", Iref, cls._f(Imov, Iref.shape),
+                  cls._f(u, out.shape), dimx, dimy, float(sigma_i), float(sigma_x), out,
+                  C.byref(st))
+        return out, int(st.value)
+
+    @classmethod
+    def smooth_compose(cls, corr, u, kw, sigma, mode):
+        """Returns ``(out, wfull)``."""
+        corr = cls._f(corr)
+        dimy, dimx, _ = corr.shape
+        out = np.zeros_like(corr)
+        w = C.c_double(0)
+        cls._call("of2d_prim_smooth_compose", corr, cls._f(u, corr.shape), dimx, dimy, int(kw),
+                  float(sigma), int(mode), out, C.byref(w))
+        return out, float(w.value)
+
+    @classmethod
+    def smooth_norm(cls, umid, prev, kw, sigma, partials=True):
+        """Returns ``(out, sums)``: ``sums`` the two fp64 Logger sums, or None
+        from the launch without partials."""
+        umid = cls._f(umid)
+        dimy, dimx, _ = umid.shape
+        out = np.zeros_like(umid)
+        sums = (C.c_double * 2)()
+        cls._call("of2d_prim_smooth_norm", umid, cls._f(prev, umid.shape), dimx, dimy, int(kw),
+                  float(sigma), out, sums if partials else None)
+        return out, ((float(sums[0]), float(sums[1])) if partials else None)
+
+    @classmethod
+    def demons_update(cls, Iref, Imov, u, sigma_i, sigma_x, kw, sigma_fluid, mode):
+        """Returns ``(out, status)``."""
+        Iref = cls._f(Iref)
+        dimy, dimx = Iref.shape
+        out = np.zeros((dimy, dimx, 2), np.float32)
+        st = C.c_uint(0)
+        cls._call("of2d_prim_demons_update", Iref, cls._f(Imov, Iref.shape),
+                  cls._f(u, out.shape), dimx, dimy, float(sigma_i), float(sigma_x), int(kw),
+                  float(sigma_fluid), int(mode), out, C.byref(st))
+        return out, int(st.value)
+
+    @classmethod
+    def motion_exp(cls, f, sigma_i=0.0, sigma_x=1.0):
+        """Returns ``(exp(f), squarings, status)``."""
+        f = cls._f(f).copy()
+        dimy, dimx, _ = f.shape
+        n, st = C.c_int(0), C.c_uint(0)
+        cls._call("of2d_prim_motion_exp", f, dimx, dimy, float(sigma_i), float(sigma_x),
+                  C.byref(n), C.byref(st))
+        return f, int(n.value), int(st.value)
+
+    @classmethod
+    def d2f(cls, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        out = np.zeros(a.shape, np.float32)
+        cls._call("of2d_prim_d2f", a, a.shape[1], a.shape[0], out)
+        return out
+
+    @classmethod
+    def f2d(cls, a):
+        a = cls._f(a)
+        out = np.zeros(a.shape, np.float64)
+        cls._call("of2d_prim_f2d", a, a.shape[1], a.shape[0], out)
+        return out
+
+    @classmethod
+    def motion_to_planar(cls, m):
+        """``[2, dimy, dimx]`` float64, the x plane first."""
+        m = cls._f(m)
+        out = np.zeros((2,) + m.shape[:2], np.float64)
+        cls._call("of2d_prim_motion_to_planar", m, m.shape[1], m.shape[0], out)
+        return out
+
+
 # ------------------------------------------------------------------ object API
 class ImageRegistration:
     """Handle on one registration context (of2d_create ... of2d_destroy).
@@ -297,4 +476,4 @@ class ImageRegistration:
 
 
 __all__ = ["Regularisation", "Verbose", "MotionAccumulation", "OpticalFlow2d",
-           "ImageRegistration", "set_print_sink", "Of2dError", "motion_norms", "dct2d"]
+           "ImageRegistration", "set_print_sink", "Of2dError", "motion_norms", "dct2d", "prim"]

@@ -117,3 +117,16 @@ def test_demons_config3_full_size_4096(gpu, oracle):
     assert g["iters"] == w["iters"] == [2]
     assert np.array_equal(g["motion"], w["motion"])
     assert np.array_equal(g["warped"], w["warped"])
+
+
+@pytest.mark.parametrize("dims,nscales,kw", [((83, 70), 1, 5), ((40, 24), 2, 7)])
+def test_thirion_odd_size_pyramid(gpu, oracle, dims, nscales, kw):
+    """Pyramids whose levels do not halve exactly (83x70 -> 41x35), and one
+    whose coarsest level (10x6) is narrower than two kernels of width 7, where
+    the linear-index tap rule wraps across j-lines."""
+    ref, mov = S.texture_pair(dims[0], seed=dims[0] + kw, ny=dims[1])
+    niter = [6] * (nscales + 1)
+    g, w = both(oracle, dims, niter, nscales, 3, [1.0, 0.25, 1.5, 2.0, kw, 0], 1, ref, mov)
+    assert g["iters"] == w["iters"]
+    assert np.array_equal(g["motion"], w["motion"])
+    assert np.array_equal(g["warped"], w["warped"])

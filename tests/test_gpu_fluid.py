@@ -176,3 +176,15 @@ def test_fluid_break_and_regrid_pyramid(gpu, oracle):
     assert np.array_equal(g["motion"], w["motion"])
     assert np.array_equal(g["warped"], w["warped"])
     assert body(gt) == body(ot)
+
+
+def test_fluid_odd_size_pyramid(gpu, oracle):
+    """83x70 -> 41x35: the coarse level drops the last column of the images and
+    its motion comes back up through the ratio 83/41."""
+    ref, mov = S.shifted_disk(83)
+    ref, mov = ref[:, :70], mov[:, :70]
+    g, w, gt, ot = run_both(gpu, oracle, (83, 70), [8, 8], 1, 5, [0.25, 0.0], 1, ref, mov)
+    assert g["iters"] == w["iters"]
+    assert np.array_equal(g["motion"], w["motion"])
+    assert np.array_equal(g["warped"], w["warped"])
+    assert body(gt) == body(ot)

@@ -280,3 +280,19 @@ def test_hs_16384_interior_matches_cropped_oracle(gpu, oracle):
         xl, xh = (0 if x0 == 0 else margin), (c if x0 + c == n else c - margin)
         yl, yh = (0 if y0 == 0 else margin), (c if y0 + c == n else c - margin)
         assert np.array_equal(m[x0 + xl:x0 + xh, y0 + yl:y0 + yh], w[xl:xh, yl:yh]), (x0, y0)
+
+
+@pytest.mark.parametrize("dims,nrefine", [((83, 70), 2), ((37, 23), 1)])
+def test_odd_size_pyramid(gpu, oracle, dims, nrefine):
+    """Levels that do not halve exactly (83x70 -> 41x35, 37x23 -> 18x11): the
+    downsampling drops the last column or row and the motion comes back up
+    through a non-integer ratio."""
+    ref, mov = S.texture_pair(dims[0], seed=dims[0] + dims[1], ny=dims[1])
+    niter = [8, 8, 8]
+    with ImageRegistration(dims, niter, 2, 0, [0.3], nrefine) as r:
+        r.register(ref, mov)
+        m, w, it = r.motion(), r.warp(mov), r.iterations()
+    o = oracle_run(oracle, dims, niter, 2, 0, [0.3], nrefine, ref, mov)
+    assert it == o["iters"]
+    assert np.array_equal(m, o["motion"])
+    assert np.array_equal(w, o["warped"])
