@@ -120,8 +120,30 @@ int of2d_last_errors(const of2d_ctx *ctx, float *out, int cap);
  *   any other axis keeps its GEMM (a 64 x 37 level runs axis x fast and axis y
  *   by GEMM), and no cosine matrix is built for a fast axis.  The two agree to
  *   fp64 rounding (a different summation order); of2d_curvature_paths tells
- *   what ran.  May be changed between of2d_estimate calls. */
+ *   what ran.  May be changed between of2d_estimate calls.
+ *   "demons_separable" (0 = default / 1; anything else is refused): how the
+ *   Demons solvers smooth with their two Gaussians.  0: the reference's direct
+ *   kw x kw convolution, bit for bit.  1: on every pixel whose kw x kw taps all
+ *   have their linear index inside the field, a row pass along the linear
+ *   index and then a column pass with the fp64 row / column marginals of the
+ *   same normalised table (about 2 kw multiply-adds per pixel instead of
+ *   kw^2); every other pixel (the first and last (kw-1)/2 j-lines and up to
+ *   (kw-1)/2 pixels of the adjacent line) keeps the direct form bit for bit.
+ *   The two differ by fp32 rounding only (1e-4 px on whole registrations,
+ *   DESIGN.md 4.2).  Taken per level for every odd kw in [3, OF2D_SEP_KW_MAX]
+ *   on a level with dimx >= kw; an even kw, kw = 1, kw > OF2D_SEP_KW_MAX or a
+ *   narrower level runs the direct form for the whole level;
+ *   of2d_demons_paths tells what ran.  May be changed between of2d_estimate
+ *   calls; ignored by the other solvers. */
 int of2d_set_option(of2d_ctx *ctx, const char *key, double value);
+/* the widest kernel "demons_separable" takes */
+#define OF2D_SEP_KW_MAX 15
+/* the Demons loops of the last of2d_estimate, one per (level, refine) in
+ * execution order: four ints {dimx, dimy, kw, separable} each (the level's
+ * size, the kernel width and 1 when the loop smoothed with the separable
+ * kernels, 0 with the direct ones), up to cap ints into out; returns the
+ * number of loops (0 for another solver) */
+int of2d_demons_paths(const of2d_ctx *ctx, int *out, int cap);
 /* line lengths the fast transforms of "curvature_dct" take (powers of two):
  * the longest is the longest x | y line pair that fits a compute unit's LDS */
 #define OF2D_DCT_NMIN 8
@@ -350,6 +372,19 @@ int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int di
 int of2d_prim_demons_update(const float *Iref, const float *Imov, const float *u, int dimx,
                             int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
                             int mode, float *out, unsigned *status);
+/* the three launches above with the smoothing chosen: method 0 the direct
+ * convolution, 1 the separable one where "demons_separable" would take it
+ * (of2d_set_option) and the direct one elsewhere; *path: 1 when the separable
+ * kernels ran, 0 the direct ones.  Another method is refused before any
+ * device work. */
+int of2d_prim_smooth_compose_m(const float *corr, const float *u, int dimx, int dimy, int kw,
+                               float sigma, int mode, float *out, double *wfull, int method,
+                               int *path);
+int of2d_prim_smooth_norm_m(const float *umid, const float *prev, int dimx, int dimy, int kw,
+                            float sigma, float *out, double *sums, int method, int *path);
+int of2d_prim_demons_update_m(const float *Iref, const float *Imov, const float *u, int dimx,
+                              int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
+                              int mode, float *out, unsigned *status, int method, int *path);
 /* Motion::exp of f, in place, with the squaring bound the diffeomorphic loop
  * derives from sigma_i / sigma_x (32 when their ratio is 0 or not finite);
  * *nsq: the squarings the device counted, *status bit 1: above the bound */

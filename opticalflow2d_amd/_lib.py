@@ -44,6 +44,7 @@ SIGNATURES = {
     "of2d_last_errors": (C.c_int, [C.c_void_p, _f32p, C.c_int]),
     "of2d_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "of2d_curvature_paths": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
+    "of2d_demons_paths": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "of2d_dct2d": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p]),
     "of2d_dct_time_passes": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
     "of2d_gateway": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
@@ -95,6 +96,15 @@ SIGNATURES = {
     "of2d_prim_demons_update": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
                                           C.c_float, C.c_int, C.c_float, C.c_int, _f32p,
                                           C.POINTER(C.c_uint)]),
+    "of2d_prim_smooth_compose_m": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.c_int, _f32p, C.POINTER(C.c_double), C.c_int,
+                                             C.POINTER(C.c_int)]),
+    "of2d_prim_smooth_norm_m": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          _f32p, C.POINTER(C.c_double), C.c_int,
+                                          C.POINTER(C.c_int)]),
+    "of2d_prim_demons_update_m": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
+                                            C.c_float, C.c_int, C.c_float, C.c_int, _f32p,
+                                            C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int)]),
     "of2d_prim_motion_exp": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_float, C.c_float,
                                        C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "of2d_prim_d2f": (C.c_int, [_f64p, C.c_int, C.c_int, _f32p]),

@@ -162,6 +162,15 @@ int of2d_curvature_paths(const of2d_ctx *ctx, int *out, int cap) {
     return (int)v.size() / 4;
 }
 
+int of2d_demons_paths(const of2d_ctx *ctx, int *out, int cap) {
+    if (!ctx) return -1;
+    const auto &v = ctx->reg->demons_paths();
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size() / 4;
+}
+
+static_assert(OF2D_SEP_KW_MAX == of2d::kSepKwMax,
+              "include/of2d.h documents the separable smoothing's widths");
 static_assert(OF2D_DCT_NMIN == of2d::kDctMinN && OF2D_DCT_NMAX == of2d::kDctMaxN,
               "include/of2d.h documents the fast transform's lengths");
 
@@ -357,7 +366,10 @@ struct StatusWord {
 struct DeviceGaussian {
     of2d::DevArray<float> kf;
     of2d::DevArray<double> kd;
+    of2d::DevArray<float> gs;  // gaussian_marginals
     double wfull = 0;
+    // the launches' gs argument for `method`
+    const float *factors(int method) const { return method ? gs.p : nullptr; }
     DeviceGaussian(int kw, float sigma) {
         const std::vector<double> k = of2d::gaussian_kernel(kw, sigma);
         std::vector<float> f(k.size());
@@ -367,6 +379,9 @@ struct DeviceGaussian {
         OF2D_HIP(hipMemcpy(kf.p, f.data(), sizeof(float) * f.size(), hipMemcpyHostToDevice));
         OF2D_HIP(hipMemcpy(kd.p, k.data(), sizeof(double) * k.size(), hipMemcpyHostToDevice));
         wfull = of2d::full_weight(k, kw);
+        const std::vector<float> g = of2d::gaussian_marginals(k, kw);
+        gs.alloc(g.size());
+        OF2D_HIP(hipMemcpy(gs.p, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
     }
 };
 template <class F>
@@ -515,7 +530,15 @@ int of2d_prim_demons_force(const float *Iref, const float *Imov, const float *u,
 
 int of2d_prim_smooth_compose(const float *corr, const float *u, int dimx, int dimy, int kw,
                              float sigma, int mode, float *out, double *wfull) {
-    return prim(corr && u && out && dimx > 0 && dimy > 0 && kw >= 1 && mode >= 0 && mode <= 3,
+    int path = 0;
+    return of2d_prim_smooth_compose_m(corr, u, dimx, dimy, kw, sigma, mode, out, wfull, 0, &path);
+}
+
+int of2d_prim_smooth_compose_m(const float *corr, const float *u, int dimx, int dimy, int kw,
+                               float sigma, int mode, float *out, double *wfull, int method,
+                               int *path) {
+    return prim(corr && u && out && dimx > 0 && dimy > 0 && kw >= 1 && mode >= 0 && mode <= 3 &&
+                    path && (method == 0 || method == 1),
                 [&] {
                     of2d::Field<float2> c, f, o;
                     upload(c, corr, dimx, dimy);
@@ -523,15 +546,23 @@ int of2d_prim_smooth_compose(const float *corr, const float *u, int dimx, int di
                     upload(o, nullptr, dimx, dimy);
                     DeviceGaussian g(kw, sigma);
                     if (wfull) *wfull = g.wfull;
-                    of2d::launch_smooth_compose(c.p, f.p, o.p, dimx, dimy, c.P, g.kf.p, g.kd.p, kw,
-                                                g.wfull, mode, nullptr);
+                    *path = of2d::launch_smooth_compose(c.p, f.p, o.p, dimx, dimy, c.P, g.kf.p,
+                                                        g.kd.p, kw, g.wfull, mode, nullptr,
+                                                        g.factors(method));
                     download(out, o.p, o.P, dimx, dimy);
                 });
 }
 
 int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int dimy, int kw,
                           float sigma, float *out, double *sums) {
-    return prim(umid && prev && out && dimx > 0 && dimy > 0 && kw >= 1, [&] {
+    int path = 0;
+    return of2d_prim_smooth_norm_m(umid, prev, dimx, dimy, kw, sigma, out, sums, 0, &path);
+}
+
+int of2d_prim_smooth_norm_m(const float *umid, const float *prev, int dimx, int dimy, int kw,
+                            float sigma, float *out, double *sums, int method, int *path) {
+    return prim(umid && prev && out && dimx > 0 && dimy > 0 && kw >= 1 && path &&
+                    (method == 0 || method == 1), [&] {
         of2d::Field<float2> m, p, o;
         upload(m, umid, dimx, dimy);
         upload(p, prev, dimx, dimy);
@@ -543,8 +574,9 @@ int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int di
         red.alloc(2);
         // sums: the Logger partials reduced as the fp64 Logger mode reduces
         // them; none: the launch of the default mode, without partials
-        of2d::launch_smooth_norm(m.p, p.p, o.p, dimx, dimy, m.P, g.kf.p, g.kd.p, kw, g.wfull,
-                                 sums ? part.p : nullptr, nullptr);
+        *path = of2d::launch_smooth_norm(m.p, p.p, o.p, dimx, dimy, m.P, g.kf.p, g.kd.p, kw,
+                                         g.wfull, sums ? part.p : nullptr, nullptr,
+                                         g.factors(method));
         if (sums) {
             of2d::launch_reduce_partials(part.p, nb, 1, red.p, nullptr);
             OF2D_HIP(hipStreamSynchronize(nullptr));
@@ -557,8 +589,16 @@ int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int di
 int of2d_prim_demons_update(const float *Iref, const float *Imov, const float *u, int dimx,
                             int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
                             int mode, float *out, unsigned *status) {
+    int path = 0;
+    return of2d_prim_demons_update_m(Iref, Imov, u, dimx, dimy, sigma_i, sigma_x, kw, sigma_fluid,
+                                     mode, out, status, 0, &path);
+}
+
+int of2d_prim_demons_update_m(const float *Iref, const float *Imov, const float *u, int dimx,
+                              int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
+                              int mode, float *out, unsigned *status, int method, int *path) {
     return prim(Iref && Imov && u && out && status && dimx > 0 && dimy > 0 && kw >= 1 &&
-                    mode >= 0 && mode <= 3,
+                    mode >= 0 && mode <= 3 && path && (method == 0 || method == 1),
                 [&] {
                     of2d::Field<float> r, m;
                     of2d::Field<float2> f, c, o;
@@ -569,9 +609,10 @@ int of2d_prim_demons_update(const float *Iref, const float *Imov, const float *u
                     upload(o, nullptr, dimx, dimy);
                     DeviceGaussian g(kw, sigma_fluid);
                     StatusWord st;
-                    of2d::launch_demons_update(r.p, m.p, f.p, c.p, o.p, dimx, dimy, r.P,
-                                               sigma_i * sigma_i, sigma_x * sigma_x, g.kf.p,
-                                               g.kd.p, kw, g.wfull, mode, st.w.p, nullptr);
+                    *path = of2d::launch_demons_update(
+                        r.p, m.p, f.p, c.p, o.p, dimx, dimy, r.P, sigma_i * sigma_i,
+                        sigma_x * sigma_x, g.kf.p, g.kd.p, kw, g.wfull, mode, st.w.p, nullptr,
+                        g.factors(method));
                     download(out, o.p, o.P, dimx, dimy);
                     *status = st.read();
                 });

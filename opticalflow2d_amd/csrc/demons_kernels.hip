@@ -22,12 +22,19 @@
 // taps past an x-edge wrap into the neighbouring j-line), the sum runs ii (x)
 // outer / jj (y) inner in fp32 with (float) weights, and it is normalised by
 // the fp64 sum of the valid weights cast to float.  A separable form cannot
-// reproduce that rounding, so the direct form is the one shipped; its x and y
+// reproduce that rounding, so the direct form is the default; its x and y
 // components are summed as one packed pair (v_pk_mul_f32 + v_pk_add_f32 round
 // exactly like the scalar multiply and add).
+// Option "demons_separable": on the pixels whose taps all lie in [0, N) (the
+// reference's interior predicate) a row pass along the linear index with the
+// table's fp64 row marginals, then a column pass with its column marginals
+// (sepR below; every odd kw in [3, OF2D_SEP_KW_MAX]).  The other pixels keep
+// the direct form bit for bit.  Rounding differs from the direct form on the
+// interior pixels only.
 #include "of2d_device.h"
 
 #include <cmath>
+#include <stdexcept>
 
 namespace of2d {
 
@@ -243,6 +250,9 @@ struct ConvArgs {
     const double *kd;  // k[idxkernel] as double (boundary weight sums)
     int kw, cx, cy;
     double wfull;  // sum of all weights in the reference's order (interior pixels)
+    // separable kernels only: (float) row marginals g[ii] = sum_jj k, then
+    // the column marginals g[jj] = sum_ii k (fp64 sums), kw each
+    const float *gs = nullptr;
 };
 
 template <int KW, int R = kCr>
@@ -405,6 +415,78 @@ __device__ __forceinline__ void convR(const float2 *tile, const ConvArgs &a, int
     }
 }
 
+// The separable smoothing at the same R pixels, from the same tile.  An
+// interior pixel L (every tap's linear index in [0, N)) takes
+//   h[L + jj dimx] = sum_ii f[L + jj dimx + ii] gr[ii]   (ii ascending)
+//   out[L]         = sum_jj h[L + jj dimx] gc[jj]         (jj ascending)
+// in fp32 without contraction and without a division (the marginals sum to
+// 1); the row pass runs along the LINEAR index, which is how the tile is
+// staged, so taps past an x-edge are the neighbouring j-line's like the
+// reference's.  Every other pixel is the direct form's (conv_px, runtime
+// width: the bits of either direct kernel).  When all R pixels are interior,
+// each of the R + 2c row sums of the column is taken once, in registers, and
+// feeds up to KW outputs as it appears (jj ascends with the row for every
+// output); no second LDS tile and no barrier, and exactly the direct form's
+// KW (R + 2c) LDS reads per thread.  The per-pixel branch below sums in the
+// same order, so a pixel's value does not depend on its place in a tile.
+template <int KW, int R, int TX = kCx>
+__device__ __forceinline__ void sepR(const float2 *tile, const ConvArgs &a, int i, int j0, int tx,
+                                     int ty0, int dimx, int dimy, long N, float2 res[R],
+                                     bool has[R]) {
+    static_assert(KW >= 3 && KW % 2 == 1, "odd widths only: the marginals of an even table are not its factors");
+    constexpr int c = (KW - 1) / 2, TW = TX + 2 * c;
+    const float *gr = a.gs, *gc = a.gs + KW;
+    if (conv_rows_interior<KW, R>(i, j0, dimx, dimy, N)) {
+        v2f acc[R];
+#pragma unroll
+        for (int k = 0; k < R; k++) acc[k] = v2f{0.0f, 0.0f};
+#pragma unroll
+        for (int q = 0; q < R + 2 * c; q++) {
+            v2f h = v2f{0.0f, 0.0f};
+#pragma unroll
+            for (int ii = 0; ii < KW; ii++) {
+                const float2 t = tile[(ty0 + q) * TW + (tx + ii)];
+                h = h + v2f{t.x, t.y} * v2f{gr[ii], gr[ii]};
+            }
+#pragma unroll
+            for (int k = 0; k < R; k++) {
+                const int jj = q - k;  // tap row jj - c of output k
+                if (jj >= 0 && jj < KW) acc[k] = acc[k] + h * v2f{gc[jj], gc[jj]};
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            has[k] = true;
+            res[k] = make_float2(acc[k].x, acc[k].y);
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        has[k] = false;
+        const int j = j0 + k;
+        if (j >= dimy) continue;
+        const long lin = (long)j * dimx + i;
+        if (!((lin - c - (long)c * dimx >= 0) && (lin + c + (long)c * dimx < N))) {
+            has[k] = conv_px<0, TX>(tile, a, i, j, tx, ty0 + k, dimx, N, res[k]);
+            continue;
+        }
+        v2f o = v2f{0.0f, 0.0f};
+#pragma unroll 1
+        for (int jj = 0; jj < KW; jj++) {
+            v2f h = v2f{0.0f, 0.0f};
+#pragma unroll 1
+            for (int ii = 0; ii < KW; ii++) {
+                const float2 t = tile[(ty0 + k + jj) * TW + (tx + ii)];
+                h = h + v2f{t.x, t.y} * v2f{gr[ii], gr[ii]};
+            }
+            o = o + h * v2f{gc[jj], gc[jj]};
+        }
+        has[k] = true;
+        res[k] = make_float2(o.x, o.y);
+    }
+}
+
 // Motion::accumulate (Motion.cpp:113-178) at pixels (i, j0..j0+G-1) with
 // increments cv: u(x) <- c(x) + u_old(x + c(x)), bilinear with in-range taps
 // renormalised; out of range keeps u_old(x).  Every gather of the G pixels is
@@ -507,7 +589,8 @@ __device__ __forceinline__ void store_update(const float2 *__restrict__ u,
 }
 
 // K2 from a correction field in HBM: smoothing + motion update (store_update)
-template <int KW, int R = kCr, bool PK = true>
+// SEP: the separable form on the interior pixels (sepR)
+template <int KW, int R = kCr, bool PK = true, bool SEP = false>
 __global__ __launch_bounds__(256) void smooth_compose_kernel(
     const float2 *__restrict__ corr, const float2 *__restrict__ u, float2 *__restrict__ out,
     int dimx, int dimy, int P, ConvArgs a, int mode, int ntl, int gxt) {
@@ -523,7 +606,10 @@ __global__ __launch_bounds__(256) void smooth_compose_kernel(
     const int r0 = (int)__builtin_amdgcn_readfirstlane(threadIdx.y) * R;
     float2 sm[R];
     bool has[R];
-    convR<KW, R, PK>(tile, a, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+    if constexpr (SEP)
+        sepR<KW, R>(tile, a, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+    else
+        convR<KW, R, PK>(tile, a, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
     float2 cv[R];
 #pragma unroll
     for (int k = 0; k < R; k++) {
@@ -551,7 +637,9 @@ __global__ __launch_bounds__(256) void smooth_compose_kernel(
 // `sxq` carries (convR W1, demons_corr SXP); otherwise `sxq` is sigma_xsq
 // TX x (TY R) output tile: TX (64 or 128) threads across (one or two waves
 // per tile row of threads), TY thread rows of R j-lines each
-template <int KW, int R, bool FAST, int TX = kCx, int TY = kCThreadsY>
+// SEP: the separable form on the interior pixels (sepR); FAST is then the
+// sigma_xsq condition alone
+template <int KW, int R, bool FAST, int TX = kCx, int TY = kCThreadsY, bool SEP = false>
 __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_kernel(
     const float *__restrict__ Iref, const float *__restrict__ Imov, const float2 *__restrict__ u,
     float2 *__restrict__ out, int dimx, int dimy, int P, float sigma_isq, float sxq,
@@ -675,7 +763,10 @@ __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_k
     const int r0 = (int)__builtin_amdgcn_readfirstlane(threadIdx.y) * R;
     float2 sm[R];
     bool has[R];
-    convR<KW, R, true, FAST, TX>(ct, ca, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+    if constexpr (SEP)
+        sepR<KW, R, TX>(ct, ca, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+    else
+        convR<KW, R, true, FAST, TX>(ct, ca, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
     float2 cv[R];
 #pragma unroll
     for (int k = 0; k < R; k++) {
@@ -694,8 +785,9 @@ __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_k
 // to ~1e-16 relative, tests/test_gpu_primitives.py).  The R previous-motion
 // loads of a thread are issued together after the convolution, whose
 // registers they reuse.
-template <int KW, int R = kCr, bool PK = true, bool W1 = false, bool NORM = true>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KW == 7 ? 7 : 8))) void smooth_norm_kernel(const float2 *__restrict__ umid,
+// SEP: the separable form on the interior pixels (sepR; W1 unused)
+template <int KW, int R = kCr, bool PK = true, bool W1 = false, bool NORM = true, bool SEP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEP ? 4 : (KW == 7 ? 7 : 8)))) void smooth_norm_kernel(const float2 *__restrict__ umid,
                                                           const float2 *__restrict__ prev,
                                                           float2 *__restrict__ out, int dimx,
                                                           int dimy, int P, ConvArgs a,
@@ -713,10 +805,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KW == 7 ? 7
         const int j0 = y0 + r0;
         float2 sm[R];
         bool has[R];
-        convR<KW, R, PK, W1>(tile, a, i, j0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+        if constexpr (SEP)
+            sepR<KW, R>(tile, a, i, j0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+        else
+            convR<KW, R, PK, W1>(tile, a, i, j0, threadIdx.x, r0, dimx, dimy, N, sm, has);
         // every output of the thread is the convolution's: no fallback loads
         // of u_mid (the loads below are skipped by branch, not by select)
-        const bool conv_all = W1 && KW > 0 && conv_rows_interior<KW, R>(i, j0, dimx, dimy, N);
+        const bool conv_all =
+            (W1 || SEP) && KW > 0 && conv_rows_interior<KW, R>(i, j0, dimx, dimy, N);
         float2 pv[R];
         if (NORM) {
 #pragma unroll
@@ -771,7 +867,15 @@ int conv_nblocks(int dimx, int dimy) {
     return int(g.x * g.y);
 }
 
+bool demons_separable_ok(int kw, int dimx) {
+    return kw >= 3 && kw <= kSepKwMax && kw % 2 == 1 && dimx >= kw;
+}
+
 namespace {
+// the separable kernels' widths: X(kw) for every odd kw in [3, kSepKwMax]
+#define OF2D_SEP_WIDTHS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(15)
+static_assert(kSepKwMax == 15, "OF2D_SEP_WIDTHS lists the odd widths up to kSepKwMax");
+
 // smooth_compose over `gridx` block columns: tiles [0, ntl) and the last
 // gridx - ntl tiles of the gxt-tile row
 void smooth_compose_tiles(const float2 *corr, const float2 *u, float2 *out, int dimx, int dimy,
@@ -782,6 +886,16 @@ void smooth_compose_tiles(const float2 *corr, const float2 *u, float2 *out, int 
         hipLaunchKernelGGL(kern, g, dim3(64, kCThreadsY), conv_lds_bytes(a.cx, a.cy), st, corr, u,
                            out, dimx, dimy, P, a, mode, ntl, gxt);
     };
+    if (a.gs) {  // separable (the caller checked demons_separable_ok)
+        switch (a.kw) {
+#define X(W) case W: go(smooth_compose_kernel<W, kCr, true, true>); break;
+            OF2D_SEP_WIDTHS(X)
+#undef X
+            default: throw std::logic_error("smooth_compose: no separable kernel of this width");
+        }
+        OF2D_HIP(hipGetLastError());
+        return;
+    }
     switch (a.kw) {
         case 3: go(smooth_compose_kernel<3>); break;
         case 5: go(smooth_compose_kernel<5>); break;
@@ -792,43 +906,55 @@ void smooth_compose_tiles(const float2 *corr, const float2 *u, float2 *out, int 
 }
 }  // namespace
 
-void launch_smooth_compose(const float2 *corr, const float2 *u, float2 *out, int dimx, int dimy,
-                           int P, const float *kf, const double *kd, int kw, double wfull,
-                           int mode, hipStream_t st) {
+int launch_smooth_compose(const float2 *corr, const float2 *u, float2 *out, int dimx, int dimy,
+                          int P, const float *kf, const double *kd, int kw, double wfull,
+                          int mode, hipStream_t st, const float *gs) {
     const int c = (kw - 1) / 2;
-    const ConvArgs a{kf, kd, kw, c, c, wfull};
+    const bool sep = gs && demons_separable_ok(kw, dimx);
+    const ConvArgs a{kf, kd, kw, c, c, wfull, sep ? gs : nullptr};
     const int gx = conv_grid(dimx, dimy).x;
     smooth_compose_tiles(corr, u, out, dimx, dimy, P, a, mode, gx, gx, gx, st);
+    return sep;
 }
 
-void launch_demons_update(const float *Iref, const float *Imov, const float2 *u, float2 *corr,
-                          float2 *out, int dimx, int dimy, int P, float sigma_isq,
-                          float sigma_xsq, const float *kf, const double *kd, int kw,
-                          double wfull, int mode, unsigned *status, hipStream_t st) {
+int launch_demons_update(const float *Iref, const float *Imov, const float2 *u, float2 *corr,
+                         float2 *out, int dimx, int dimy, int P, float sigma_isq,
+                         float sigma_xsq, const float *kf, const double *kd, int kw,
+                         double wfull, int mode, unsigned *status, hipStream_t st,
+                         const float *gs) {
     const int c = (kw - 1) / 2;
-    const ConvArgs a{kf, kd, kw, c, c, wfull};
+    const bool sep = gs && demons_separable_ok(kw, dimx);
+    const ConvArgs a{kf, kd, kw, c, c, wfull, sep ? gs : nullptr};
     const int gx = (dimx + kCx - 1) / kCx;
+    constexpr int TX = OF2D_DEMONS_TX, TY = OF2D_DEMONS_TY;
     // the fused kernel takes every tile, the x-edge ones included, when its
-    // width is compiled in and no tile wraps more than once (dimx >= 128)
-    if (!(kw == 3 || kw == 5 || kw == 7) || dimx < 2 * kCx) {
+    // width is compiled in (direct: 3, 5, 7; separable: every width it has)
+    // and no tile wraps more than once: the tile narrower than half the image
+    if (!(sep || kw == 3 || kw == 5 || kw == 7) || dimx < 2 * kCx || dimx < 2 * TX) {
         launch_demons_force(Iref, Imov, u, corr, dimx, dimy, P, sigma_isq, sigma_xsq, status, st);
         smooth_compose_tiles(corr, u, out, dimx, dimy, P, a, mode, gx, gx, gx, st);
-        return;
+        return sep;
     }
     float rsx = 0.0f;
-    const bool fast = (float)wfull == 1.0f && pow2_reciprocal(sigma_xsq, &rsx);
-    constexpr int TX = OF2D_DEMONS_TX, TY = OF2D_DEMONS_TY;
-    // one wrap at most per tile: the tile narrower than half the image
-    if (dimx < 2 * TX) {
-        launch_demons_force(Iref, Imov, u, corr, dimx, dimy, P, sigma_isq, sigma_xsq, status, st);
-        smooth_compose_tiles(corr, u, out, dimx, dimy, P, a, mode, gx, gx, gx, st);
-        return;
-    }
+    // the separable kernels never divide by the weight sum
+    const bool fast = (sep || (float)wfull == 1.0f) && pow2_reciprocal(sigma_xsq, &rsx);
     const dim3 g((dimx + TX - 1) / TX, (dimy + TY * kCr - 1) / (TY * kCr));
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, g, dim3(TX, TY), 0, st, Iref, Imov, u, out, dimx, dimy, P,
                            sigma_isq, fast ? rsx : sigma_xsq, a, mode, status, 0);
     };
+    if (sep) {
+        switch (kw * 2 + fast) {
+#define X(W)                                                                    \
+    case 2 * W: go(demons_fused_kernel<W, kCr, false, TX, TY, true>); break;    \
+    case 2 * W + 1: go(demons_fused_kernel<W, kCr, true, TX, TY, true>); break;
+            OF2D_SEP_WIDTHS(X)
+#undef X
+            default: throw std::logic_error("demons_update: no separable kernel of this width");
+        }
+        OF2D_HIP(hipGetLastError());
+        return 1;
+    }
     switch (kw * 2 + fast) {
         case 6: go(demons_fused_kernel<3, kCr, false, TX, TY>); break;
         case 7: go(demons_fused_kernel<3, kCr, true, TX, TY>); break;
@@ -838,17 +964,31 @@ void launch_demons_update(const float *Iref, const float *Imov, const float2 *u,
         default: go(demons_fused_kernel<7, kCr, false, TX, TY>); break;
     }
     OF2D_HIP(hipGetLastError());
+    return 0;
 }
 
-void launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int dimx, int dimy,
-                        int P, const float *kf, const double *kd, int kw, double wfull,
-                        double *partial, hipStream_t st) {
+int launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int dimx, int dimy,
+                       int P, const float *kf, const double *kd, int kw, double wfull,
+                       double *partial, hipStream_t st, const float *gs) {
     const int c = (kw - 1) / 2;
-    ConvArgs a{kf, kd, kw, c, c, wfull};
+    const bool sep = gs && demons_separable_ok(kw, dimx);
+    ConvArgs a{kf, kd, kw, c, c, wfull, sep ? gs : nullptr};
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, conv_grid(dimx, dimy), dim3(64, kCThreadsY),
                            conv_lds_bytes(c, c), st, umid, prev, out, dimx, dimy, P, a, partial);
     };
+    if (sep) {
+        switch (partial ? kw : -kw) {
+#define X(W)                                                                      \
+    case W: go(smooth_norm_kernel<W, kCr, true, false, true, true>); break;       \
+    case -W: go(smooth_norm_kernel<W, kCr, true, false, false, true>); break;
+            OF2D_SEP_WIDTHS(X)
+#undef X
+            default: throw std::logic_error("smooth_norm: no separable kernel of this width");
+        }
+        OF2D_HIP(hipGetLastError());
+        return 1;
+    }
     const bool w1 = (float)wfull == 1.0f;
     // no partials wanted (the Logger's float sums come from seqnorm): no norms
     if (!partial) {
@@ -862,7 +1002,7 @@ void launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int
             default: go(smooth_norm_kernel<0, kCr, true, false, false>); break;
         }
         OF2D_HIP(hipGetLastError());
-        return;
+        return 0;
     }
     switch (w1 ? kw : -kw) {
         case 3: go(smooth_norm_kernel<3, kCr, true, true>); break;
@@ -874,6 +1014,7 @@ void launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int
         default: go(smooth_norm_kernel<0>); break;
     }
     OF2D_HIP(hipGetLastError());
+    return 0;
 }
 
 // ------------------------------------------------------------------ exp (diffeomorphic)

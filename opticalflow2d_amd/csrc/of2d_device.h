@@ -385,22 +385,34 @@ void launch_demons_force(const float *Iref, const float *Imov, const float2 *u, 
                          unsigned *status, hipStream_t st);
 dim3 conv_grid(int dimx, int dimy);
 int conv_nblocks(int dimx, int dimy);
+// the widest kernel the separable smoothing is compiled for (OF2D_SEP_KW_MAX)
+constexpr int kSepKwMax = 15;
+// the separable smoothing takes a level: kw odd, 3 <= kw <= kSepKwMax (an even
+// table's taps do not cover it and its marginals are not its factors), and
+// dimx >= kw
+bool demons_separable_ok(int kw, int dimx);
 // One correction update (DemonsThirions.cpp:20-38): force, sigma_fluid
 // smoothing and the motion update (mode as launch_smooth_compose) -> out.
 // One fused launch over every tile (demons_fused_kernel; the x-edge tiles hold
-// the wrapped tap pixels) for kw 3 / 5 / 7 and dimx >= 128; otherwise the
-// unfused kernels through corr (scratch).
-void launch_demons_update(const float *Iref, const float *Imov, const float2 *u, float2 *corr,
-                          float2 *out, int dimx, int dimy, int P, float sigma_isq,
-                          float sigma_xsq, const float *kf, const double *kd, int kw,
-                          double wfull, int mode, unsigned *status, hipStream_t st);
+// the wrapped tap pixels) for kw 3 / 5 / 7 (separable: every width it takes)
+// and dimx >= 128; otherwise the unfused kernels through corr (scratch).
+// gs (this and the two launches below): nullptr for the direct convolution;
+// otherwise the kernel's (float) row marginals then column marginals (kw
+// each, gaussian_marginals) for the separable smoothing where
+// demons_separable_ok, the direct one elsewhere.  Returns 1 when the separable
+// kernels ran, 0 for the direct ones.
+int launch_demons_update(const float *Iref, const float *Imov, const float2 *u, float2 *corr,
+                         float2 *out, int dimx, int dimy, int P, float sigma_isq,
+                         float sigma_xsq, const float *kf, const double *kd, int kw,
+                         double wfull, int mode, unsigned *status, hipStream_t st,
+                         const float *gs = nullptr);
 // mode 0 Composition, 1 Addition, 2 no update, 3 store the smoothed corr only
-void launch_smooth_compose(const float2 *corr, const float2 *u, float2 *out, int dimx, int dimy,
-                           int P, const float *kf, const double *kd, int kw, double wfull,
-                           int mode, hipStream_t st);
-void launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int dimx, int dimy,
-                        int P, const float *kf, const double *kd, int kw, double wfull,
-                        double *partial, hipStream_t st);
+int launch_smooth_compose(const float2 *corr, const float2 *u, float2 *out, int dimx, int dimy,
+                          int P, const float *kf, const double *kd, int kw, double wfull,
+                          int mode, hipStream_t st, const float *gs = nullptr);
+int launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int dimx, int dimy,
+                       int P, const float *kf, const double *kd, int kw, double wfull,
+                       double *partial, hipStream_t st, const float *gs = nullptr);
 // Motion::exp (Motion.cpp:253-277) on f; *result is f or scratch
 void launch_motion_exp(float2 *f, float2 *scratch, int dimx, int dimy, int P, int nsq_max,
                        float *d_part, int nparts, int *d_nsq, float *d_maxabs, unsigned *status,

@@ -198,6 +198,8 @@ class Registration {
     const std::vector<float> &last_errors() const { return last_err_; }
     // {dx, dy, fast_x, fast_y} per Curvature loop of the last estimate()
     const std::vector<int> &curvature_paths() const { return cpaths_; }
+    // {dx, dy, kw, separable} per Demons loop of the last estimate()
+    const std::vector<int> &demons_paths() const { return dpaths_; }
     int dimx() const { return dimx_; }
     int dimy() const { return dimy_; }
 
@@ -317,6 +319,8 @@ class Registration {
     std::vector<float> last_err_;
     int curv_dct_ = 0;  // option "curvature_dct"
     std::vector<int> cpaths_;
+    int demons_sep_ = 0;  // option "demons_separable"
+    std::vector<int> dpaths_;
     // Demons kernels (Kernel::set_gaussian, src/Kernel.cpp:45-73)
     std::vector<double> kdiff_, kfluid_;
     std::shared_ptr<DemonsKernels> demons_k_;
@@ -329,6 +333,10 @@ bool valid_regularisation_parameters(int reg, unsigned nparams);
 
 // Kernel::set_gaussian (src/Kernel.cpp:45-73): expf in float, normalised in double
 std::vector<double> gaussian_kernel(int kw, float sigma);
+// the separable smoothing's factors of a kw x kw table k: the (float) row
+// marginals g[ii] = sum_jj k[ii + jj kw], then the column marginals g[jj] =
+// sum_ii k[ii + jj kw], each summed in fp64 in ascending order (2 kw values)
+std::vector<float> gaussian_marginals(const std::vector<double> &k, int kw);
 // the weight sum of a pixel whose taps are all valid, in the reference's
 // summation order (Field.tpp:242-256)
 double full_weight(const std::vector<double> &k, int kw);

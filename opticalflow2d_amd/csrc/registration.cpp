@@ -91,6 +91,20 @@ std::vector<double> gaussian_kernel(int kw, float sigma) {
     return k;
 }
 
+std::vector<float> gaussian_marginals(const std::vector<double> &k, int kw) {
+    std::vector<float> g(2 * (size_t)kw);
+    for (int a = 0; a < kw; a++) {
+        double row = 0, col = 0;
+        for (int b = 0; b < kw; b++) {
+            row += k[a + (size_t)b * kw];
+            col += k[b + (size_t)a * kw];
+        }
+        g[a] = (float)row;
+        g[kw + a] = (float)col;
+    }
+    return g;
+}
+
 static const char kRule[] =
     "%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%%";  // 71 x '%'
 
@@ -202,6 +216,11 @@ void Registration::set_option(const std::string &key, double v) {
     else if (key == "curvature_dct") {
         if (v != 0 && v != 1) throw std::invalid_argument("option 'curvature_dct' must be 0 or 1");
         curv_dct_ = (int)v;
+    }
+    else if (key == "demons_separable") {
+        if (v != 0 && v != 1)
+            throw std::invalid_argument("option 'demons_separable' must be 0 or 1");
+        demons_sep_ = (int)v;
     }
     else if (key == "device") {
         if (ready_) throw std::invalid_argument("option 'device' must be set before first use");
@@ -353,6 +372,7 @@ void Registration::estimate() {
     ensure_device();
     iters_.clear();
     cpaths_.clear();
+    dpaths_.clear();
     OF2D_HIP(hipMemsetAsync(d_status_, 0, 64 * sizeof(unsigned), st_));
     Level &L0 = lv_[0];
     for (int s = nscales_; s >= 0; s--) {

@@ -57,15 +57,19 @@ int max_partial_blocks(const Level &L, int reg) {
 
 // Device copies of the two Gaussian kernels: float weights for the sums,
 // double weights for boundary weight sums, and the interior weight sum in the
-// reference's summation order (Field.tpp:242-256).
+// reference's summation order (Field.tpp:242-256); gs: the separable
+// smoothing's factors (gaussian_marginals) of the fluid kernel, then of the
+// diffusion kernel, 2 kw floats each.
 struct DemonsKernels {
     float *kf = nullptr;
     double *kd = nullptr;
+    float *gs = nullptr;
     int kw = 0;
     double wfull_fluid = 0, wfull_diff = 0;
     ~DemonsKernels() {
         if (kf) (void)hipFree(kf);
         if (kd) (void)hipFree(kd);
+        if (gs) (void)hipFree(gs);
     }
 };
 
@@ -110,6 +114,12 @@ int Registration::loop_demons(Level &L, int niter, int &final_buf) {
         OF2D_HIP(hipMalloc(&demons_k_->kd, sizeof(double) * 2 * n));
         OF2D_HIP(hipMemcpy(demons_k_->kf, kf.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
         OF2D_HIP(hipMemcpy(demons_k_->kd, kd.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+        std::vector<float> gs = gaussian_marginals(kfluid_, kw);
+        const std::vector<float> gd = gaussian_marginals(kdiff_, kw);
+        gs.insert(gs.end(), gd.begin(), gd.end());
+        OF2D_HIP(hipMalloc(&demons_k_->gs, sizeof(float) * gs.size()));
+        OF2D_HIP(hipMemcpy(demons_k_->gs, gs.data(), sizeof(float) * gs.size(),
+                           hipMemcpyHostToDevice));
         demons_k_->kw = kw;
         demons_k_->wfull_fluid = full_weight(kfluid_, kw);
         demons_k_->wfull_diff = full_weight(kdiff_, kw);
@@ -131,6 +141,10 @@ int Registration::loop_demons(Level &L, int niter, int &final_buf) {
     // the default Logger mode sums the reference's float norms itself
     // (run_chunked_exact): the smoothing pass then computes no partials
     const bool partials = !exact_norms();
+    // option "demons_separable": both smoothings of the level, or neither
+    const bool sep = demons_sep_ != 0 && demons_separable_ok(kw, L.dx);
+    const float *gfluid = sep ? K.gs : nullptr, *gdiff = sep ? K.gs + 2 * kw : nullptr;
+    dpaths_.insert(dpaths_.end(), {L.dx, L.dy, kw, sep ? 1 : 0});
     return run_chunked(
         L, niter, nb,
         [&](const float2 *src, float2 *dst, double *partial) {
@@ -139,7 +153,7 @@ int Registration::loop_demons(Level &L, int niter, int &final_buf) {
             // correspondence itself, then exp() and motion->accumulate)
             launch_demons_update(L.Iref.p, L.Iaux.p, src, L.corr.p, L.tmp.p, L.dx, L.dy, L.P,
                                  sigma_isq, sigma_xsq, K.kf, K.kd, kw, K.wfull_fluid,
-                                 diffeo ? 3 : mode, d_status_, st_);
+                                 diffeo ? 3 : mode, d_status_, st_, gfluid);
             const float2 *umid = L.tmp.p;
             if (diffeo) {
                 float2 *cexp = nullptr;
@@ -150,7 +164,7 @@ int Registration::loop_demons(Level &L, int niter, int &final_buf) {
                 umid = L.increment.p;
             }
             launch_smooth_norm(umid, src, dst, L.dx, L.dy, L.P, K.kf + n, K.kd + n, kw,
-                               K.wfull_diff, partials ? partial : nullptr, st_);
+                               K.wfull_diff, partials ? partial : nullptr, st_, gdiff);
         },
         final_buf);
 }

@@ -177,6 +177,8 @@ def motion_norms_chain(u, dims: Sequence[int], batch: int = 3):
 # ------------------------------------------------------------------ Curvature transforms
 #: line lengths the fast transforms take (powers of two; include/of2d.h)
 DCT_NMIN, DCT_NMAX = 8, 8192
+# the widest Demons kernel "demons_separable" takes (include/of2d.h OF2D_SEP_KW_MAX)
+SEP_KW_MAX = 15
 
 
 def dct2d(a, kind: int, method: int = 1):
@@ -310,39 +312,59 @@ class prim:
         return out, int(st.value)
 
     @classmethod
-    def smooth_compose(cls, corr, u, kw, sigma, mode):
-        """Returns ``(out, wfull)``."""
+    def smooth_compose(cls, corr, u, kw, sigma, mode, method=None):
+        """Returns ``(out, wfull)``; with ``method`` (0 the direct convolution,
+        1 the separable one where it qualifies) ``(out, wfull, path)``, ``path``
+        1 when the separable kernels ran."""
         corr = cls._f(corr)
         dimy, dimx, _ = corr.shape
         out = np.zeros_like(corr)
         w = C.c_double(0)
-        cls._call("of2d_prim_smooth_compose", corr, cls._f(u, corr.shape), dimx, dimy, int(kw),
-                  float(sigma), int(mode), out, C.byref(w))
-        return out, float(w.value)
+        if method is None:
+            cls._call("of2d_prim_smooth_compose", corr, cls._f(u, corr.shape), dimx, dimy,
+                      int(kw), float(sigma), int(mode), out, C.byref(w))
+            return out, float(w.value)
+        path = C.c_int(-1)
+        cls._call("of2d_prim_smooth_compose_m", corr, cls._f(u, corr.shape), dimx, dimy, int(kw),
+                  float(sigma), int(mode), out, C.byref(w), int(method), C.byref(path))
+        return out, float(w.value), int(path.value)
 
     @classmethod
-    def smooth_norm(cls, umid, prev, kw, sigma, partials=True):
+    def smooth_norm(cls, umid, prev, kw, sigma, partials=True, method=None):
         """Returns ``(out, sums)``: ``sums`` the two fp64 Logger sums, or None
-        from the launch without partials."""
+        from the launch without partials; with ``method`` (as smooth_compose)
+        ``(out, sums, path)``."""
         umid = cls._f(umid)
         dimy, dimx, _ = umid.shape
         out = np.zeros_like(umid)
         sums = (C.c_double * 2)()
-        cls._call("of2d_prim_smooth_norm", umid, cls._f(prev, umid.shape), dimx, dimy, int(kw),
-                  float(sigma), out, sums if partials else None)
-        return out, ((float(sums[0]), float(sums[1])) if partials else None)
+        if method is None:
+            cls._call("of2d_prim_smooth_norm", umid, cls._f(prev, umid.shape), dimx, dimy,
+                      int(kw), float(sigma), out, sums if partials else None)
+            return out, ((float(sums[0]), float(sums[1])) if partials else None)
+        path = C.c_int(-1)
+        cls._call("of2d_prim_smooth_norm_m", umid, cls._f(prev, umid.shape), dimx, dimy, int(kw),
+                  float(sigma), out, sums if partials else None, int(method), C.byref(path))
+        return out, ((float(sums[0]), float(sums[1])) if partials else None), int(path.value)
 
     @classmethod
-    def demons_update(cls, Iref, Imov, u, sigma_i, sigma_x, kw, sigma_fluid, mode):
-        """Returns ``(out, status)``."""
+    def demons_update(cls, Iref, Imov, u, sigma_i, sigma_x, kw, sigma_fluid, mode, method=None):
+        """Returns ``(out, status)``; with ``method`` (as smooth_compose)
+        ``(out, status, path)``."""
         Iref = cls._f(Iref)
         dimy, dimx = Iref.shape
         out = np.zeros((dimy, dimx, 2), np.float32)
         st = C.c_uint(0)
-        cls._call("of2d_prim_demons_update", Iref, cls._f(Imov, Iref.shape),
+        if method is None:
+            cls._call("of2d_prim_demons_update", Iref, cls._f(Imov, Iref.shape),
+                      cls._f(u, out.shape), dimx, dimy, float(sigma_i), float(sigma_x), int(kw),
+                      float(sigma_fluid), int(mode), out, C.byref(st))
+            return out, int(st.value)
+        path = C.c_int(-1)
+        cls._call("of2d_prim_demons_update_m", Iref, cls._f(Imov, Iref.shape),
                   cls._f(u, out.shape), dimx, dimy, float(sigma_i), float(sigma_x), int(kw),
-                  float(sigma_fluid), int(mode), out, C.byref(st))
-        return out, int(st.value)
+                  float(sigma_fluid), int(mode), out, C.byref(st), int(method), C.byref(path))
+        return out, int(st.value), int(path.value)
 
     @classmethod
     def motion_exp(cls, f, sigma_i=0.0, sigma_x=1.0):
@@ -386,7 +408,7 @@ class ImageRegistration:
     floats), ``nrefine``, ``verbose``.  Extra keyword options map to
     ``of2d_set_option`` (``fixed_iters``, ``chunk``, ``device``,
     ``hs_gradients_from_image``, ``logger_fp64``, ``ngpus``,
-    ``curvature_dct``).
+    ``curvature_dct``, ``demons_separable``).
     """
 
     def __init__(self, dims: Sequence[int], niter: Sequence[int], nscales: int, reg: int,
@@ -455,6 +477,13 @@ class ImageRegistration:
         estimate, in execution order (of2d_curvature_paths)."""
         buf = np.zeros(4 * 1024, np.int32)
         n = _lib.lib().of2d_curvature_paths(self._h, buf, buf.size)
+        return [tuple(int(v) for v in buf[4 * k: 4 * k + 4]) for k in range(max(n, 0))]
+
+    def demons_paths(self) -> list:
+        """``(dimx, dimy, kw, separable)`` per Demons loop of the last
+        estimate, in execution order (of2d_demons_paths)."""
+        buf = np.zeros(4 * 1024, np.int32)
+        n = _lib.lib().of2d_demons_paths(self._h, buf, buf.size)
         return [tuple(int(v) for v in buf[4 * k: 4 * k + 4]) for k in range(max(n, 0))]
 
     def close(self) -> None:
