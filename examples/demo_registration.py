@@ -9,11 +9,14 @@ repository; this one builds a synthetic pair (a disk shifted by a few pixels,
 or a smooth texture pair for Demons,
 replicate-padded by 11 pixels along x like the demo) so it runs anywhere an MI355X is.
 
-    python examples/demo_registration.py [--reg 5] [--size 256]
+    python examples/demo_registration.py [--reg 5] [--size 256] [--report]
 
 Prints the motion statistics the reference demo prints (mean / std, maxabs)
 plus the residual before and after warping and the minimum Jacobian of the
-motion (the quantity the demo plots).
+motion (the quantity the demo plots).  ``--report`` adds the device-side
+deformation analysis (``opticalflow2d_amd.field``) of the whole padded grid:
+the Jacobian's extrema and folded pixels, the inverse field's iterations and
+residual, and MSE / NCC of Iref against Imov before and after warping.
 """
 from __future__ import annotations
 
@@ -26,7 +29,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from opticalflow2d_amd import OpticalFlow2d, Regularisation  # noqa: E402
+from opticalflow2d_amd import OpticalFlow2d, Regularisation, field  # noqa: E402
 from opticalflow2d_amd import synthetic as S  # noqa: E402
 
 # per regularisation: niter per scale, nscales, parameters (SolverOptions order)
@@ -50,11 +53,28 @@ def jacobian_min(motion: np.ndarray) -> float:
     return float(((1.0 + dudx) * (1.0 + dvdy) - dudy * dvdx).min())
 
 
+def report(ref, mov, ireg, motion) -> None:
+    """The analysis of the motion the gateway returned, on the device; `field`
+    takes float32 arrays in the C-ABI's layout ([dimy, dimx], x fastest)."""
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a).T, dtype=np.float32)  # noqa: E731
+    u = np.ascontiguousarray(np.transpose(motion, (1, 0, 2)), dtype=np.float32)
+    _, st = field.jacobian(u, jac=False)
+    print(f"Jacobian: min {st['min']:.3f} max {st['max']:.3f}, folded pixels {st['folded']}")
+    _, info, _ = field.invert(u)
+    print(f"Inverse: {info['iterations']} iterations, residual {info['residual']:.2e} px"
+          f"{'' if info['converged'] else ' (not converged)'}")
+    mse0, ncc0 = field.similarity(f32(ref), f32(mov))
+    mse1, ncc1 = field.similarity(f32(ref), f32(ireg))
+    print(f"MSE {mse0:.3e} -> {mse1:.3e}, NCC {ncc0:.4f} -> {ncc1:.4f}")
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reg", type=int, default=int(Regularisation.Fluid))
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--verbose", type=int, default=0)
+    ap.add_argument("--report", action="store_true",
+                    help="print the device-side Jacobian / inverse / similarity report")
     args = ap.parse_args()
     reg = Regularisation(args.reg)
     if reg not in PRESETS:
@@ -95,6 +115,8 @@ def main() -> int:
     print(f"mean |Iref - Imov| {np.abs(ref_c - mov_c).mean():.4f} -> "
           f"mean |Iref - Ireg| {np.abs(ref_c - reg_c).mean():.4f}")
     print(f"min Jacobian {jacobian_min(motion_c):.3f}")
+    if args.report:
+        report(ref, mov, ireg, motion)
     return 0
 
 

@@ -396,6 +396,66 @@ int of2d_prim_d2f(const double *in, int dimx, int dimy, float *out);
 int of2d_prim_f2d(const float *in, int dimx, int dimy, double *out);
 int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out);
 
+/* ---- deformation analysis: is the registration any good? ----
+ * Per-pixel passes over fields that are on the device, in the registration's
+ * own layout; only the results cross the boundary.  Not in the reference's
+ * interface; the Jacobian is Image::jacobian (src/Image.cpp:189-218) and the
+ * composition Motion::accumulate (src/Motion.cpp:113-178), bit for bit.  Every
+ * reduction runs in a fixed order: two calls on the same input give the same
+ * bits.  The of2d_field_* / of2d_image_* entries take host arrays in the
+ * layout of the of2d_prim_* entries (u is float [dimx*dimy*2], x and y
+ * interleaved, idx = i + j*dimx) and report errors as they do
+ * (of2d_gateway_last_error); the entries on a context read its level-0 motion
+ * (zero before the first of2d_estimate) and leave it untouched. */
+/* J = (1 + du.x/dx) (1 + du.y/dy) - du.y/dx du.x/dy with the reference's
+ * partial_x / partial_y (central differences, one-sided on the borders), the
+ * number Fluid regrids on.  stats[5] = {min, max, mean, count(J <= 0) (folded
+ * pixels), count(J < 0.5) (Fluid's regrid threshold)}; jac (float [dimx*dimy])
+ * may be NULL: only the statistics are produced.  dimx < 2 or dimy < 2 is
+ * refused with OF2D_ERR_INVALID_ARGUMENT before any device work (the one-sided
+ * difference would read outside the field). */
+int of2d_field_jacobian(const float *u, int dimx, int dimy, float *jac, double *stats);
+/* of the registration's current level-0 motion, without leaving the device
+ * except for the results; jac is double [dimx*dimy] (boundary layout) or NULL */
+int of2d_jacobian(of2d_ctx *ctx, double *jac, double *stats);
+/* The inverse field v with (id + u) o (id + v) = id, by the fixed-point
+ * iteration v_0 = 0, r_k = accumulate(u, v_k) (= v_k + u(x + v_k), bilinear),
+ * v_{k+1} = v_k - r_k, m_k = max |r_k| over pixels and components.  Where
+ * floor(x + v_k) falls outside the grid r_k is 0 (v keeps its value there) and
+ * the pixel is counted as out of bounds (Motion::accumulate would keep u's
+ * value instead, and the iteration would run away along the border).  The
+ * update is always applied; the loop stops after the first k with
+ * m_k < (float)tol, or after max_iter updates.  The stop is decided on the
+ * device: the host enqueues OF2D_INVERT_CHUNK updates at a time and reads the
+ * report once per chunk; updates behind the stop do nothing.
+ * info[4] = {iterations (updates applied), residual (m of the last one),
+ * out-of-bounds pixels at the last evaluated iterate, converged 0/1};
+ * residuals (optional, float[max_iter]): m_k per update applied, 0 beyond.
+ * Refused with OF2D_ERR_INVALID_ARGUMENT before any device work: NULL u, v or
+ * info, max_iter < 1, tol not finite or <= 0, dimx < 2 or dimy < 2.  A folded
+ * field (min J <= 0) has no inverse: the call returns OF2D_OK with
+ * converged = 0. */
+#define OF2D_INVERT_CHUNK 8
+int of2d_field_invert(const float *u, int dimx, int dimy, int max_iter, double tol, float *v,
+                      double *info, float *residuals);
+/* inverse of the registration's level-0 motion; out planar double like of2d_get_motion */
+int of2d_invert_motion(of2d_ctx *ctx, int max_iter, double tol, double *out, double *info);
+/* out[2] = {mse, ncc} of two float images [dimx*dimy]: the mean squared
+ * difference and the zero-mean normalised cross-correlation, from fp64 sums
+ * of a, b, a^2, b^2, ab and (a - b)^2.  ncc is NaN when either image is
+ * constant (zero variance); the call still returns OF2D_OK. */
+int of2d_image_similarity(const float *a, const float *b, int dimx, int dimy, double *out);
+/* Iref against Imov and against warp2d(Imov, motion) (images as of2d_warp's):
+ * out[4] = {mse_before, ncc_before, mse_after, ncc_after}; the warp is the one
+ * of2d_warp takes, on the device */
+int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *out);
+/* average duration (microseconds, HIP events around nlaunch back-to-back
+ * launches after one untimed launch) at dimx x dimy: us[0] the Jacobian map
+ * with its statistics (the map launch and its one-block reduction), us[1] one
+ * update of the inverse at an iterate near the fixed point of a smooth 3-pixel
+ * field.  A timing entry for tools/analysis_bench.py, not a result. */
+int of2d_analysis_time_kernels(int dimx, int dimy, int nlaunch, double *us);
+
 /* ---- library info ---- */
 const char *of2d_version(void);
 int of2d_device_count(int *count);

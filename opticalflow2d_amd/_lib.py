@@ -110,6 +110,14 @@ SIGNATURES = {
     "of2d_prim_d2f": (C.c_int, [_f64p, C.c_int, C.c_int, _f32p]),
     "of2d_prim_f2d": (C.c_int, [_f32p, C.c_int, C.c_int, _f64p]),
     "of2d_prim_motion_to_planar": (C.c_int, [_f32p, C.c_int, C.c_int, _f64p]),
+    "of2d_field_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_void_p, _f64p]),
+    "of2d_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, _f64p]),
+    "of2d_field_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_double, _f32p, _f64p,
+                                    C.c_void_p]),
+    "of2d_invert_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f64p, _f64p]),
+    "of2d_image_similarity": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f64p]),
+    "of2d_quality": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
+    "of2d_analysis_time_kernels": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
     "of2d_version": (C.c_char_p, []),
     "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }

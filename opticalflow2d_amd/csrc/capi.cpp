@@ -6,6 +6,7 @@
 // process-global singleton (WrapperOpticalFlow2d.cpp:13-155).
 #include "../../include/of2d.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -674,6 +675,171 @@ int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out) 
         of2d::launch_motion_to_planar(a.p, a.P, dimx, dimy, d.p, nullptr);
         OF2D_HIP(hipStreamSynchronize(nullptr));
         OF2D_HIP(hipMemcpy(out, d.p, sizeof(double) * d.n, hipMemcpyDeviceToHost));
+    });
+}
+
+// ------------------------------------------------------------------ analysis
+}  // extern "C"
+
+namespace {
+// a refusal before any device work, with its reason for of2d_gateway_last_error
+// (and of2d_last_error of the context, where there is one)
+int refuse(of2d_ctx *ctx, const char *why) {
+    g_gateway_err = why;
+    if (ctx) ctx->err = why;
+    return OF2D_ERR_INVALID_ARGUMENT;
+}
+// the analysis of a context's motion: its own error string, mirrored for
+// of2d_gateway_last_error
+template <class F>
+int analysis(of2d_ctx *ctx, F &&f) {
+    const int rc = guarded(ctx->err, f);
+    if (rc != OF2D_OK) g_gateway_err = ctx->err;
+    return rc;
+}
+const char *invert_args(int dimx, int dimy, int max_iter, double tol) {
+    if (dimx < 2 || dimy < 2) return "invert: the field needs dimx >= 2 and dimy >= 2";
+    if (max_iter < 1) return "invert: max_iter < 1";
+    if (!std::isfinite(tol) || tol <= 0.0)
+        return "invert: tol must be finite and > 0";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
+static_assert(OF2D_INVERT_CHUNK == of2d::kInvertChunk,
+              "include/of2d.h documents the inverse's chunk");
+
+int of2d_field_jacobian(const float *u, int dimx, int dimy, float *jac, double *stats) {
+    if (!u || !stats) return refuse(nullptr, "of2d_field_jacobian: u or stats is NULL");
+    if (dimx < 2 || dimy < 2)
+        return refuse(nullptr, "jacobian: the field needs dimx >= 2 and dimy >= 2");
+    return prim(true, [&] {
+        of2d::Field<float2> f;
+        of2d::Field<float> j;
+        upload(f, u, dimx, dimy);
+        if (jac) upload(j, nullptr, dimx, dimy);
+        of2d::DevArray<of2d::JacPartial> part;
+        part.alloc((size_t)of2d::jacobian_nblocks(dimx, dimy));
+        of2d::DevArray<double> ds;
+        ds.alloc(5);
+        of2d::launch_jacobian(f.p, dimx, dimy, f.P, j.p, part.p, ds.p, nullptr);
+        if (jac) download(jac, j.p, j.P, dimx, dimy);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(stats, ds.p, 5 * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int of2d_jacobian(of2d_ctx *ctx, double *jac, double *stats) {
+    if (!ctx || !stats) return refuse(ctx, "of2d_jacobian: ctx or stats is NULL");
+    if (ctx->reg->dimx() < 2 || ctx->reg->dimy() < 2)
+        return refuse(ctx, "jacobian: the field needs dimx >= 2 and dimy >= 2");
+    return analysis(ctx, [&] { ctx->reg->jacobian(jac, stats); });
+}
+
+int of2d_field_invert(const float *u, int dimx, int dimy, int max_iter, double tol, float *v,
+                      double *info, float *residuals) {
+    if (!u || !v || !info) return refuse(nullptr, "of2d_field_invert: u, v or info is NULL");
+    if (const char *why = invert_args(dimx, dimy, max_iter, tol)) return refuse(nullptr, why);
+    return prim(true, [&] {
+        of2d::Field<float2> f, v0, v1;
+        upload(f, u, dimx, dimy);
+        upload(v0, nullptr, dimx, dimy);
+        upload(v1, nullptr, dimx, dimy);
+        of2d::DevArray<unsigned> ctl;
+        ctl.alloc(of2d::invert_ctl_words(max_iter));
+        const of2d::InvertResult r = of2d::invert_field(f.p, v0.p, v1.p, dimx, dimy, f.P,
+                                                        max_iter, (float)tol, ctl.p, residuals,
+                                                        nullptr);
+        download(v, r.v, f.P, dimx, dimy);
+        info[0] = r.iterations;
+        info[1] = (double)r.residual;
+        info[2] = (double)r.oob;
+        info[3] = r.converged ? 1.0 : 0.0;
+    });
+}
+
+int of2d_invert_motion(of2d_ctx *ctx, int max_iter, double tol, double *out, double *info) {
+    if (!ctx || !out || !info) return refuse(ctx, "of2d_invert_motion: ctx, out or info is NULL");
+    if (const char *why = invert_args(ctx->reg->dimx(), ctx->reg->dimy(), max_iter, tol))
+        return refuse(ctx, why);
+    return analysis(ctx, [&] { ctx->reg->invert_motion(max_iter, tol, out, info); });
+}
+
+int of2d_image_similarity(const float *a, const float *b, int dimx, int dimy, double *out) {
+    if (!a || !b || !out) return refuse(nullptr, "of2d_image_similarity: a, b or out is NULL");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "similarity: empty image");
+    return prim(true, [&] {
+        of2d::Field<float> x, y;
+        upload(x, a, dimx, dimy);
+        upload(y, b, dimx, dimy);
+        of2d::DevArray<of2d::SimPartial> part;
+        part.alloc((size_t)of2d::similarity_nblocks(dimx, dimy));
+        of2d::DevArray<double> ds;
+        ds.alloc(2);
+        of2d::launch_similarity(x.p, y.p, dimx, dimy, x.P, part.p, ds.p, nullptr);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(out, ds.p, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *out) {
+    if (!ctx || !Iref || !Imov || !out)
+        return refuse(ctx, "of2d_quality: ctx, Iref, Imov or out is NULL");
+    return analysis(ctx, [&] { ctx->reg->quality(Iref, Imov, out); });
+}
+
+int of2d_analysis_time_kernels(int dimx, int dimy, int nlaunch, double *us) {
+    if (!us || nlaunch <= 0) return refuse(nullptr, "of2d_analysis_time_kernels: us, nlaunch");
+    if (dimx < 2 || dimy < 2)
+        return refuse(nullptr, "analysis timing: the field needs dimx >= 2 and dimy >= 2");
+    return prim(true, [&] {
+        // the inverse's test field (tests/test_gpu_analysis.py), amplitude 3
+        std::vector<float> hu((size_t)dimx * dimy * 2);
+        const double tp = 6.283185307179586;
+        for (int j = 0; j < dimy; j++)
+            for (int i = 0; i < dimx; i++) {
+                float *p = &hu[((size_t)j * dimx + i) * 2];
+                p[0] = (float)(3.0 * sin(tp * i / dimx + 0.3) * cos(tp * j / dimy));
+                p[1] = (float)(2.1 * cos(2 * tp * i / dimx) * sin(tp * j / dimy + 0.5));
+            }
+        of2d::Field<float2> f, v0, v1;
+        of2d::Field<float> jm;
+        upload(f, hu.data(), dimx, dimy);
+        upload(v0, nullptr, dimx, dimy);
+        upload(v1, nullptr, dimx, dimy);
+        upload(jm, nullptr, dimx, dimy);
+        of2d::DevArray<of2d::JacPartial> part;
+        part.alloc((size_t)of2d::jacobian_nblocks(dimx, dimy));
+        of2d::DevArray<double> ds;
+        ds.alloc(5);
+        of2d::DevArray<unsigned> ctl;
+        ctl.alloc(of2d::invert_ctl_words(4));
+        // an iterate near the fixed point: the gather pattern of a real update
+        const of2d::InvertResult r =
+            of2d::invert_field(f.p, v0.p, v1.p, dimx, dimy, f.P, 4, 1e-3f, ctl.p, nullptr, nullptr);
+        float2 *vin = r.v, *vout = r.v == v0.p ? v1.p : v0.p;
+        hipEvent_t e0, e1;
+        OF2D_HIP(hipEventCreate(&e0));
+        OF2D_HIP(hipEventCreate(&e1));
+        for (int which = 0; which < 2; which++) {
+            for (int k = -1; k < nlaunch; k++) {  // k = -1: one untimed launch
+                if (k == 0) OF2D_HIP(hipEventRecord(e0, nullptr));
+                if (which == 0)
+                    of2d::launch_jacobian(f.p, dimx, dimy, f.P, jm.p, part.p, ds.p, nullptr);
+                else  // update 0 reads no control word: every launch does the work
+                    of2d::launch_invert_step(f.p, vin, vout, dimx, dimy, f.P, 0, 1e-3f, ctl.p, 4,
+                                             nullptr);
+            }
+            OF2D_HIP(hipEventRecord(e1, nullptr));
+            OF2D_HIP(hipEventSynchronize(e1));
+            float ms = 0.0f;
+            OF2D_HIP(hipEventElapsedTime(&ms, e0, e1));
+            us[which] = 1000.0 * (double)ms / nlaunch;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
     });
 }
 

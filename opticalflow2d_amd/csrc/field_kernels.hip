@@ -272,42 +272,7 @@ void launch_gradients(const float *Iref, const float *Iaux, float2 *dI, float *I
 // Motion::accumulate (src/Motion.cpp:113-178): u(x) <- v(x) + u_old(x + v(x))
 // (bilinear, renormalised); out-of-range keeps u_old(x).
 // Branch-free as warp_kernel.
-__device__ __forceinline__ float2 accumulate_px(const float2 *__restrict__ mo, float2 c,
-                                                float2 own, int i, int j, int dimx, int dimy,
-                                                int P) {
-    const float px = (float)i + c.x;
-    const int dx = (int)floorf(px);
-    const float fx = px - (float)dx;
-    const float py = (float)j + c.y;
-    const int dy = (int)floorf(py);
-    const float fy = py - (float)dy;
-    const bool ok = !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
-    const bool ax = dx < dimx - 1, ay = dy < dimy - 1, axy = ax && ay;
-    const float2 *b = mo + (ok ? ((unsigned)dy * (unsigned)P + (unsigned)dx) : 0u);
-    const float2 t00 = b[0], t10 = b[1], t01 = b[P], t11 = b[P + 1];
-    float vx = (t00.x * (1 - fx)) * (1 - fy);
-    float vy = (t00.y * (1 - fx)) * (1 - fy);
-    float w = (1 - fx) * (1 - fy);
-    const float x10 = vx + (t10.x * fx) * (1 - fy), y10 = vy + (t10.y * fx) * (1 - fy);
-    const float w10 = w + fx * (1 - fy);
-    vx = ax ? x10 : vx;
-    vy = ax ? y10 : vy;
-    w = ax ? w10 : w;
-    const float x01 = vx + (t01.x * (1 - fx)) * fy, y01 = vy + (t01.y * (1 - fx)) * fy;
-    const float w01 = w + (1 - fx) * fy;
-    vx = ay ? x01 : vx;
-    vy = ay ? y01 : vy;
-    w = ay ? w01 : w;
-    const float x11 = vx + (t11.x * fx) * fy, y11 = vy + (t11.y * fx) * fy;
-    const float w11 = w + fx * fy;
-    vx = axy ? x11 : vx;
-    vy = axy ? y11 : vy;
-    w = axy ? w11 : w;
-    float2 q = make_float2(c.x + vx, c.y + vy);  // vx / 1.0f is vx
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(ok && w != 1.0f) != 0, 0))
-        q = make_float2(c.x + vx / w, c.y + vy / w);
-    return ok ? (w != 0 ? q : c) : own;
-}
+// (accumulate_px: of2d_device.h, shared with analysis_kernels.hip)
 __global__ void accumulate_kernel(const float2 *__restrict__ mo, const float2 *__restrict__ v,
                                   float2 *__restrict__ mn, int dimx, int dimy, int P) {
     OF2D_PX_PROLOGUE(dimx, dimy)

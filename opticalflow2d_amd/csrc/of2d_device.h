@@ -378,6 +378,110 @@ void launch_compose_zero(const float2 *v, float2 *out, int dimx, int nrows, int 
                          int dimy, hipStream_t st);
 void launch_add_motion(const float2 *a, const float2 *b, float2 *out, int dimx, int dimy, int P,
                        hipStream_t st);
+// One pixel of Motion::accumulate (src/Motion.cpp:113-178): c + mo(x + c),
+// bilinear and renormalised by the valid weight; `own` where floor(x + c) falls
+// outside the grid.  Branch-free (field_kernels.hip, warp_px): the taps are
+// loaded unconditionally (an out-of-range pattern reads element 0; g[1], g[P],
+// g[P+1] of an in-image pixel stay in the allocation: pitch padding and the
+// zeroed ghost j-line below the last row) and the reference's conditional terms
+// are selects.
+__device__ __forceinline__ float2 accumulate_px(const float2 *__restrict__ mo, float2 c,
+                                                float2 own, int i, int j, int dimx, int dimy,
+                                                int P) {
+    const float px = (float)i + c.x;
+    const int dx = (int)floorf(px);
+    const float fx = px - (float)dx;
+    const float py = (float)j + c.y;
+    const int dy = (int)floorf(py);
+    const float fy = py - (float)dy;
+    const bool ok = !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
+    const bool ax = dx < dimx - 1, ay = dy < dimy - 1, axy = ax && ay;
+    const float2 *b = mo + (ok ? ((unsigned)dy * (unsigned)P + (unsigned)dx) : 0u);
+    const float2 t00 = b[0], t10 = b[1], t01 = b[P], t11 = b[P + 1];
+    float vx = (t00.x * (1 - fx)) * (1 - fy);
+    float vy = (t00.y * (1 - fx)) * (1 - fy);
+    float w = (1 - fx) * (1 - fy);
+    const float x10 = vx + (t10.x * fx) * (1 - fy), y10 = vy + (t10.y * fx) * (1 - fy);
+    const float w10 = w + fx * (1 - fy);
+    vx = ax ? x10 : vx;
+    vy = ax ? y10 : vy;
+    w = ax ? w10 : w;
+    const float x01 = vx + (t01.x * (1 - fx)) * fy, y01 = vy + (t01.y * (1 - fx)) * fy;
+    const float w01 = w + (1 - fx) * fy;
+    vx = ay ? x01 : vx;
+    vy = ay ? y01 : vy;
+    w = ay ? w01 : w;
+    const float x11 = vx + (t11.x * fx) * fy, y11 = vy + (t11.y * fx) * fy;
+    const float w11 = w + fx * fy;
+    vx = axy ? x11 : vx;
+    vy = axy ? y11 : vy;
+    w = axy ? w11 : w;
+    float2 q = make_float2(c.x + vx, c.y + vy);  // vx / 1.0f is vx
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(ok && w != 1.0f) != 0, 0))
+        q = make_float2(c.x + vx / w, c.y + vy / w);
+    return ok ? (w != 0 ? q : c) : own;
+}
+
+// ---------------------------------------------------------------- analysis
+// Deformation analysis of a motion field that is already on the device
+// (analysis_kernels.hip; DESIGN.md "Deformation analysis").  Every reduction
+// runs over per-block partials in a fixed order, without float atomics: two
+// calls on the same input give the same bits.
+//
+// Jacobian determinant map (Image::jacobian, src/Image.cpp:189-218, the
+// expression fluid_step_kernel evaluates inline) with its statistics in the
+// same launch; a second, one-block launch reduces the partials.
+struct JacPartial {
+    float mn, mx;
+    double sum;
+    unsigned le0, lt05;  // J <= 0 (folded), J < 0.5f (Fluid's regrid threshold)
+};
+int jacobian_nblocks(int dimx, int dimy);
+// jac (optional): pitched float map (pitch P; the pitch padding of a written
+// row is zeroed); part: jacobian_nblocks partials; stats: device double[5] =
+// {min, max, mean, count(J <= 0), count(J < 0.5)}.  dimx, dimy >= 2.
+void launch_jacobian(const float2 *u, int dimx, int dimy, int P, float *jac, JacPartial *part,
+                     double *stats, hipStream_t st);
+
+// Similarity of two pitched float images: fp64 sums of a, b, a^2, b^2, ab and
+// (a - b)^2 and the images' extrema per block, reduced by a one-block launch to
+// out = device double[2] = {mse, ncc}; ncc (zero-mean normalised
+// cross-correlation) is NaN when an image is constant (min == max).
+struct SimPartial {
+    double s[6];
+    float mn[2], mx[2];
+};
+int similarity_nblocks(int dimx, int dimy);
+void launch_similarity(const float *a, const float *b, int dimx, int dimy, int P,
+                       SimPartial *part, double *out, hipStream_t st);
+
+// Inverse field by fixed-point iteration: v_{k+1} = v_k - r_k with r_k =
+// accumulate(u, v_k), 0 where floor(x + v_k) is outside the grid (the pixel is
+// counted, v kept), m_k = max |r_k| over both components.  Control words
+// (device, invert_ctl_words(max_iter), prepared by invert_field): [0] the
+// updates applied when the loop stopped (kInvertRunning until then), [1 + k]
+// the bits of m_k, [1 + max_iter + k] the out-of-bounds pixels of update k.
+// Update k > 0 first reads its predecessor's m: below tol it writes the stop
+// word and, like every later launch, does nothing.
+constexpr int kInvertChunk = 8;  // updates enqueued between the host's reads
+constexpr unsigned kInvertRunning = 0x7f7f7f7fu;
+inline size_t invert_ctl_words(int max_iter) { return 1 + 2 * (size_t)max_iter; }
+void launch_invert_step(const float2 *u, const float2 *vin, float2 *vout, int dimx, int dimy,
+                        int P, int k, float tol, unsigned *ctl, int max_iter, hipStream_t st);
+struct InvertResult {
+    int iterations = 0;
+    float residual = 0.0f;  // m of the last update applied
+    unsigned oob = 0;       // out-of-bounds pixels at the last evaluated iterate
+    bool converged = false;
+    float2 *v = nullptr;    // v0 or v1: the buffer holding the result
+};
+// The loop from v_0 = 0 (v0 zeroed by the caller over the image; v1 scratch),
+// kInvertChunk launches between reads of the control words.  residuals
+// (optional, host float[max_iter]): m_k of every update applied, 0 beyond.
+// Synchronises st.
+InvertResult invert_field(const float2 *u, float2 *v0, float2 *v1, int dimx, int dimy, int P,
+                          int max_iter, float tol, unsigned *ctl, float *residuals,
+                          hipStream_t st);
 
 // ---------------------------------------------------------------- Demons
 void launch_demons_force(const float *Iref, const float *Imov, const float2 *u, float2 *corr,

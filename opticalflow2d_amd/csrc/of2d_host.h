@@ -193,6 +193,11 @@ class Registration {
     void estimate();
     void get_motion(double *out);
     void warp(const double *in, double *out);
+    // Deformation analysis of the level-0 motion, on the device (include/of2d.h
+    // of2d_jacobian, of2d_invert_motion, of2d_quality); the motion is only read
+    void jacobian(double *jac, double *stats);
+    void invert_motion(int max_iter, double tol, double *out, double *info);
+    void quality(const double *ref, const double *mov, double *out);
     void set_option(const std::string &key, double v);
     const std::vector<int> &iterations() const { return iters_; }
     const std::vector<float> &last_errors() const { return last_err_; }

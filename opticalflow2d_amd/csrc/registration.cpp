@@ -941,4 +941,74 @@ void Registration::warp(const double *in, double *out) {
     OF2D_HIP(hipStreamSynchronize(st_));
 }
 
+// ------------------------------------------------------------ analysis
+// The Jacobian map of the level-0 motion and its statistics; the map crosses
+// the boundary as an image does (Image::copy_image_to_input)
+void Registration::jacobian(double *jac, double *stats) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    Level &L0 = lv_[0];
+    const size_t n0 = (size_t)dimx_ * dimy_;
+    Field<float> jf;
+    if (jac) jf.alloc(dimx_, dimy_);
+    DevArray<JacPartial> part;
+    part.alloc((size_t)jacobian_nblocks(dimx_, dimy_));
+    DevArray<double> ds;
+    ds.alloc(5);
+    launch_jacobian(L0.cur_motion(), dimx_, dimy_, L0.P, jf.p, part.p, ds.p, st_);
+    if (jac) {
+        launch_f2d(jf.p, L0.P, dimx_, dimy_, d_stage_, st_);
+        OF2D_HIP(hipMemcpyAsync(jac, d_stage_, n0 * sizeof(double), hipMemcpyDeviceToHost, st_));
+    }
+    OF2D_HIP(hipMemcpyAsync(stats, ds.p, 5 * sizeof(double), hipMemcpyDeviceToHost, st_));
+    OF2D_HIP(hipStreamSynchronize(st_));
+}
+
+// v with (id + motion) o (id + v) = id; out as get_motion's
+void Registration::invert_motion(int max_iter, double tol, double *out, double *info) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    Level &L0 = lv_[0];
+    Field<float2> v0, v1;
+    v0.alloc(dimx_, dimy_);
+    v1.alloc(dimx_, dimy_);
+    DevArray<unsigned> ctl;
+    ctl.alloc(invert_ctl_words(max_iter));
+    const InvertResult r = invert_field(L0.cur_motion(), v0.p, v1.p, dimx_, dimy_, L0.P, max_iter,
+                                        (float)tol, ctl.p, nullptr, st_);
+    launch_motion_to_planar(r.v, L0.P, dimx_, dimy_, d_stage_, st_);
+    OF2D_HIP(hipMemcpyAsync(out, d_stage_, sizeof(double) * 2 * dimx_ * dimy_,
+                            hipMemcpyDeviceToHost, st_));
+    OF2D_HIP(hipStreamSynchronize(st_));
+    info[0] = r.iterations;
+    info[1] = (double)r.residual;
+    info[2] = (double)r.oob;
+    info[3] = r.converged ? 1.0 : 0.0;
+}
+
+// {mse, ncc} of Iref against Imov, then against warp2d(Imov, motion)
+void Registration::quality(const double *ref, const double *mov, double *out) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    Level &L0 = lv_[0];
+    const size_t n0 = (size_t)dimx_ * dimy_;
+    Field<float> a, b, c;
+    a.alloc(dimx_, dimy_);
+    b.alloc(dimx_, dimy_);
+    c.alloc(dimx_, dimy_);
+    DevArray<SimPartial> part;
+    part.alloc((size_t)similarity_nblocks(dimx_, dimy_));
+    DevArray<double> ds;
+    ds.alloc(4);
+    OF2D_HIP(hipMemcpyAsync(d_stage_, ref, n0 * sizeof(double), hipMemcpyHostToDevice, st_));
+    launch_d2f(d_stage_, dimx_, dimy_, a.p, L0.P, 0, st_);
+    OF2D_HIP(hipMemcpyAsync(d_stage_, mov, n0 * sizeof(double), hipMemcpyHostToDevice, st_));
+    launch_d2f(d_stage_, dimx_, dimy_, b.p, L0.P, 0, st_);
+    launch_similarity(a.p, b.p, dimx_, dimy_, L0.P, part.p, ds.p, st_);
+    launch_warp(b.p, L0.cur_motion(), c.p, dimx_, dimy_, L0.P, st_);
+    launch_similarity(a.p, c.p, dimx_, dimy_, L0.P, part.p, ds.p + 2, st_);
+    OF2D_HIP(hipMemcpyAsync(out, ds.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st_));
+    OF2D_HIP(hipStreamSynchronize(st_));
+}
+
 }  // namespace of2d

@@ -399,6 +399,87 @@ class prim:
         return out
 
 
+# ------------------------------------------------------------------ deformation analysis
+#: updates of the inverse enqueued between the host's reads (include/of2d.h)
+INVERT_CHUNK = 8
+
+
+def _jac_stats(st) -> dict:
+    return {"min": float(st[0]), "max": float(st[1]), "mean": float(st[2]),
+            "folded": int(st[3]), "below_half": int(st[4])}
+
+
+def _invert_info(info) -> dict:
+    return {"iterations": int(info[0]), "residual": float(info[1]),
+            "out_of_bounds": int(info[2]), "converged": bool(info[3])}
+
+
+def _invert_args(max_iter, tol):
+    max_iter, tol = int(max_iter), float(tol)
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1")
+    if not np.isfinite(tol) or tol <= 0:
+        raise ValueError("tol must be finite and > 0")
+    return max_iter, tol
+
+
+class field:
+    """Deformation analysis of a motion field on the device (include/of2d.h,
+    "deformation analysis"): the Jacobian determinant map, the inverse field
+    and the similarity of two images.  Arrays as for :class:`prim`: float32, an
+    image ``[dimy, dimx]`` and a motion field ``[dimy, dimx, 2]`` in C order."""
+
+    @staticmethod
+    def _motion(u):
+        u = prim._f(u)
+        if u.ndim != 3 or u.shape[2] != 2:
+            raise ValueError(f"a motion field is [dimy, dimx, 2], got {u.shape}")
+        if u.shape[0] < 2 or u.shape[1] < 2:
+            raise ValueError("the field needs dimx >= 2 and dimy >= 2")
+        return u
+
+    @classmethod
+    def jacobian(cls, u, jac=True):
+        """``(jac [dimy, dimx], stats)``: the reference's Jacobian determinant
+        of ``id + u`` and ``stats = {min, max, mean, folded (J <= 0),
+        below_half (J < 0.5)}``; ``jac=False`` takes the statistics only and
+        returns ``(None, stats)``."""
+        u = cls._motion(u)
+        dimy, dimx, _ = u.shape
+        out = np.zeros((dimy, dimx), np.float32) if jac else None
+        st = np.zeros(5, np.float64)
+        prim._call("of2d_field_jacobian", u, dimx, dimy,
+                   out.ctypes.data if jac else None, st)
+        return out, _jac_stats(st)
+
+    @classmethod
+    def invert(cls, u, max_iter=50, tol=1e-3):
+        """``(v, info, residuals)`` with ``(id + u) o (id + v) = id``: the
+        fixed-point iteration of of2d_field_invert.  ``info = {iterations,
+        residual, out_of_bounds, converged}``; ``residuals`` (float32
+        ``[iterations]``) holds max |r_k| of every update applied."""
+        u = cls._motion(u)
+        max_iter, tol = _invert_args(max_iter, tol)
+        dimy, dimx, _ = u.shape
+        v = np.zeros_like(u)
+        info = np.zeros(4, np.float64)
+        res = np.zeros(max_iter, np.float32)
+        prim._call("of2d_field_invert", u, dimx, dimy, max_iter, tol, v, info, res.ctypes.data)
+        info = _invert_info(info)
+        return v, info, res[: info["iterations"]].copy()
+
+    @classmethod
+    def similarity(cls, a, b):
+        """``(mse, ncc)`` of two images; ``ncc`` is NaN when one is constant."""
+        a = prim._f(a)
+        if a.ndim != 2 or a.size == 0:
+            raise ValueError(f"an image is [dimy, dimx], got {a.shape}")
+        b = prim._f(b, a.shape)
+        out = np.zeros(2, np.float64)
+        prim._call("of2d_image_similarity", a, b, a.shape[1], a.shape[0], out)
+        return float(out[0]), float(out[1])
+
+
 # ------------------------------------------------------------------ object API
 class ImageRegistration:
     """Handle on one registration context (of2d_create ... of2d_destroy).
@@ -462,6 +543,38 @@ class ImageRegistration:
         self._chk(_lib.lib().of2d_warp(self._h, m, out))
         return out.reshape((self.dimx, self.dimy), order="F")
 
+    def jacobian(self, jac: bool = True):
+        """``(jac [dimx, dimy], stats)`` of the current motion, on the device
+        (of2d_jacobian): the Jacobian determinant map and ``{min, max, mean,
+        folded, below_half}``; ``jac=False``: ``(None, stats)``."""
+        n = self.dimx * self.dimy
+        out = np.zeros(n, np.float64) if jac else None
+        st = np.zeros(5, np.float64)
+        self._chk(_lib.lib().of2d_jacobian(self._h, out.ctypes.data if jac else None, st))
+        return (out.reshape((self.dimx, self.dimy), order="F") if jac else None), _jac_stats(st)
+
+    def inverse_motion(self, max_iter: int = 50, tol: float = 1e-3):
+        """``(motion [dimx, dimy, 2], info)``: the inverse of the current
+        motion (of2d_invert_motion), ``info`` as :meth:`field.invert`'s."""
+        max_iter, tol = _invert_args(max_iter, tol)
+        out = np.zeros(self.dimx * self.dimy * 2, np.float64)
+        info = np.zeros(4, np.float64)
+        self._chk(_lib.lib().of2d_invert_motion(self._h, max_iter, tol, out, info))
+        return out.reshape((self.dimx, self.dimy, 2), order="F"), _invert_info(info)
+
+    def quality(self, Iref, Imov) -> dict:
+        """MSE and zero-mean NCC of ``Iref`` against ``Imov`` and against
+        ``Imov`` warped by the current motion (of2d_quality): ``{mse_before,
+        ncc_before, mse_after, ncc_after}``."""
+        n = self.dimx * self.dimy
+        r, m = _col(Iref, n), _col(Imov, n)
+        if r.size != n or m.size != n:
+            raise ValueError(f"images must have {n} elements")
+        out = np.zeros(4, np.float64)
+        self._chk(_lib.lib().of2d_quality(self._h, r, m, out))
+        return dict(zip(("mse_before", "ncc_before", "mse_after", "ncc_after"),
+                        (float(v) for v in out)))
+
     def iterations(self) -> list:
         buf = np.zeros(4096, np.int32)
         n = _lib.lib().of2d_iterations_executed(self._h, buf, buf.size)
@@ -505,4 +618,5 @@ class ImageRegistration:
 
 
 __all__ = ["Regularisation", "Verbose", "MotionAccumulation", "OpticalFlow2d",
-           "ImageRegistration", "set_print_sink", "Of2dError", "motion_norms", "dct2d", "prim"]
+           "ImageRegistration", "set_print_sink", "Of2dError", "motion_norms", "dct2d", "prim",
+           "field", "INVERT_CHUNK"]
