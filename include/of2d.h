@@ -396,6 +396,27 @@ int of2d_prim_d2f(const double *in, int dimx, int dimy, float *out);
 int of2d_prim_f2d(const float *in, int dimx, int dimy, double *out);
 int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out);
 
+/* ---- test and diagnostic entries: Curvature, one call each ----
+ * One call of the function the Curvature loop calls, on a bare level of that
+ * size (as of2d_dct2d).  Planes are dense double [dimx*dimy], idx = i + j*dimx;
+ * method as of2d_dct2d.  Bad arguments are refused before any device work. */
+/* the rhs kernel: out = u - tau * f, f the optical flow force of (u, dI, It),
+ * in float, widened; out_x, out_y the two planes */
+int of2d_prim_curv_rhs(const float *u, const float *dI, const float *It, float tau, int dimx,
+                       int dimy, double *out_x, double *out_y);
+/* the eigenvalue table the level is built with, out[p + q*dimx] = E(p, q) */
+int of2d_prim_curv_eigen(int dimx, int dimy, float alpha, float tau, int method, double *out);
+/* of2d_dct2d on the plane pair ax | ay, in place: both planes go through the
+ * one transform call of an iteration.  with_eig 1 (kind 10 only, as in the
+ * solver) multiplies by the eigenvalues of (alpha, tau) in the axis-x pass. */
+int of2d_prim_curv_dct2d(double *ax, double *ay, int dimx, int dimy, int kind, int method,
+                         int with_eig, float alpha, float tau, int *paths);
+/* the construct kernel: out = (float)z / div per component, and sums[0] =
+ * sum |out - u|, sums[1] = sum |u|: the launch's per-block Logger partials
+ * added in block order on the host */
+int of2d_prim_curv_construct(const double *zx, const double *zy, const float *u, float div,
+                             int dimx, int dimy, float *out, double *sums);
+
 /* ---- deformation analysis: is the registration any good? ----
  * Per-pixel passes over fields that are on the device, in the registration's
  * own layout; only the results cross the boundary.  Not in the reference's

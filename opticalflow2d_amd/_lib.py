@@ -110,6 +110,13 @@ SIGNATURES = {
     "of2d_prim_d2f": (C.c_int, [_f64p, C.c_int, C.c_int, _f32p]),
     "of2d_prim_f2d": (C.c_int, [_f32p, C.c_int, C.c_int, _f64p]),
     "of2d_prim_motion_to_planar": (C.c_int, [_f32p, C.c_int, C.c_int, _f64p]),
+    "of2d_prim_curv_rhs": (C.c_int, [_f32p, _f32p, _f32p, C.c_float, C.c_int, C.c_int, _f64p,
+                                     _f64p]),
+    "of2d_prim_curv_eigen": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _f64p]),
+    "of2d_prim_curv_dct2d": (C.c_int, [_f64p, _f64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_float, C.c_float, _i32p]),
+    "of2d_prim_curv_construct": (C.c_int, [_f64p, _f64p, _f32p, C.c_float, C.c_int, C.c_int,
+                                           _f32p, _f64p]),
     "of2d_field_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_void_p, _f64p]),
     "of2d_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, _f64p]),
     "of2d_field_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_double, _f32p, _f64p,

@@ -678,6 +678,104 @@ int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out) 
     });
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------ Curvature primitives
+namespace {
+// a level of the solver with nothing but Curvature's buffers, tables and
+// eigenvalues (as of2d_dct2d)
+void curvature_level(of2d::Level &L, int dimx, int dimy, float alpha, float tau, int method) {
+    L.dx = dimx;
+    L.dy = dimy;
+    L.P = of2d::pitch_for(dimx);
+    of2d::solvers::alloc_level(L, OF2D_REG_CURVATURE);
+    of2d::solvers::build_curvature(L, alpha, tau, method, nullptr);
+}
+void upload_plane(double *dev, int P, const double *host, int dimx, int dimy) {
+    const size_t row = (size_t)dimx * sizeof(double);
+    OF2D_HIP(hipMemcpy2D(dev, (size_t)P * sizeof(double), host, row, row, dimy,
+                         hipMemcpyHostToDevice));
+}
+void download_plane(double *host, const double *dev, int P, int dimx, int dimy) {
+    const size_t row = (size_t)dimx * sizeof(double);
+    OF2D_HIP(hipStreamSynchronize(nullptr));
+    OF2D_HIP(hipMemcpy2D(host, row, dev, (size_t)P * sizeof(double), row, dimy,
+                         hipMemcpyDeviceToHost));
+}
+}  // namespace
+
+extern "C" {
+
+int of2d_prim_curv_rhs(const float *u, const float *dI, const float *It, float tau, int dimx,
+                       int dimy, double *out_x, double *out_y) {
+    return prim(u && dI && It && out_x && out_y && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> m, g;
+        of2d::Field<float> t;
+        upload(m, u, dimx, dimy);
+        upload(g, dI, dimx, dimy);
+        upload(t, It, dimx, dimy);
+        const long plane = (long)m.P * dimy;
+        of2d::DevArray<double> X;
+        X.alloc(2 * (size_t)plane);
+        of2d::launch_curv_rhs(m.p, g.p, t.p, tau, dimx, dimy, m.P, X.p, plane, nullptr);
+        download_plane(out_x, X.p, m.P, dimx, dimy);
+        download_plane(out_y, X.p + plane, m.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_curv_eigen(int dimx, int dimy, float alpha, float tau, int method, double *out) {
+    return prim(out && dimx > 0 && dimy > 0 && (method == 0 || method == 1), [&] {
+        of2d::Level L;
+        curvature_level(L, dimx, dimy, alpha, tau, method);
+        download_plane(out, L.cE.p, L.P, dimx, dimy);
+    });
+}
+
+int of2d_prim_curv_dct2d(double *ax, double *ay, int dimx, int dimy, int kind, int method,
+                         int with_eig, float alpha, float tau, int *paths) {
+    return prim(ax && ay && paths && dimx > 0 && dimy > 0 && (kind == 10 || kind == 1) &&
+                    (method == 0 || method == 1) && (with_eig == 0 || (with_eig == 1 && kind == 10)),
+                [&] {
+                    of2d::Level L;
+                    curvature_level(L, dimx, dimy, alpha, tau, method);
+                    paths[0] = L.cpath & 1;
+                    paths[1] = (L.cpath >> 1) & 1;
+                    const long plane = (long)L.P * dimy;
+                    upload_plane(L.cbuf[0].p, L.P, ax, dimx, dimy);
+                    upload_plane(L.cbuf[0].p + plane, L.P, ay, dimx, dimy);
+                    const double *res = of2d::solvers::curvature_dct2d(
+                        L, kind == 1, L.cbuf[0].p, L.cbuf[1].p, with_eig ? L.cE.p : nullptr,
+                        nullptr);
+                    download_plane(ax, res, L.P, dimx, dimy);
+                    download_plane(ay, res + plane, L.P, dimx, dimy);
+                });
+}
+
+int of2d_prim_curv_construct(const double *zx, const double *zy, const float *u, float div,
+                             int dimx, int dimy, float *out, double *sums) {
+    return prim(zx && zy && u && out && sums && dimx > 0 && dimy > 0, [&] {
+        of2d::Field<float2> m, o;
+        upload(m, u, dimx, dimy);
+        upload(o, nullptr, dimx, dimy);
+        const long plane = (long)m.P * dimy;
+        of2d::DevArray<double> Z, part;
+        Z.alloc(2 * (size_t)plane);
+        upload_plane(Z.p, m.P, zx, dimx, dimy);
+        upload_plane(Z.p + plane, m.P, zy, dimx, dimy);
+        const int nb = of2d::curv_nblocks(dimx, dimy);
+        part.alloc(2 * (size_t)nb);
+        of2d::launch_curv_construct(Z.p, plane, m.p, o.p, div, dimx, dimy, m.P, part.p, nullptr);
+        download(out, o.p, o.P, dimx, dimy);
+        std::vector<double> h(2 * (size_t)nb);
+        OF2D_HIP(hipMemcpy(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        sums[0] = sums[1] = 0.0;
+        for (int b = 0; b < nb; b++) {
+            sums[0] += h[2 * (size_t)b];
+            sums[1] += h[2 * (size_t)b + 1];
+        }
+    });
+}
+
 // ------------------------------------------------------------------ analysis
 }  // extern "C"
 

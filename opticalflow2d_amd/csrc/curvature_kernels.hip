@@ -149,9 +149,11 @@ __global__ __launch_bounds__(256) void curv_construct_kernel(const double *__res
         const float2 n = make_float2((float)Z[idx] / div, (float)Z[plane + idx] / div);
         const float2 o = u[idx];
         out[idx] = n;
-        const float ex = n.x - o.x, ey = n.y - o.y;
-        sd = (double)__builtin_sqrtf(ex * ex + ey * ey);
-        sp = (double)__builtin_sqrtf(o.x * o.x + o.y * o.y);
+        // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
+        const double ex = (double)(n.x - o.x), ey = (double)(n.y - o.y);
+        const double qx = (double)o.x, qy = (double)o.y;
+        sd = sqrt(ex * ex + ey * ey);
+        sp = sqrt(qx * qx + qy * qy);
     }
     for (int off = 32; off > 0; off >>= 1) {
         sd += __shfl_down(sd, off);

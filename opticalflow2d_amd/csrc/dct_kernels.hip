@@ -5,20 +5,25 @@
 //   REDFT10: Y_k = 2 sum_j X_j cos(pi (j + 1/2) k / n)
 //   REDFT01: Y_k = X_0 + 2 sum_{j>=1} X_j cos(pi j (k + 1/2) / n)
 //
-// Makhoul's reordering onto a complex FFT of the same length (J. Makhoul, "A
-// fast cosine transform in one and two dimensions", IEEE Trans. ASSP 28(1),
-// 1980).  With v_m = x_2m, v_{n-1-m} = x_{2m+1} and V = FFT_n(v),
+// Makhoul's reordering onto an FFT of the same length (J. Makhoul, "A fast
+// cosine transform in one and two dimensions", IEEE Trans. ASSP 28(1), 1980).
+// With v_m = x_2m, v_{n-1-m} = x_{2m+1} and V = FFT_n(v),
 //   REDFT10(x)_k = 2 Re(c_k V_k),  c_k = exp(-i pi k / (2n)),
 // and, since c_k V_k = C_k - i C_{n-k} for the half-sized result C = Y / 2,
 //   REDFT01(C) = the unnormalised inverse FFT of V_k = conj(c_k) (C_k - i C_{n-k})
-// (C_n = 0), read back through the same reordering.  The x plane and the y
-// plane of a line are the real and imaginary part of ONE complex FFT (both
-// directions are linear and map real lines to real lines), which halves the
-// work and puts a 4096-point line pair into 64 KiB of LDS.  The inverse FFT is
-// the forward one on data with real and imaginary parts swapped, so there is a
-// single FFT: in-place decimation in frequency, radix-4 passes (a last radix-2
-// pass when log2 n is odd) with one barrier between passes; the result is left
-// in digit-reversed order and the post-processing reads it through dct_pos().
+// (C_n = 0), read back through the same reordering.  v is real, so its FFT is
+// taken as a complex FFT of half the length: u_j = v_2j + i v_{2j+1}, U =
+// FFT_{n/2}(u), and with w = exp(-2 pi i / n), U_{n/2} = U_0,
+//   2 V_k = (U_k + conj U_{n/2-k}) - i w^k (U_k - conj U_{n/2-k}),  0 <= k <= n/2,
+//   U_k = (V_k + conj V_{n/2-k}) + i conj(w^k) (V_k - conj V_{n/2-k})  (inverse).
+// The x plane and the y plane of a line are two such half-length FFTs side by
+// side in LDS (the work of one complex FFT of length n, a 4096-point line pair
+// in 64 KiB): no arithmetic mixes the planes, so a plane of zeros stays zero on
+// the bits.  The inverse FFT is the forward one on data with real and imaginary
+// parts swapped, so there is a single FFT: in-place decimation in frequency,
+// radix-4 passes (a last radix-2 pass when log2 (n/2) is odd) with one barrier
+// between passes; the result is left in digit-reversed order and the
+// post-processing reads it through dct_pos().
 //
 // fp64 throughout; the twiddles are a host-built fp64 table (dct_table).
 // Lines are contiguous (element k of line l at l * P + k, the y plane `plane`
@@ -52,26 +57,45 @@ __device__ inline double2 cmul(double2 a, double2 w) {
     return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
 }
 
-// conj(c) (p - i q) for the x plane (.x of p, q) and the y plane (.y), packed
-// as x + i y and stored with real and imaginary parts swapped
-__device__ inline double2 dct_inv_pack(double2 p, double2 q, double2 c) {
-    const double er = c.x, ei = -c.y;
-    const double vax = er * p.x + ei * q.x, vay = ei * p.x - er * q.x;
-    const double vbx = er * p.y + ei * q.y, vby = ei * p.y - er * q.y;
-    return make_double2(vay + vbx, vax - vby);
+// REDFT10 output k of one plane from its half-length spectrum zs (digit-
+// reversed): Re(c_k 2 V_k) for k <= n/2, -Im(c_{n-k} 2 V_{n-k}) above
+__device__ inline double dct_fwd_out(const double2 *zs, const double2 *tw, int k, int N) {
+    const int Nh = N >> 1, kk = k <= Nh ? k : N - k;
+    const double2 uk = zs[dct_pos(kk & (Nh - 1), Nh)], un = zs[dct_pos((Nh - kk) & (Nh - 1), Nh)];
+    const double2 a = make_double2(uk.x + un.x, uk.y - un.y);   // U_k + conj U_{n/2-k}
+    const double2 b = make_double2(uk.y + un.y, un.x - uk.x);   // -i (U_k - conj U_{n/2-k})
+    const double2 wb = cmul(b, tw[kk]);
+    const double2 t = cmul(make_double2(a.x + wb.x, a.y + wb.y), tw[N + kk]);
+    return k <= Nh ? t.x : -t.y;
+}
+
+// V_k = conj(c_k) (C_k - i C_{n-k}) of one plane's coefficients C (C_n = 0), 0 <= k <= n/2
+__device__ inline double2 dct_inv_v(const double *C, const double2 *tw, int k, int N) {
+    const double2 c = tw[N + k];
+    const double er = c.x, ei = -c.y, p = C[k], q = k == 0 ? 0.0 : C[N - k];
+    return make_double2(er * p + ei * q, ei * p - er * q);
+}
+
+// REDFT01 sample n of the reordered line v from the FFT of the swapped
+// spectrum (digit-reversed): v_2j = Im, v_{2j+1} = Re of element j
+__device__ inline double dct_inv_out(const double2 *zs, int n, int Nh) {
+    const double2 r = zs[dct_pos(n >> 1, Nh)];
+    return (n & 1) ? r.x : r.y;
 }
 }  // namespace
 
 // KIND 0: REDFT10 (times E[k + line * P] when E != nullptr), 1: REDFT01, in
 // place on lines [0, nlines) of the plane pair X | X + plane.  A block holds
-// lpb lines (lpb * N = T complex points) in LDS; tw[0, N) = exp(-2 pi i m / N),
-// tw[N, 2N) = exp(-i pi k / (2N)).
+// lpb lines in LDS (lpb * N = T complex points: per line the x plane's N/2
+// points, then the y plane's); tw[0, N) = exp(-2 pi i m / N), tw[N, 2N) =
+// exp(-i pi k / (2N)).
 template <int KIND>
 __global__ __launch_bounds__(kDctThreads) void dct_lines_kernel(double *X, long plane, int P,
                                                                 int nlines, int N, int logN,
                                                                 int lpb, const double2 *tw,
                                                                 const double *E) {
     extern __shared__ double2 z[];
+    double *zd = reinterpret_cast<double *>(z);
     const int tid = threadIdx.x, nt = blockDim.x;
     const int T = lpb * N, half = N >> 1;
     const int line0 = blockIdx.x * lpb;
@@ -85,32 +109,49 @@ __global__ __launch_bounds__(kDctThreads) void dct_lines_kernel(double *X, long 
             a = *reinterpret_cast<const double2 *>(pa);
             b = *reinterpret_cast<const double2 *>(pa + plane);
         }
-        double2 *zl = z + l * N;
         if (KIND == 0) {
-            zl[m] = make_double2(a.x, b.x);
-            zl[N - 1 - m] = make_double2(a.y, b.y);
+            // v_m = x_2m, v_{N-1-m} = x_{2m+1}; u_j = (v_2j, v_{2j+1}) is v itself
+            double *vx = zd + 2 * (long)l * N, *vy = vx + N;
+            vx[m] = a.x;
+            vx[N - 1 - m] = a.y;
+            vy[m] = b.x;
+            vy[N - 1 - m] = b.y;
         } else {
-            zl[2 * m] = make_double2(a.x, b.x);
-            zl[2 * m + 1] = make_double2(a.y, b.y);
+            z[l * N + m] = a;  // C in natural order
+            z[l * N + half + m] = b;
         }
     }
     __syncthreads();
     if (KIND == 1) {
-        // V_k and V_{n-k} from C_k and C_{n-k}: one lane per pair (k = 0 takes n/2 too)
-        for (int g = tid; g < (T >> 1); g += nt) {
-            const int l = g >> (logN - 1), k = g & (half - 1);
-            double2 *zl = z + l * N;
-            const int k2 = k == 0 ? half : N - k;
-            const double2 c1 = zl[k], c2 = zl[k2];
-            const double2 zero = make_double2(0.0, 0.0);
-            zl[k] = dct_inv_pack(c1, k == 0 ? zero : c2, tw[N + k]);
-            zl[k2] = dct_inv_pack(c2, k == 0 ? c2 : c1, tw[N + k2]);
+        // U_k of each plane from its C, stored with real and imaginary parts
+        // swapped; every lane reads its inputs before any lane overwrites them
+        constexpr int kPer = kDctMaxN / kDctThreads;  // T / nt at most
+        double2 ur[kPer];
+#pragma unroll
+        for (int q = 0; q < kPer; q++) {
+            const int g = tid + q * nt;
+            if (g < T) {
+                const int l = g >> logN, r = g & (N - 1), pl = r >> (logN - 1), k = r & (half - 1);
+                const double *C = zd + 2 * (long)l * N + (long)pl * N;
+                const double2 vk = dct_inv_v(C, tw, k, N), vh = dct_inv_v(C, tw, half - k, N);
+                const double2 s = make_double2(vk.x + vh.x, vk.y - vh.y);  // V_k + conj V_{N/2-k}
+                const double2 d = make_double2(vk.x - vh.x, vk.y + vh.y);  // V_k - conj V_{N/2-k}
+                const double2 w = tw[k];
+                const double px = d.x * w.x + d.y * w.y, py = d.y * w.x - d.x * w.y;  // d conj(w^k)
+                ur[q] = make_double2(s.y + px, s.x - py);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kPer; q++) {
+            const int g = tid + q * nt;
+            if (g < T) z[g] = ur[q];  // line l, plane pl, k: l * N + pl * N/2 + k = g
         }
         __syncthreads();
     }
 
-    // forward FFT of every line, in place
-    int M = N, logQ = logN - 2;
+    // forward FFT of every half-length line, in place
+    int M = half, logQ = logN - 3;
     for (; M >= 4; M >>= 2, logQ -= 2) {
         const int Q = M >> 2, step = N / M;
         for (int t = tid; t < (T >> 2); t += nt) {
@@ -141,19 +182,14 @@ __global__ __launch_bounds__(kDctThreads) void dct_lines_kernel(double *X, long 
     for (int g = tid; g < (T >> 1); g += nt) {
         const int l = g >> (logN - 1), m = g & (half - 1);
         if (line0 + l >= nlines) continue;
-        const double2 *zl = z + l * N;
+        const double2 *zx = z + l * N, *zy = zx + half;
         const long off = (long)(line0 + l) * P + 2 * m;
         double ya[2], yb[2];
         if (KIND == 0) {
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                const int k = 2 * m + e;
-                const double2 zk = zl[dct_pos(k, N)], zn = zl[dct_pos((N - k) & (N - 1), N)];
-                const double2 c = tw[N + k];
-                const double sx = zk.x + zn.x, sy = zk.y - zn.y;
-                const double dx = zk.x - zn.x, dy = zk.y + zn.y;
-                ya[e] = c.x * sx - c.y * sy;
-                yb[e] = c.x * dy + c.y * dx;
+                ya[e] = dct_fwd_out(zx, tw, 2 * m + e, N);
+                yb[e] = dct_fwd_out(zy, tw, 2 * m + e, N);
             }
             if (E) {
                 const double2 ev = *reinterpret_cast<const double2 *>(E + off);
@@ -163,11 +199,11 @@ __global__ __launch_bounds__(kDctThreads) void dct_lines_kernel(double *X, long 
                 yb[1] *= ev.y;
             }
         } else {
-            const double2 r0 = zl[dct_pos(m, N)], r1 = zl[dct_pos(N - 1 - m, N)];
-            ya[0] = r0.y;
-            ya[1] = r1.y;
-            yb[0] = r0.x;
-            yb[1] = r1.x;
+            // x_2m = v_m, x_{2m+1} = v_{N-1-m}
+            ya[0] = dct_inv_out(zx, m, half);
+            ya[1] = dct_inv_out(zx, N - 1 - m, half);
+            yb[0] = dct_inv_out(zy, m, half);
+            yb[1] = dct_inv_out(zy, N - 1 - m, half);
         }
         *reinterpret_cast<double2 *>(X + off) = make_double2(ya[0], ya[1]);
         *reinterpret_cast<double2 *>(X + off + plane) = make_double2(yb[0], yb[1]);

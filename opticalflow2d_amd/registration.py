@@ -398,6 +398,59 @@ class prim:
         cls._call("of2d_prim_motion_to_planar", m, m.shape[1], m.shape[0], out)
         return out
 
+    # Curvature, one call each (include/of2d.h).  curv_rhs and curv_construct
+    # take fields in the layout above; curv_eigen and curv_dct2d speak
+    # ``[dimx, dimy]`` arrays as :func:`dct2d` does.
+    @classmethod
+    def curv_rhs(cls, u, dI, It, tau):
+        """``u - tau * force`` as float64 ``[2, dimy, dimx]``, the x plane first."""
+        u = cls._f(u)
+        dimy, dimx, _ = u.shape
+        out = np.zeros((2, dimy, dimx), np.float64)
+        cls._call("of2d_prim_curv_rhs", u, cls._f(dI, u.shape), cls._f(It, (dimy, dimx)),
+                  float(tau), dimx, dimy, out[0], out[1])
+        return out
+
+    @classmethod
+    def curv_eigen(cls, dims, alpha, tau, method=0):
+        """The eigenvalue table of a ``dims = (dimx, dimy)`` level, ``E[p, q]``."""
+        dimx, dimy = int(dims[0]), int(dims[1])
+        out = np.zeros(dimx * dimy, np.float64)
+        cls._call("of2d_prim_curv_eigen", dimx, dimy, float(alpha), float(tau), int(method), out)
+        return out.reshape((dimx, dimy), order="F")
+
+    @classmethod
+    def curv_dct2d(cls, ax, ay, kind, method=0, eig=None):
+        """:func:`dct2d` of both planes in the one call an iteration makes;
+        ``eig = (alpha, tau)`` fuses the eigenvalue product (``kind`` 10 only).
+        Returns ``(x [dimx, dimy], y [dimx, dimy], (fast_x, fast_y))``."""
+        ax, ay = np.asarray(ax, dtype=np.float64), np.asarray(ay, dtype=np.float64)
+        if ax.ndim != 2 or ay.shape != ax.shape:
+            raise ValueError("ax and ay must be [dimx, dimy]")
+        dimx, dimy = ax.shape
+        bx = np.ascontiguousarray(ax.reshape(-1, order="F")).copy()
+        by = np.ascontiguousarray(ay.reshape(-1, order="F")).copy()
+        paths = np.zeros(2, np.int32)
+        alpha, tau = (0.0, 0.0) if eig is None else eig
+        cls._call("of2d_prim_curv_dct2d", bx, by, dimx, dimy, int(kind), int(method),
+                  int(eig is not None), float(alpha), float(tau), paths)
+        return (bx.reshape((dimx, dimy), order="F"), by.reshape((dimx, dimy), order="F"),
+                (int(paths[0]), int(paths[1])))
+
+    @classmethod
+    def curv_construct(cls, z, u, div):
+        """``z`` float64 ``[2, dimy, dimx]``; returns ``(out [dimy, dimx, 2],
+        (sum |out - u|, sum |u|))``, the sums from the launch's Logger partials."""
+        u = cls._f(u)
+        dimy, dimx, _ = u.shape
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.shape != (2, dimy, dimx):
+            raise ValueError(f"z is {z.shape}, expected {(2, dimy, dimx)}")
+        out = np.zeros_like(u)
+        sums = np.zeros(2, np.float64)
+        cls._call("of2d_prim_curv_construct", z[0], z[1], u, float(div), dimx, dimy, out, sums)
+        return out, (float(sums[0]), float(sums[1]))
+
 
 # ------------------------------------------------------------------ deformation analysis
 #: updates of the inverse enqueued between the host's reads (include/of2d.h)

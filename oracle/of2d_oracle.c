@@ -803,6 +803,19 @@ void oracle_dct2d(double *a, int n0, int n1, int kind) {
     dct_axis(a, (unsigned)n0, (unsigned)n1, 0, kind);
 }
 
+/* Curvature's eigenvalues (OpticalFlowCurvature.cpp:6-30): out[p*dy + q], with
+ * the reference's PI, its float tau*alpha and its float literals */
+void oracle_curvature_eigenvalues(int dimx, int dimy, float alpha, float tau, double *out) {
+    const unsigned dx = (unsigned)dimx, dy = (unsigned)dimy;
+    const double PI_ = 3.14159265;
+    for (unsigned pp = 0; pp < dx; pp++)
+        for (unsigned q = 0; q < dy; q++) {
+            unsigned idx = pp * dy + q;
+            double lam = -4 + 2 * cos(pp * PI_ / dx) + 2 * cos(q * PI_ / dy);
+            out[idx] = 1.0f / (1.0f + (double)(tau * alpha) * pow(lam, 2));
+        }
+}
+
 /* ------------------------------------------------------------------ registration */
 enum { R_DIFFUSION = 0, R_CURVATURE, R_ELASTIC, R_THIRION, R_DIFFEO, R_FLUID };
 
@@ -862,15 +875,7 @@ static void solver_init(solver *s, int reg, unsigned dx, unsigned dy, const floa
         s->rhs_x = (double *)calloc(n, sizeof(double));
         s->rhs_y = (double *)calloc(n, sizeof(double));
         s->eig = (double *)calloc(n, sizeof(double));
-        {
-            const double PI_ = 3.14159265;
-            for (unsigned pp = 0; pp < dx; pp++)
-                for (unsigned q = 0; q < dy; q++) {
-                    unsigned idx = pp * dy + q;
-                    double lam = -4 + 2 * cos(pp * PI_ / dx) + 2 * cos(q * PI_ / dy);
-                    s->eig[idx] = 1.0f / (1.0f + (double)(s->tau * s->alpha) * pow(lam, 2));
-                }
-        }
+        oracle_curvature_eigenvalues((int)dx, (int)dy, s->alpha, s->tau, s->eig);
         break;
     case R_ELASTIC: /* :49-66 */
         s->force = (v2 *)calloc(n, sizeof(v2));

@@ -80,6 +80,8 @@ void oracle_sor_sweep(float *x, const float *b, int dimx, int dimy, float mu, fl
 void oracle_get_force(const float *u, const float *dI, const float *It, int n, float *f);
 void oracle_dct2d(double *a, int n0, int n1, int kind);
 void oracle_fluid_increment(const float *u, const float *v, int dimx, int dimy, float *R);
+/* Curvature's eigenvalue table of a dimx x dimy level, out[p*dimy + q] */
+void oracle_curvature_eigenvalues(int dimx, int dimy, float alpha, float tau, double *out);
 
 /* thread/loop-order knob for the CPU baseline: 1 = reference loop order
  * (i outer, j inner, strided), 0 = row order (same results, faster) */

@@ -14,6 +14,11 @@ The oracle costs n^2 cosines per line: the two orientations of a long-line
 shape ((n, 16) and (16, n)) share one oracle run, on the same numbers
 transposed (the separable transform of the transpose is the transpose; only
 the order of the two axis passes differs, far inside the bar).
+
+of2d_dct2d transforms one plane: these cases check the x plane of the device's
+plane pair next to a y plane of zeros.  Both planes at once, the GEMM path's
+ragged tiles and the fused eigenvalue product are in
+tests/test_gpu_curvature_prims.py, against an extended-precision reference.
 """
 import functools
 

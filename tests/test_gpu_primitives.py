@@ -29,7 +29,8 @@ Arrays are in the C-ABI's layout: image [dimy, dimx], motion [dimy, dimx, 2].
 Out of scope here: the SOR sweep and the Fluid step kernels (they wait on
 other workgroups and are covered at many strip counts by test_gpu_fluid.py),
 the HS and seqnorm kernels (test_gpu_hs.py, test_gpu_seqnorm.py), Curvature
-(test_gpu_dct.py, test_gpu_curvature*.py) and the slab and rank layers.
+(test_gpu_curvature_prims.py, test_gpu_dct.py, test_gpu_curvature*.py) and the slab
+and rank layers.
 """
 import functools
 

@@ -159,6 +159,30 @@ def test_curvature_dct_matches_r2r_definitions(oracle, shape):
         np.testing.assert_allclose(b, want, rtol=1e-12, atol=1e-12 * np.abs(want).max())
 
 
+@pytest.mark.parametrize("shape", [(5, 4), (37, 64)])
+def test_curvature_eigenvalues_match_the_expression(oracle, shape):
+    """oracle_curvature_eigenvalues (the loop oracle_create runs) against the
+    reference's expression restated in numpy fp64 (OpticalFlowCurvature.cpp:6-30):
+    PI = 3.14159265, tau * alpha a float product, the square as lam * lam (what
+    the compilers make of pow(lam, 2)), the division in double.  The cosines
+    are libm's on both sides (math.cos), so the comparison is on the bits."""
+    import math
+    dx, dy = shape
+    PI_ = 3.14159265
+    cp = np.array([math.cos(p * PI_ / dx) for p in range(dx)])[:, None]
+    cq = np.array([math.cos(q * PI_ / dy) for q in range(dy)])[None, :]
+    for alpha, tau in ((0.5, 0.2), (2.0, 1.0), (1e-3, 3.0), (0.0, 1.0)):
+        ta = np.float64(np.float32(tau) * np.float32(alpha))
+        lam = (-4 + 2 * cp) + 2 * cq
+        want = 1.0 / (1.0 + ta * (lam * lam))
+        got = np.zeros(dx * dy)
+        oracle.lib().oracle_curvature_eigenvalues(dx, dy, alpha, tau, got)
+        assert want.dtype == np.float64
+        assert np.array_equal(got.reshape(dx, dy).view(np.uint64), want.view(np.uint64)), \
+            (alpha, tau)
+    assert np.all(got == 1.0)  # alpha = 0: the identity
+
+
 def test_hs_loop_mt_motion_equals_single_thread(oracle):
     """bench.py's all-cores CPU baseline (oracle_hs_loop_mt, OpenMP over
     j-lines) computes the same motion bit for bit as the sequential loop: the
