@@ -417,6 +417,69 @@ int of2d_prim_curv_dct2d(double *ax, double *ay, int dimx, int dimy, int kind, i
 int of2d_prim_curv_construct(const double *zx, const double *zy, const float *u, float div,
                              int dimx, int dimy, float *out, double *sums);
 
+/* ---- test and diagnostic entries: the SOR sweep, Fluid and Elastic, per launch ----
+ * Each entry allocates a bare level of that size with the solver's own
+ * helpers (the skewed working array, the hand-off granules, the ticket and
+ * counter words, the partials), uploads its arguments, makes the launch calls
+ * the Fluid or Elastic loop makes and no others, and downloads the results
+ * unskewed.  Layouts as above; granules are unsigned [dimy*4]: row j of region
+ * 0 as {x bits, y bits, tag, tag}.  Every entry refuses a NULL array (other
+ * than those marked optional), a size below 1 and an unknown mode with
+ * OF2D_ERR_INVALID_ARGUMENT and a message (of2d_gateway_last_error) before
+ * any device work.  Not in the reference. */
+/* launch_sor_pack.  elastic 0 (Fluid): force only, the working array's v plane
+ * holds v0 before the launch; elastic 1: v = u as well (v0 unused).  v, b: the
+ * planes after the launch; gran: region 0 (tags 0 before the launch). */
+int of2d_prim_sor_pack(const float *u, const float *dI, const float *It, const float *v0,
+                       int elastic, int dimx, int dimy, unsigned epoch, float *v, float *b,
+                       unsigned *gran);
+/* launch_regrid_pack with the Fluid loop's control words, the regrid word =
+ * regridded (0: the launch must do nothing).  dI, It, b and gran are in/out:
+ * the buffers hold the caller's values before the launch.  dimx, dimy >= 2. */
+int of2d_prim_regrid_pack(const float *Iref, const float *Iaux, const float *v0, int regridded,
+                          int dimx, int dimy, unsigned epoch, float *dI, float *It, float *b,
+                          unsigned *gran);
+/* nsweeps sweeps (epochs 1, 2, ...) of v with right-hand side b on one
+ * workspace; between sweeps only the region-0 granules are re-tagged (a copy).
+ * method 0: launch_sor on Elastic's buffers.  method 1: launch_sor_increment
+ * on Fluid's, with the estimate u; after the last sweep R, scal = {maxabs, dt},
+ * part = the increment_nblocks per-tile maxima and *path = 1 when the increment
+ * workers ran, 0 for the fallback pair (R, scal, part, u optional at method 0).
+ * zero_est: the regrid word is set.  skip_at = k (-1: none): the stop word says
+ * the loop broke before sweep k, which must do nothing.  poison: every word of
+ * the working array and of all granule regions is poison_word before v, b and
+ * the region-0 granules are written.  words = {sweep ticket, role ticket, tile
+ * counter} after the last sweep; *status the kernels' status word. */
+int of2d_prim_sor_sweep(const float *v, const float *b, const float *u, int dimx, int dimy,
+                        float mu, float lambda, float omega, int method, int nsweeps,
+                        int zero_est, int skip_at, int poison, unsigned poison_word,
+                        float *v_out, float *R, float *scal, float *part, int *path,
+                        unsigned long long *words, unsigned *status);
+/* launch_increment: R of the estimate u (read as zero with zero_est) and the
+ * velocity v, scal = {maxabs, dt}, part as above */
+int of2d_prim_fluid_increment(const float *u, const float *v, int dimx, int dimy, int zero_est,
+                              float *R, float *scal, float *part);
+/* launch_fluid_step with scal[1] = dt, then launch_fluid_report: uo, sums =
+ * {sum |uo - prev|, sum |prev|} (prev optional: NULL takes u), the Jacobian
+ * minimum, the packed force b and the region-0 granules (column 0 of v0)
+ * tagged epoch + 1 */
+int of2d_prim_fluid_step(const float *u, const float *R, const float *prev, const float *dI,
+                         const float *It, const float *v0, float dt, int zero_est, int dimx,
+                         int dimy, unsigned epoch, float *uo, double *sums, float *jmin, float *b,
+                         unsigned *gran);
+/* launch_fluid_report_decide on nb partial pairs lpart[2*nb] and minima
+ * jpart[nb]; seq (optional): the exact float sums; scal = {maxabs, dt}.  words
+ * (in/out) = {status, stop, regrid, mcur}.  The report starts as bytes 0xAB:
+ * sums[2], repf = {maxabs, dt, jmin, seq[0], seq[1], err, scal[2]} (repf[6] is
+ * in/out: scal[2] before the launch), repu = {status, flags}. */
+int of2d_prim_fluid_decide(const double *lpart, const float *jpart, int nb, const float *seq,
+                           double npx, int fixed, int it, const float *scal, unsigned *words,
+                           double *sums, float *repf, unsigned *repu);
+/* launch_logger on a working array whose v plane is v, then
+ * launch_reduce_partials: u, the new prev, sums as of2d_prim_fluid_step */
+int of2d_prim_elastic_logger(const float *v, const float *prev, int dimx, int dimy, float *u,
+                             float *prev_out, double *sums);
+
 /* ---- deformation analysis: is the registration any good? ----
  * Per-pixel passes over fields that are on the device, in the registration's
  * own layout; only the results cross the boundary.  Not in the reference's

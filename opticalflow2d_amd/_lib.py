@@ -26,6 +26,16 @@ OF2D_ERR_STATE = 4
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+_u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
+_u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
+
+
+class _f32p_opt(_f32p):
+    """A float32 array, or None for an optional (NULL) argument."""
+
+    @classmethod
+    def from_param(cls, obj):
+        return None if obj is None else _f32p.from_param(obj)
 
 PRINT_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)
 
@@ -117,6 +127,22 @@ SIGNATURES = {
                                        C.c_float, C.c_float, _i32p]),
     "of2d_prim_curv_construct": (C.c_int, [_f64p, _f64p, _f32p, C.c_float, C.c_int, C.c_int,
                                            _f32p, _f64p]),
+    "of2d_prim_sor_pack": (C.c_int, [_f32p, _f32p, _f32p, _f32p_opt, C.c_int, C.c_int, C.c_int,
+                                     C.c_uint, _f32p, _f32p, _u32p]),
+    "of2d_prim_regrid_pack": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_uint,
+                                        _f32p, _f32p, _f32p, _u32p]),
+    "of2d_prim_sor_sweep": (C.c_int, [_f32p, _f32p, _f32p_opt, C.c_int, C.c_int, C.c_float,
+                                      C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_uint, _f32p, _f32p_opt, _f32p_opt, _f32p_opt,
+                                      C.POINTER(C.c_int), _u64p, C.POINTER(C.c_uint)]),
+    "of2d_prim_fluid_increment": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p,
+                                            _f32p, _f32p]),
+    "of2d_prim_fluid_step": (C.c_int, [_f32p, _f32p, _f32p_opt, _f32p, _f32p, _f32p, C.c_float,
+                                       C.c_int, C.c_int, C.c_int, C.c_uint, _f32p, _f64p,
+                                       C.POINTER(C.c_float), _f32p, _u32p]),
+    "of2d_prim_fluid_decide": (C.c_int, [_f64p, _f32p, C.c_int, _f32p_opt, C.c_double, C.c_int,
+                                         C.c_int, _f32p, _u32p, _f64p, _f32p, _u32p]),
+    "of2d_prim_elastic_logger": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f64p]),
     "of2d_field_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_void_p, _f64p]),
     "of2d_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, _f64p]),
     "of2d_field_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_double, _f32p, _f64p,

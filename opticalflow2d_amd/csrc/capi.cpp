@@ -6,6 +6,7 @@
 // process-global singleton (WrapperOpticalFlow2d.cpp:13-155).
 #include "../../include/of2d.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -938,6 +939,366 @@ int of2d_analysis_time_kernels(int dimx, int dimy, int nlaunch, double *us) {
         }
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
+    });
+}
+
+// ------------------------------------------------------------------ SOR / Fluid / Elastic primitives
+}  // extern "C"
+
+namespace {
+constexpr unsigned kNoStop = 0x7f7f7f7fu;  // the stop word before any break (loop_fluid)
+
+// A level with nothing but the buffers solvers::alloc_level gives Elastic
+// (reg 2) or Fluid (reg 5), the 64-word status / control buffer of a context,
+// and the host side of the skewed working array and the hand-off granules.
+struct SorLevel {
+    of2d::Level L;
+    StatusWord st;
+    std::vector<float2> hvb;   // the whole vb allocation (from L.vb.base)
+    std::vector<unsigned> hH;  // every granule region
+    SorLevel(int dimx, int dimy, int reg) {
+        L.dx = dimx;
+        L.dy = dimy;
+        L.P = of2d::pitch_for(dimx);
+        of2d::solvers::alloc_level(L, reg);
+        hvb.assign(2 * L.vb.count, make_float2(0.0f, 0.0f));
+        hH.assign(2 * L.sorH.n, 0u);
+    }
+    float2 &cell(long k) { return hvb[(size_t)(2L * L.P + k)]; }  // k: sor_v / sor_b
+    unsigned *granule0(int j) { return &hH[4 * (size_t)(of2d::kSorPadRows + j)]; }
+    // every word of both allocations (the padding cells, the never-published
+    // granule rows), before put() writes the image's cells
+    void fill(unsigned word) {
+        float f;
+        memcpy(&f, &word, sizeof f);
+        std::fill(hvb.begin(), hvb.end(), make_float2(f, f));
+        std::fill(hH.begin(), hH.end(), word);
+    }
+    // v and b of the image pixels (a null plane keeps the fill) and the
+    // region-0 granules: column 0 of v tagged with `epoch` (gran non-null: those
+    // dimy x 4 words instead)
+    void put(const float *v, const float *b, unsigned epoch, const unsigned *gran = nullptr) {
+        const float2 *v2 = reinterpret_cast<const float2 *>(v);
+        const float2 *b2 = reinterpret_cast<const float2 *>(b);
+        for (int j = 0; j < L.dy; j++) {
+            for (int i = 0; i < L.dx; i++) {
+                if (v) cell(of2d::sor_v(i, j, L.P)) = v2[(size_t)j * L.dx + i];
+                if (b) cell(of2d::sor_b(i, j, L.P)) = b2[(size_t)j * L.dx + i];
+            }
+            unsigned *g = granule0(j);
+            if (gran) {
+                memcpy(g, gran + 4 * (size_t)j, 16);
+            } else {
+                memcpy(g, &cell(of2d::sor_v(0, j, L.P)), 8);
+                g[2] = g[3] = epoch;
+            }
+        }
+        OF2D_HIP(hipMemcpy(L.vb.base, hvb.data(), L.vb.bytes(), hipMemcpyHostToDevice));
+        OF2D_HIP(hipMemcpy(L.sorH.p, hH.data(), hH.size() * sizeof(unsigned),
+                           hipMemcpyHostToDevice));
+    }
+    // the region-0 granules' tags for the next sweep (their values, column 0
+    // of v, are never relaxed)
+    void retag(unsigned epoch) {
+        for (int j = 0; j < L.dy; j++) granule0(j)[2] = granule0(j)[3] = epoch;
+        OF2D_HIP(hipMemcpy(reinterpret_cast<unsigned *>(L.sorH.p) + 4 * (size_t)of2d::kSorPadRows,
+                           granule0(0), 16 * (size_t)L.dy, hipMemcpyHostToDevice));
+    }
+    void control(unsigned status, unsigned stop, unsigned regrid, unsigned mcur) {
+        unsigned w[64] = {};
+        w[0] = status;
+        w[of2d::kStopWord] = stop;
+        w[of2d::kFluidRegridWord] = regrid;
+        w[of2d::kFluidMcurWord] = mcur;
+        OF2D_HIP(hipMemcpy(st.w.p, w, sizeof w, hipMemcpyHostToDevice));
+    }
+    void words(unsigned *out) {  // status, stop, regrid, mcur
+        unsigned w[64];
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(w, st.w.p, sizeof w, hipMemcpyDeviceToHost));
+        out[0] = w[0];
+        out[1] = w[of2d::kStopWord];
+        out[2] = w[of2d::kFluidRegridWord];
+        out[3] = w[of2d::kFluidMcurWord];
+    }
+    // the unskewed planes and the region-0 granules (dimy x 4 words)
+    void get(float *v, float *b, unsigned *gran) {
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+        OF2D_HIP(hipMemcpy(hvb.data(), L.vb.base, L.vb.bytes(), hipMemcpyDeviceToHost));
+        OF2D_HIP(hipMemcpy(hH.data(), L.sorH.p, hH.size() * sizeof(unsigned),
+                           hipMemcpyDeviceToHost));
+        float2 *v2 = reinterpret_cast<float2 *>(v), *b2 = reinterpret_cast<float2 *>(b);
+        for (int j = 0; j < L.dy; j++) {
+            for (int i = 0; i < L.dx; i++) {
+                if (v) v2[(size_t)j * L.dx + i] = cell(of2d::sor_v(i, j, L.P));
+                if (b) b2[(size_t)j * L.dx + i] = cell(of2d::sor_b(i, j, L.P));
+            }
+            if (gran) memcpy(gran + 4 * (size_t)j, granule0(j), 16);
+        }
+    }
+};
+template <class T>
+void fetch(T *host, const T *dev, size_t n) {
+    OF2D_HIP(hipStreamSynchronize(nullptr));
+    OF2D_HIP(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
+}
+// a FluidReport where the Fluid loop keeps its ring: host memory the device
+// writes; every byte 0xAB until a kernel writes it
+struct HostReport {
+    of2d::FluidReport *p = nullptr;
+    HostReport() {
+        OF2D_HIP(hipHostMalloc(&p, sizeof(of2d::FluidReport),
+                               hipHostMallocCoherent | hipHostMallocMapped));
+        memset(p, 0xAB, sizeof(of2d::FluidReport));
+    }
+    ~HostReport() {
+        if (p) (void)hipHostFree(p);
+    }
+    HostReport(const HostReport &) = delete;
+    HostReport &operator=(const HostReport &) = delete;
+};
+}  // namespace
+
+extern "C" {
+
+int of2d_prim_sor_pack(const float *u, const float *dI, const float *It, const float *v0,
+                       int elastic, int dimx, int dimy, unsigned epoch, float *v, float *b,
+                       unsigned *gran) {
+    if (!u || !dI || !It || !v || !b || !gran)
+        return refuse(nullptr, "of2d_prim_sor_pack: u, dI, It, v, b or gran is NULL");
+    if (elastic != 0 && elastic != 1) return refuse(nullptr, "of2d_prim_sor_pack: elastic is 0 or 1");
+    if (!elastic && !v0)
+        return refuse(nullptr, "of2d_prim_sor_pack: the force-only mode takes the prior v plane");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_sor_pack: dimx, dimy < 1");
+    return prim(true, [&] {
+        SorLevel S(dimx, dimy, elastic ? 2 : 5);
+        of2d::Field<float2> m, g;
+        of2d::Field<float> t;
+        upload(m, u, dimx, dimy);
+        upload(g, dI, dimx, dimy);
+        upload(t, It, dimx, dimy);
+        S.put(elastic ? nullptr : v0, nullptr, 0u);  // stale granules: tag 0
+        of2d::launch_sor_pack(S.L.vb.p, m.p, g.p, t.p, elastic ? m.p : nullptr, dimx, dimy,
+                              S.L.P, S.L.sorH.p, epoch, nullptr);
+        S.get(v, b, gran);
+    });
+}
+
+int of2d_prim_regrid_pack(const float *Iref, const float *Iaux, const float *v0, int regridded,
+                          int dimx, int dimy, unsigned epoch, float *dI, float *It, float *b,
+                          unsigned *gran) {
+    if (!Iref || !Iaux || !v0 || !dI || !It || !b || !gran)
+        return refuse(nullptr, "of2d_prim_regrid_pack: Iref, Iaux, v0, dI, It, b or gran is NULL");
+    if (regridded != 0 && regridded != 1)
+        return refuse(nullptr, "of2d_prim_regrid_pack: regridded is 0 or 1");
+    if (dimx < 2 || dimy < 2)
+        return refuse(nullptr, "of2d_prim_regrid_pack: the gradients need dimx >= 2 and dimy >= 2");
+    return prim(true, [&] {
+        SorLevel S(dimx, dimy, 5);
+        of2d::Field<float> ir, ia, t;
+        of2d::Field<float2> g;
+        upload(ir, Iref, dimx, dimy);
+        upload(ia, Iaux, dimx, dimy);
+        upload(g, dI, dimx, dimy);
+        upload(t, It, dimx, dimy);
+        S.put(v0, b, 0u, gran);
+        S.control(0u, kNoStop, (unsigned)regridded, 0u);
+        of2d::launch_regrid_pack(ir.p, ia.p, g.p, t.p, S.L.vb.p, dimx, dimy, S.L.P, S.L.sorH.p,
+                                 epoch, nullptr, of2d::FluidCtl{S.st.w.p, 1});
+        download(dI, g.p, g.P, dimx, dimy);
+        download(It, t.p, t.P, dimx, dimy);
+        S.get(nullptr, b, gran);
+    });
+}
+
+int of2d_prim_sor_sweep(const float *v, const float *b, const float *u, int dimx, int dimy,
+                        float mu, float lambda, float omega, int method, int nsweeps,
+                        int zero_est, int skip_at, int poison, unsigned poison_word,
+                        float *v_out, float *R, float *scal, float *part, int *path,
+                        unsigned long long *words, unsigned *status) {
+    if (!v || !b || !v_out || !words || !status || !path)
+        return refuse(nullptr, "of2d_prim_sor_sweep: v, b, v_out, path, words or status is NULL");
+    if (method != 0 && method != 1)
+        return refuse(nullptr, "of2d_prim_sor_sweep: method is 0 (launch_sor) or 1 "
+                               "(launch_sor_increment)");
+    if (method == 1 && (!u || !R || !scal || !part))
+        return refuse(nullptr, "of2d_prim_sor_sweep: method 1 takes u and returns R, scal, part");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_sor_sweep: dimx, dimy < 1");
+    if (nsweeps < 1) return refuse(nullptr, "of2d_prim_sor_sweep: nsweeps < 1");
+    if (skip_at < -1 || skip_at >= nsweeps)
+        return refuse(nullptr, "of2d_prim_sor_sweep: skip_at is -1 or a sweep of the call");
+    return prim(true, [&] {
+        SorLevel S(dimx, dimy, method ? 5 : 2);
+        of2d::Level &L = S.L;
+        of2d::Field<float2> m;
+        of2d::DevArray<float> sc;
+        sc.alloc(4);
+        upload(m, method ? u : nullptr, dimx, dimy);
+        if (poison) S.fill(poison_word);
+        const unsigned ep0 = 1u;
+        S.put(v, b, ep0);
+        // the stop word of a loop that broke at iteration 0: sweep skip_at runs
+        // as iteration 1, every other sweep as iteration 0
+        S.control(0u, skip_at >= 0 ? 0u : kNoStop, zero_est ? 1u : 0u, 0u);
+        *path = method ? (of2d::sor_increment_plan(dimx, dimy) > 0 ? 1 : 0) : 0;
+        for (int s = 0; s < nsweeps; s++) {
+            const of2d::FluidCtl c{S.st.w.p, s == skip_at ? 1 : 0};
+            if (s) S.retag(ep0 + (unsigned)s);
+            if (method)
+                of2d::launch_sor_increment(L.vb.p, dimx, dimy, L.P, mu, lambda, omega, L.sorH.p,
+                                           ep0 + (unsigned)s, L.sorTicket.p, L.sorCtr.p, m.p,
+                                           L.increment.p, L.part.p, sc.p, S.st.w.p, nullptr, c);
+            else
+                of2d::launch_sor(L.vb.p, dimx, dimy, L.P, mu, lambda, omega, L.sorH.p,
+                                 ep0 + (unsigned)s, L.sorTicket.p, S.st.w.p, nullptr, c);
+        }
+        S.get(v_out, nullptr, nullptr);
+        unsigned w[4];
+        S.words(w);
+        *status = w[0];
+        unsigned t = 0;
+        fetch(&t, L.sorTicket.p, 1);
+        words[0] = t;
+        words[1] = words[2] = 0;
+        if (method) {
+            fetch(words + 1, L.sorCtr.p, 2);
+            download(R, L.increment.p, L.increment.P, dimx, dimy);
+            fetch(scal, sc.p, 2);
+            fetch(part, L.part.p, (size_t)of2d::increment_nblocks(dimx, dimy));
+        }
+    });
+}
+
+int of2d_prim_fluid_increment(const float *u, const float *v, int dimx, int dimy, int zero_est,
+                              float *R, float *scal, float *part) {
+    if (!u || !v || !R || !scal || !part)
+        return refuse(nullptr, "of2d_prim_fluid_increment: u, v, R, scal or part is NULL");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_fluid_increment: dimx, dimy < 1");
+    return prim(true, [&] {
+        SorLevel S(dimx, dimy, 5);
+        of2d::Level &L = S.L;
+        of2d::Field<float2> m;
+        of2d::DevArray<float> sc;
+        sc.alloc(4);
+        upload(m, u, dimx, dimy);
+        S.put(v, nullptr, 0u);
+        S.control(0u, kNoStop, zero_est ? 1u : 0u, 0u);
+        of2d::launch_increment(m.p, L.vb.p, L.increment.p, dimx, dimy, L.P, L.part.p, sc.p,
+                               nullptr, of2d::FluidCtl{S.st.w.p, 0});
+        download(R, L.increment.p, L.increment.P, dimx, dimy);
+        fetch(scal, sc.p, 2);
+        fetch(part, L.part.p, (size_t)of2d::increment_nblocks(dimx, dimy));
+    });
+}
+
+int of2d_prim_fluid_step(const float *u, const float *R, const float *prev, const float *dI,
+                         const float *It, const float *v0, float dt, int zero_est, int dimx,
+                         int dimy, unsigned epoch, float *uo, double *sums, float *jmin, float *b,
+                         unsigned *gran) {
+    if (!u || !R || !dI || !It || !v0 || !uo || !sums || !jmin || !b || !gran)
+        return refuse(nullptr, "of2d_prim_fluid_step: an array other than prev is NULL");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_fluid_step: dimx, dimy < 1");
+    return prim(true, [&] {
+        SorLevel S(dimx, dimy, 5);
+        of2d::Level &L = S.L;
+        of2d::Field<float2> m, r, o, pv, g;
+        of2d::Field<float> t;
+        upload(m, u, dimx, dimy);
+        upload(r, R, dimx, dimy);
+        upload(o, nullptr, dimx, dimy);
+        if (prev) upload(pv, prev, dimx, dimy);
+        upload(g, dI, dimx, dimy);
+        upload(t, It, dimx, dimy);
+        const int nb = of2d::increment_nblocks(dimx, dimy);
+        of2d::DevArray<double> lpart;
+        of2d::DevArray<float> sc;
+        lpart.alloc(2 * (size_t)nb);
+        sc.alloc(4);
+        const float s[2] = {0.0f, dt};
+        OF2D_HIP(hipMemcpy(sc.p, s, sizeof s, hipMemcpyHostToDevice));
+        S.put(v0, nullptr, 0u);
+        S.control(0u, kNoStop, zero_est ? 1u : 0u, 0u);
+        HostReport rep;
+        // the next sweep's epoch, as loop_fluid passes it
+        of2d::launch_fluid_step(m.p, r.p, o.p, prev ? pv.p : nullptr, sc.p, g.p, t.p, L.vb.p,
+                                dimx, dimy, L.P, L.sorH.p, epoch + 1, lpart.p, L.part.p, nullptr,
+                                of2d::FluidCtl{S.st.w.p, 0});
+        of2d::launch_fluid_report(lpart.p, nb, L.part.p, sc.p, S.st.w.p, rep.p, nullptr);
+        download(uo, o.p, o.P, dimx, dimy);
+        S.get(nullptr, b, gran);
+        sums[0] = rep.p->sums[0];
+        sums[1] = rep.p->sums[1];
+        *jmin = rep.p->jmin;
+    });
+}
+
+int of2d_prim_fluid_decide(const double *lpart, const float *jpart, int nb, const float *seq,
+                           double npx, int fixed, int it, const float *scal, unsigned *words,
+                           double *sums, float *repf, unsigned *repu) {
+    if (!lpart || !jpart || !scal || !words || !sums || !repf || !repu)
+        return refuse(nullptr, "of2d_prim_fluid_decide: an array other than seq is NULL");
+    if (nb < 1) return refuse(nullptr, "of2d_prim_fluid_decide: nb < 1");
+    if (!(npx >= 1.0)) return refuse(nullptr, "of2d_prim_fluid_decide: npx < 1");
+    if (it < 0) return refuse(nullptr, "of2d_prim_fluid_decide: it < 0");
+    return prim(true, [&] {
+        StatusWord st;
+        of2d::DevArray<double> lp;
+        of2d::DevArray<float> jp, sq, sc;
+        lp.alloc(2 * (size_t)nb);
+        jp.alloc((size_t)nb);
+        sq.alloc(2);
+        sc.alloc(4);
+        OF2D_HIP(hipMemcpy(lp.p, lpart, 2 * (size_t)nb * sizeof(double), hipMemcpyHostToDevice));
+        OF2D_HIP(hipMemcpy(jp.p, jpart, (size_t)nb * sizeof(float), hipMemcpyHostToDevice));
+        if (seq) OF2D_HIP(hipMemcpy(sq.p, seq, 2 * sizeof(float), hipMemcpyHostToDevice));
+        const float s[3] = {scal[0], scal[1], repf[6]};  // scal[2]: the caller's marker
+        OF2D_HIP(hipMemcpy(sc.p, s, sizeof s, hipMemcpyHostToDevice));
+        unsigned w[64] = {};
+        w[0] = words[0];
+        w[of2d::kStopWord] = words[1];
+        w[of2d::kFluidRegridWord] = words[2];
+        w[of2d::kFluidMcurWord] = words[3];
+        OF2D_HIP(hipMemcpy(st.w.p, w, sizeof w, hipMemcpyHostToDevice));
+        HostReport rep;
+        of2d::launch_fluid_report_decide(lp.p, nb, jp.p, sc.p, seq ? sq.p : nullptr, npx,
+                                         fixed != 0, rep.p, nullptr, of2d::FluidCtl{st.w.p, it});
+        fetch(w, st.w.p, 64);
+        words[0] = w[0];
+        words[1] = w[of2d::kStopWord];
+        words[2] = w[of2d::kFluidRegridWord];
+        words[3] = w[of2d::kFluidMcurWord];
+        const of2d::FluidReport &r = *rep.p;
+        sums[0] = r.sums[0];
+        sums[1] = r.sums[1];
+        const float f[6] = {r.maxabs, r.dt, r.jmin, r.seq[0], r.seq[1], r.err};
+        memcpy(repf, f, sizeof f);
+        fetch(repf + 6, sc.p + 2, 1);
+        repu[0] = r.status;
+        repu[1] = r.flags;
+    });
+}
+
+int of2d_prim_elastic_logger(const float *v, const float *prev, int dimx, int dimy, float *u,
+                             float *prev_out, double *sums) {
+    if (!v || !prev || !u || !prev_out || !sums)
+        return refuse(nullptr, "of2d_prim_elastic_logger: v, prev, u, prev_out or sums is NULL");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_elastic_logger: dimx, dimy < 1");
+    return prim(true, [&] {
+        SorLevel S(dimx, dimy, 2);
+        of2d::Level &L = S.L;
+        of2d::Field<float2> est, pv;
+        upload(est, nullptr, dimx, dimy);
+        upload(pv, prev, dimx, dimy);
+        const int nb = of2d::increment_nblocks(dimx, dimy);
+        of2d::DevArray<double> part, ds;
+        part.alloc(2 * (size_t)nb);
+        ds.alloc(2);
+        S.put(v, nullptr, 0u);
+        of2d::launch_logger(L.vb.p, est.p, pv.p, dimx, dimy, L.P, part.p, nullptr);
+        of2d::launch_reduce_partials(part.p, nb, 1, ds.p, nullptr);
+        download(u, est.p, est.P, dimx, dimy);
+        download(prev_out, pv.p, pv.P, dimx, dimy);
+        fetch(sums, ds.p, 2);
     });
 }
 

@@ -950,13 +950,11 @@ void launch_increment(const float2 *u, const float4 *vel, float2 *R, int dimx, i
 #endif
 int sor_increment_workers() { return OF2D_SOR_NCONS; }
 
-void launch_sor_increment(float4 *vb, int dimx, int dimy, int P, float mu, float lambda,
-                          float omega, void *H, unsigned epoch, unsigned *ticket,
-                          unsigned long long *ctr, const float2 *u, float2 *R, float *part,
-                          float *scal, unsigned *status, hipStream_t st, FluidCtl ctl) {
+// launch_sor_increment's decision: the worker workgroups of its fused launch,
+// 0 where it falls back to launch_sor + launch_increment
+int sor_increment_plan(int dimx, int dimy) {
     const int ns = sor_nstrips(dimx);
-    const dim3 g = field_grid(dimx, dimy);
-    const int ntiles = (int)(g.x * g.y);
+    const int ntiles = increment_nblocks(dimx, dimy);
     // one 256-thread workgroup per CU (a strip's or a worker's; registers
     // allow one wave per SIMD): no strip shares its CU's load path
     int dev = 0;
@@ -971,7 +969,19 @@ void launch_sor_increment(float4 *vb, int dimx, int dimy, int P, float mu, float
     int nwg = sor_increment_workers();
     if (nwg < 0) nwg = ncu - ns;
     nwg = std::min(nwg, (ntiles + 3) / 4);
-    if (ns == 0 || dimx < 3 || dimy < 3 || nwg < 8) {  // no sweep (OpticalFlowFluid.cpp:23-24)
+    // no sweep (OpticalFlowFluid.cpp:23-24), or too few workers
+    return (ns == 0 || dimx < 3 || dimy < 3 || nwg < 8) ? 0 : nwg;
+}
+
+void launch_sor_increment(float4 *vb, int dimx, int dimy, int P, float mu, float lambda,
+                          float omega, void *H, unsigned epoch, unsigned *ticket,
+                          unsigned long long *ctr, const float2 *u, float2 *R, float *part,
+                          float *scal, unsigned *status, hipStream_t st, FluidCtl ctl) {
+    const int ns = sor_nstrips(dimx);
+    const dim3 g = field_grid(dimx, dimy);
+    const int ntiles = (int)(g.x * g.y);
+    const int nwg = sor_increment_plan(dimx, dimy);
+    if (nwg == 0) {
         launch_sor(vb, dimx, dimy, P, mu, lambda, omega, H, epoch, ticket, status, st, ctl);
         launch_increment(u, vb, R, dimx, dimy, P, part, scal, st, ctl);
         return;
@@ -1075,9 +1085,11 @@ __global__ __launch_bounds__(256) void fluid_step_kernel(
         const float2 m = un[r][c];
         const float2 pv = pvk[k];
         uo[idx] = m;
-        const float ex = m.x - pv.x, ey = m.y - pv.y;
-        sd += (double)__builtin_sqrtf(ex * ex + ey * ey);
-        sp += (double)__builtin_sqrtf(pv.x * pv.x + pv.y * pv.y);
+        // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
+        const double ex = (double)(m.x - pv.x), ey = (double)(m.y - pv.y);
+        const double qx = (double)pv.x, qy = (double)pv.y;
+        sd += sqrt(ex * ex + ey * ey);
+        sp += sqrt(qx * qx + qy * qy);
         // motion_gradients of the new u (gradients.h:9-32)
         float2 dx, dy;
         if (i == 0) {
@@ -1275,9 +1287,11 @@ __global__ __launch_bounds__(256) void logger_kernel(const float4 *__restrict__ 
         const long idx = (long)j * P + i;
         const float2 m = vt[4 * k + threadIdx.y][threadIdx.x], pv = prev[idx];
         u[idx] = m;
-        const float ex = m.x - pv.x, ey = m.y - pv.y;
-        sd += (double)__builtin_sqrtf(ex * ex + ey * ey);
-        sp += (double)__builtin_sqrtf(pv.x * pv.x + pv.y * pv.y);
+        // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
+        const double ex = (double)(m.x - pv.x), ey = (double)(m.y - pv.y);
+        const double qx = (double)pv.x, qy = (double)pv.y;
+        sd += sqrt(ex * ex + ey * ey);
+        sp += sqrt(qx * qx + qy * qy);
         prev[idx] = m;
     }
     block_sum2(sd, sp, partial);

@@ -599,6 +599,9 @@ int increment_nblocks(int dimx, int dimy);
 // + launch_increment where too few CUs are left for workers; with
 // sor_increment_workers() == 0 (OF2D_SOR_NCONS=0) the caller runs those.
 int sor_increment_workers();
+// what launch_sor_increment does at this size on the current device: the
+// worker workgroups of the fused launch, 0 for the fallback pair
+int sor_increment_plan(int dimx, int dimy);
 void launch_sor_increment(float4 *vb, int dimx, int dimy, int P, float mu, float lambda,
                           float omega, void *H, unsigned epoch, unsigned *ticket,
                           unsigned long long *ctr, const float2 *u, float2 *R, float *part,

@@ -451,6 +451,128 @@ class prim:
         cls._call("of2d_prim_curv_construct", z[0], z[1], u, float(div), dimx, dimy, out, sums)
         return out, (float(sums[0]), float(sums[1]))
 
+    # The SOR sweep, Fluid and Elastic, per launch (include/of2d.h).  Granules
+    # are uint32 ``[dimy, 4]``: row j of region 0 as (x bits, y bits, tag, tag).
+    @staticmethod
+    def increment_nblocks(dimx, dimy):
+        """The 64 x 32 tiles of the Fluid field kernels (their partial slots)."""
+        return ((dimx + 63) // 64) * ((dimy + 31) // 32)
+
+    @classmethod
+    def sor_pack(cls, u, dI, It, v0=None, epoch=1):
+        """``v0`` given: Fluid's force-only pack over a working array whose v
+        plane holds ``v0``; None: Elastic's pack with v = u.  Returns
+        ``(v, b, granules)``."""
+        u = cls._f(u)
+        dimy, dimx, _ = u.shape
+        v, b = np.zeros_like(u), np.zeros_like(u)
+        gran = np.zeros((dimy, 4), np.uint32)
+        cls._call("of2d_prim_sor_pack", u, cls._f(dI, u.shape), cls._f(It, (dimy, dimx)),
+                  None if v0 is None else cls._f(v0, u.shape), int(v0 is None), dimx, dimy,
+                  int(epoch), v, b, gran)
+        return v, b, gran
+
+    @classmethod
+    def regrid_pack(cls, Iref, Iaux, v0, regridded, dI, It, b, gran, epoch=1):
+        """``dI``, ``It``, ``b``, ``gran``: the buffers' content before the
+        launch.  Returns their content after it, ``(dI, It, b, granules)``."""
+        Iref = cls._f(Iref)
+        dimy, dimx = Iref.shape
+        m = (dimy, dimx, 2)
+        dI, It, b = cls._f(dI, m).copy(), cls._f(It, (dimy, dimx)).copy(), cls._f(b, m).copy()
+        gran = np.ascontiguousarray(gran, dtype=np.uint32).copy()
+        if gran.shape != (dimy, 4):
+            raise ValueError(f"gran is {gran.shape}, expected {(dimy, 4)}")
+        cls._call("of2d_prim_regrid_pack", Iref, cls._f(Iaux, (dimy, dimx)), cls._f(v0, m),
+                  int(bool(regridded)), dimx, dimy, int(epoch), dI, It, b, gran)
+        return dI, It, b, gran
+
+    @classmethod
+    def sor_sweep(cls, v, b, mu, lam, omega, nsweeps=1, method=0, u=None, zero_est=False,
+                  skip_at=-1, poison=None):
+        """``nsweeps`` sweeps of ``v``.  Returns a dict: ``v``, ``status``,
+        ``words`` (sweep ticket, role ticket, tile counter) and, for
+        ``method`` 1, ``R``, ``maxabs``, ``dt``, ``part``, ``path``."""
+        v = cls._f(v)
+        dimy, dimx, _ = v.shape
+        out = np.zeros_like(v)
+        words = np.zeros(3, np.uint64)
+        path, status = C.c_int(-1), C.c_uint(0)
+        R = scal = part = None
+        if method:
+            R, scal = np.zeros_like(v), np.zeros(2, np.float32)
+            part = np.zeros(cls.increment_nblocks(dimx, dimy), np.float32)
+        cls._call("of2d_prim_sor_sweep", v, cls._f(b, v.shape),
+                  None if u is None else cls._f(u, v.shape), dimx, dimy, float(mu), float(lam),
+                  float(omega), int(method), int(nsweeps), int(bool(zero_est)), int(skip_at),
+                  int(poison is not None), int(poison or 0), out, R, scal, part, C.byref(path),
+                  words, C.byref(status))
+        res = {"v": out, "status": status.value, "words": tuple(int(w) for w in words),
+               "path": path.value}
+        if method:
+            res.update(R=R, maxabs=scal[0], dt=scal[1], part=part)
+        return res
+
+    @classmethod
+    def fluid_increment(cls, u, v, zero_est=False):
+        """Returns ``(R, maxabs, dt, part)``."""
+        u = cls._f(u)
+        dimy, dimx, _ = u.shape
+        R, scal = np.zeros_like(u), np.zeros(2, np.float32)
+        part = np.zeros(cls.increment_nblocks(dimx, dimy), np.float32)
+        cls._call("of2d_prim_fluid_increment", u, cls._f(v, u.shape), dimx, dimy,
+                  int(bool(zero_est)), R, scal, part)
+        return R, scal[0], scal[1], part
+
+    @classmethod
+    def fluid_step(cls, u, R, dI, It, v0, dt, prev=None, zero_est=False, epoch=1):
+        """Returns a dict: ``uo``, ``sums``, ``jmin``, ``b``, ``gran``."""
+        u = cls._f(u)
+        dimy, dimx, _ = u.shape
+        uo, b = np.zeros_like(u), np.zeros_like(u)
+        gran = np.zeros((dimy, 4), np.uint32)
+        sums, jmin = np.zeros(2, np.float64), C.c_float(0)
+        cls._call("of2d_prim_fluid_step", u, cls._f(R, u.shape),
+                  None if prev is None else cls._f(prev, u.shape), cls._f(dI, u.shape),
+                  cls._f(It, (dimy, dimx)), cls._f(v0, u.shape), float(dt), int(bool(zero_est)),
+                  dimx, dimy, int(epoch), uo, sums, C.byref(jmin), b, gran)
+        return {"uo": uo, "sums": (float(sums[0]), float(sums[1])),
+                "jmin": np.float32(jmin.value), "b": b, "gran": gran}
+
+    @classmethod
+    def fluid_decide(cls, lpart, jpart, npx, fixed, it, words, seq=None, scal=(0.0, 0.0),
+                     marker=-1234.5):
+        """``lpart`` float64 ``[nb, 2]``, ``jpart`` float32 ``[nb]``, ``words`` =
+        (status, stop, regrid, mcur).  Returns a dict: ``words`` after the
+        launch, the report's fields (``flags`` 0xABABABAB: not written) and
+        ``scal2`` (``marker`` when not written)."""
+        lpart = np.ascontiguousarray(lpart, dtype=np.float64)
+        jpart = cls._f(jpart)
+        nb = jpart.size
+        if lpart.shape != (nb, 2):
+            raise ValueError(f"lpart is {lpart.shape}, expected {(nb, 2)}")
+        w = np.array(words, dtype=np.uint32)
+        if w.shape != (4,):
+            raise ValueError("words is (status, stop, regrid, mcur)")
+        sums, repf, repu = np.zeros(2), np.zeros(7, np.float32), np.zeros(2, np.uint32)
+        repf[6] = marker
+        cls._call("of2d_prim_fluid_decide", lpart.reshape(-1), jpart, nb,
+                  None if seq is None else cls._f(seq, (2,)), float(npx), int(bool(fixed)),
+                  int(it), cls._f(scal, (2,)), w, sums, repf, repu)
+        return {"words": tuple(int(x) for x in w), "sums": (float(sums[0]), float(sums[1])),
+                "maxabs": repf[0], "dt": repf[1], "jmin": repf[2], "seq": (repf[3], repf[4]),
+                "err": repf[5], "scal2": repf[6], "status": int(repu[0]), "flags": int(repu[1])}
+
+    @classmethod
+    def elastic_logger(cls, v, prev):
+        """Returns ``(u, new prev, (sum |u - prev|, sum |prev|))``."""
+        v = cls._f(v)
+        dimy, dimx, _ = v.shape
+        u, pv = np.zeros_like(v), np.zeros_like(v)
+        sums = np.zeros(2, np.float64)
+        cls._call("of2d_prim_elastic_logger", v, cls._f(prev, v.shape), dimx, dimy, u, pv, sums)
+        return u, pv, (float(sums[0]), float(sums[1]))
+
 
 # ------------------------------------------------------------------ deformation analysis
 #: updates of the inverse enqueued between the host's reads (include/of2d.h)

@@ -26,9 +26,9 @@ read past a one-pixel axis.
 
 Arrays are in the C-ABI's layout: image [dimy, dimx], motion [dimy, dimx, 2].
 
-Out of scope here: the SOR sweep and the Fluid step kernels (they wait on
-other workgroups and are covered at many strip counts by test_gpu_fluid.py),
-the HS and seqnorm kernels (test_gpu_hs.py, test_gpu_seqnorm.py), Curvature
+Out of scope here: the SOR sweep, Fluid and Elastic kernels
+(test_gpu_fluid_prims.py), the HS and seqnorm kernels (test_gpu_hs.py,
+test_gpu_seqnorm.py), Curvature
 (test_gpu_curvature_prims.py, test_gpu_dct.py, test_gpu_curvature*.py) and the slab
 and rank layers.
 """
