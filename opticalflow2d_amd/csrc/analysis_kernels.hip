@@ -16,43 +16,8 @@
 
 namespace of2d {
 
-namespace {
-// wave tree sums / extrema in the order of reduce_partials_kernel
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned o = __shfl_down(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-}  // namespace
+// (wave_sum, wave_min, wave_max and the order of every sum below: the shared
+// helpers of of2d_device.h, "Logger sums")
 
 // ------------------------------------------------------------ Jacobian
 // A block of 256 threads takes a kJacW x kJacH pixel tile: the tile of u plus

@@ -149,27 +149,9 @@ __global__ __launch_bounds__(256) void curv_construct_kernel(const double *__res
         const float2 n = make_float2((float)Z[idx] / div, (float)Z[plane + idx] / div);
         const float2 o = u[idx];
         out[idx] = n;
-        // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
-        const double ex = (double)(n.x - o.x), ey = (double)(n.y - o.y);
-        const double qx = (double)o.x, qy = (double)o.y;
-        sd = sqrt(ex * ex + ey * ey);
-        sp = sqrt(qx * qx + qy * qy);
+        logger_add(n, o, sd, sp);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        sd += __shfl_down(sd, off);
-        sp += __shfl_down(sp, off);
-    }
-    __shared__ double red[2][4];
-    if (threadIdx.x == 0) {
-        red[0][threadIdx.y] = sd;
-        red[1][threadIdx.y] = sp;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
-        partial[2 * blk] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        partial[2 * blk + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    }
+    block_logger_partial(sd, sp, partial);
 }
 int curv_nblocks(int dimx, int dimy) { return ((dimx + 63) / 64) * ((dimy + 3) / 4); }
 void launch_curv_construct(const double *Z, long plane, const float2 *u, float2 *out, float div,

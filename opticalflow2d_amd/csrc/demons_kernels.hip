@@ -35,6 +35,7 @@
 
 #include <cmath>
 #include <stdexcept>
+#include <type_traits>
 
 namespace of2d {
 
@@ -364,9 +365,12 @@ __device__ __forceinline__ bool conv_rows_interior(int i, int j0, int dimx, int 
 // each tap column are read once and shared by the R outputs (each output
 // still sums ii outer / jj inner, the reference's order), x and y as one
 // packed pair (PK) or as two scalars; otherwise per pixel.
-// W1: the interior weight sum (float)wfull is exactly 1 (a normalised kernel,
-// the reference's set_gaussian / set_average), so acc / wf is acc itself
-template <int KW, int R, bool PK, bool W1 = false, int TX = kCx>
+// A compile-time width is launched only where the interior weight sum
+// (float)wfull is exactly 1 (every normalised odd kernel, the reference's
+// set_gaussian / set_average; tests/test_gpu_logger_partials.py): acc / 1.0f
+// is acc itself, so the interior result is the accumulator.  The runtime
+// width (conv_px) divides.
+template <int KW, int R, bool PK, int TX = kCx>
 __device__ __forceinline__ void convR(const float2 *tile, const ConvArgs &a, int i, int j0,
                                       int tx, int ty0, int dimx, int dimy, long N, float2 res[R],
                                       bool has[R]) {
@@ -397,12 +401,10 @@ __device__ __forceinline__ void convR(const float2 *tile, const ConvArgs &a, int
                         }
                     }
             }
-            const float wf = (float)a.wfull;
 #pragma unroll
             for (int k = 0; k < R; k++) {
-                has[k] = W1 || a.wfull != 0;
-                res[k] = W1 ? make_float2(acc[k].x, acc[k].y)
-                            : make_float2(acc[k].x / wf, acc[k].y / wf);
+                has[k] = true;
+                res[k] = make_float2(acc[k].x, acc[k].y);
             }
             return;
         }
@@ -633,12 +635,11 @@ __global__ __launch_bounds__(256) void smooth_compose_kernel(
 // neighbour is exactly the column across the seam), so the convolution reads
 // the reference's tap values from LDS like anywhere else.  Needs one wrap at
 // most: dimx >= 2 * 64 (launch_demons_update).
-// FAST: (float)ca.wfull == 1 and sigma_xsq a power of two whose reciprocal
-// `sxq` carries (convR W1, demons_corr SXP); otherwise `sxq` is sigma_xsq
+// FAST: sigma_xsq is a power of two whose reciprocal `sxq` carries
+// (demons_corr SXP); otherwise `sxq` is sigma_xsq
 // TX x (TY R) output tile: TX (64 or 128) threads across (one or two waves
 // per tile row of threads), TY thread rows of R j-lines each
-// SEP: the separable form on the interior pixels (sepR); FAST is then the
-// sigma_xsq condition alone
+// SEP: the separable form on the interior pixels (sepR)
 template <int KW, int R, bool FAST, int TX = kCx, int TY = kCThreadsY, bool SEP = false>
 __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_kernel(
     const float *__restrict__ Iref, const float *__restrict__ Imov, const float2 *__restrict__ u,
@@ -766,7 +767,7 @@ __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_k
     if constexpr (SEP)
         sepR<KW, R, TX>(ct, ca, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
     else
-        convR<KW, R, true, FAST, TX>(ct, ca, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+        convR<KW, R, true, TX>(ct, ca, i, y0 + r0, threadIdx.x, r0, dimx, dimy, N, sm, has);
     float2 cv[R];
 #pragma unroll
     for (int k = 0; k < R; k++) {
@@ -785,8 +786,8 @@ __global__ __launch_bounds__(TX * TY) OF2D_DEMONS_FUSED_ATTR void demons_fused_k
 // to ~1e-16 relative, tests/test_gpu_primitives.py).  The R previous-motion
 // loads of a thread are issued together after the convolution, whose
 // registers they reuse.
-// SEP: the separable form on the interior pixels (sepR; W1 unused)
-template <int KW, int R = kCr, bool PK = true, bool W1 = false, bool NORM = true, bool SEP = false>
+// SEP: the separable form on the interior pixels (sepR)
+template <int KW, int R = kCr, bool PK = true, bool NORM = true, bool SEP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEP ? 4 : (KW == 7 ? 7 : 8)))) void smooth_norm_kernel(const float2 *__restrict__ umid,
                                                           const float2 *__restrict__ prev,
                                                           float2 *__restrict__ out, int dimx,
@@ -808,11 +809,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEP ? 4 : (
         if constexpr (SEP)
             sepR<KW, R>(tile, a, i, j0, threadIdx.x, r0, dimx, dimy, N, sm, has);
         else
-            convR<KW, R, PK, W1>(tile, a, i, j0, threadIdx.x, r0, dimx, dimy, N, sm, has);
+            convR<KW, R, PK>(tile, a, i, j0, threadIdx.x, r0, dimx, dimy, N, sm, has);
         // every output of the thread is the convolution's: no fallback loads
         // of u_mid (the loads below are skipped by branch, not by select)
-        const bool conv_all =
-            (W1 || SEP) && KW > 0 && conv_rows_interior<KW, R>(i, j0, dimx, dimy, N);
+        const bool conv_all = KW > 0 && conv_rows_interior<KW, R>(i, j0, dimx, dimy, N);
         float2 pv[R];
         if (NORM) {
 #pragma unroll
@@ -827,32 +827,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEP ? 4 : (
             float2 v = sm[k];
             if (!conv_all && !has[k]) v = umid[idx];
             out[idx] = v;
-            if (NORM) {
-                // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
-                const double ex = (double)(v.x - pv[k].x), ey = (double)(v.y - pv[k].y);
-                const double qx = (double)pv[k].x, qy = (double)pv[k].y;
-                sd += sqrt(ex * ex + ey * ey);
-                sp += sqrt(qx * qx + qy * qy);
-            }
+            if (NORM) logger_add(v, pv[k], sd, sp);
         }
     }
     if (!NORM) return;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sd += __shfl_down(sd, off);
-        sp += __shfl_down(sp, off);
-    }
-    __shared__ double red[2][4];
-    if (threadIdx.x == 0) {
-        red[0][threadIdx.y] = sd;
-        red[1][threadIdx.y] = sp;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
-        partial[2 * blk] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        partial[2 * blk + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    }
+    block_logger_partial(sd, sp, partial);
 }
 
 inline size_t conv_lds_bytes(int cx, int cy, int R = kCr) {
@@ -872,9 +851,44 @@ bool demons_separable_ok(int kw, int dimx) {
 }
 
 namespace {
-// the separable kernels' widths: X(kw) for every odd kw in [3, kSepKwMax]
+// the widths compiled in, each listed once: X(kw) for every odd kw in
+// [3, kSepKwMax] (separable) and for the direct kernels' 3, 5, 7
 #define OF2D_SEP_WIDTHS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(15)
+#define OF2D_DIRECT_WIDTHS(X) X(3) X(5) X(7)
 static_assert(kSepKwMax == 15, "OF2D_SEP_WIDTHS lists the odd widths up to kSepKwMax");
+
+// The one width dispatch of the launchers: f(KW, SEP) as integral constants.
+// Separable (a.gs; the caller checked demons_separable_ok): the width itself.
+// Direct: a compile-time width only where it is compiled in AND the interior
+// weight sum is float 1 (convR then keeps the accumulator); every other table
+// takes KW = 0, the runtime-width kernel, which divides (the bits of either
+// direct kernel).
+template <class F>
+void dispatch_width(const ConvArgs &a, F &&f) {
+    if (a.gs) {
+        switch (a.kw) {
+#define X(W) case W: return f(std::integral_constant<int, W>{}, std::true_type{});
+            OF2D_SEP_WIDTHS(X)
+#undef X
+            default: throw std::logic_error("demons: no separable kernel of this width");
+        }
+    }
+    if ((float)a.wfull == 1.0f) {
+        switch (a.kw) {
+#define X(W) case W: return f(std::integral_constant<int, W>{}, std::false_type{});
+            OF2D_DIRECT_WIDTHS(X)
+#undef X
+            default: break;
+        }
+    }
+    return f(std::integral_constant<int, 0>{}, std::false_type{});
+}
+
+ConvArgs conv_args(const float *kf, const double *kd, int kw, double wfull, const float *gs,
+                   int dimx) {
+    const int c = (kw - 1) / 2;
+    return ConvArgs{kf, kd, kw, c, c, wfull, gs && demons_separable_ok(kw, dimx) ? gs : nullptr};
+}
 
 // smooth_compose over `gridx` block columns: tiles [0, ntl) and the last
 // gridx - ntl tiles of the gxt-tile row
@@ -882,26 +896,11 @@ void smooth_compose_tiles(const float2 *corr, const float2 *u, float2 *out, int 
                           int P, const ConvArgs &a, int mode, int gridx, int ntl, int gxt,
                           hipStream_t st) {
     const dim3 g(gridx, conv_grid(dimx, dimy).y);
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, g, dim3(64, kCThreadsY), conv_lds_bytes(a.cx, a.cy), st, corr, u,
-                           out, dimx, dimy, P, a, mode, ntl, gxt);
-    };
-    if (a.gs) {  // separable (the caller checked demons_separable_ok)
-        switch (a.kw) {
-#define X(W) case W: go(smooth_compose_kernel<W, kCr, true, true>); break;
-            OF2D_SEP_WIDTHS(X)
-#undef X
-            default: throw std::logic_error("smooth_compose: no separable kernel of this width");
-        }
-        OF2D_HIP(hipGetLastError());
-        return;
-    }
-    switch (a.kw) {
-        case 3: go(smooth_compose_kernel<3>); break;
-        case 5: go(smooth_compose_kernel<5>); break;
-        case 7: go(smooth_compose_kernel<7>); break;
-        default: go(smooth_compose_kernel<0>); break;
-    }
+    dispatch_width(a, [&](auto W, auto S) {
+        hipLaunchKernelGGL((smooth_compose_kernel<decltype(W)::value, kCr, true, decltype(S)::value>),
+                           g, dim3(64, kCThreadsY), conv_lds_bytes(a.cx, a.cy), st, corr, u, out,
+                           dimx, dimy, P, a, mode, ntl, gxt);
+    });
     OF2D_HIP(hipGetLastError());
 }
 }  // namespace
@@ -909,12 +908,10 @@ void smooth_compose_tiles(const float2 *corr, const float2 *u, float2 *out, int 
 int launch_smooth_compose(const float2 *corr, const float2 *u, float2 *out, int dimx, int dimy,
                           int P, const float *kf, const double *kd, int kw, double wfull,
                           int mode, hipStream_t st, const float *gs) {
-    const int c = (kw - 1) / 2;
-    const bool sep = gs && demons_separable_ok(kw, dimx);
-    const ConvArgs a{kf, kd, kw, c, c, wfull, sep ? gs : nullptr};
+    const ConvArgs a = conv_args(kf, kd, kw, wfull, gs, dimx);
     const int gx = conv_grid(dimx, dimy).x;
     smooth_compose_tiles(corr, u, out, dimx, dimy, P, a, mode, gx, gx, gx, st);
-    return sep;
+    return a.gs != nullptr;
 }
 
 int launch_demons_update(const float *Iref, const float *Imov, const float2 *u, float2 *corr,
@@ -922,99 +919,62 @@ int launch_demons_update(const float *Iref, const float *Imov, const float2 *u, 
                          float sigma_xsq, const float *kf, const double *kd, int kw,
                          double wfull, int mode, unsigned *status, hipStream_t st,
                          const float *gs) {
-    const int c = (kw - 1) / 2;
-    const bool sep = gs && demons_separable_ok(kw, dimx);
-    const ConvArgs a{kf, kd, kw, c, c, wfull, sep ? gs : nullptr};
+    const ConvArgs a = conv_args(kf, kd, kw, wfull, gs, dimx);
     const int gx = (dimx + kCx - 1) / kCx;
     constexpr int TX = OF2D_DEMONS_TX, TY = OF2D_DEMONS_TY;
     // the fused kernel takes every tile, the x-edge ones included, when its
-    // width is compiled in (direct: 3, 5, 7; separable: every width it has)
-    // and no tile wraps more than once: the tile narrower than half the image
-    if (!(sep || kw == 3 || kw == 5 || kw == 7) || dimx < 2 * kCx || dimx < 2 * TX) {
+    // width is compiled in (dispatch_width: KW > 0) and no tile wraps more
+    // than once: the tile narrower than half the image
+    bool fused = false;
+    if (dimx >= 2 * kCx && dimx >= 2 * TX)
+        dispatch_width(a, [&](auto W, auto S) {
+            constexpr int KW = decltype(W)::value;
+            constexpr bool SEP = decltype(S)::value;
+            if constexpr (KW > 0) {
+                float rsx = 0.0f;
+                const bool fast = pow2_reciprocal(sigma_xsq, &rsx);
+                const dim3 g((dimx + TX - 1) / TX, (dimy + TY * kCr - 1) / (TY * kCr));
+                auto go = [&](auto kern) {
+                    hipLaunchKernelGGL(kern, g, dim3(TX, TY), 0, st, Iref, Imov, u, out, dimx,
+                                       dimy, P, sigma_isq, fast ? rsx : sigma_xsq, a, mode, status,
+                                       0);
+                };
+                if (fast)
+                    go(demons_fused_kernel<KW, kCr, true, TX, TY, SEP>);
+                else
+                    go(demons_fused_kernel<KW, kCr, false, TX, TY, SEP>);
+                fused = true;
+            }
+        });
+    if (fused) {
+        OF2D_HIP(hipGetLastError());
+    } else {
         launch_demons_force(Iref, Imov, u, corr, dimx, dimy, P, sigma_isq, sigma_xsq, status, st);
         smooth_compose_tiles(corr, u, out, dimx, dimy, P, a, mode, gx, gx, gx, st);
-        return sep;
     }
-    float rsx = 0.0f;
-    // the separable kernels never divide by the weight sum
-    const bool fast = (sep || (float)wfull == 1.0f) && pow2_reciprocal(sigma_xsq, &rsx);
-    const dim3 g((dimx + TX - 1) / TX, (dimy + TY * kCr - 1) / (TY * kCr));
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, g, dim3(TX, TY), 0, st, Iref, Imov, u, out, dimx, dimy, P,
-                           sigma_isq, fast ? rsx : sigma_xsq, a, mode, status, 0);
-    };
-    if (sep) {
-        switch (kw * 2 + fast) {
-#define X(W)                                                                    \
-    case 2 * W: go(demons_fused_kernel<W, kCr, false, TX, TY, true>); break;    \
-    case 2 * W + 1: go(demons_fused_kernel<W, kCr, true, TX, TY, true>); break;
-            OF2D_SEP_WIDTHS(X)
-#undef X
-            default: throw std::logic_error("demons_update: no separable kernel of this width");
-        }
-        OF2D_HIP(hipGetLastError());
-        return 1;
-    }
-    switch (kw * 2 + fast) {
-        case 6: go(demons_fused_kernel<3, kCr, false, TX, TY>); break;
-        case 7: go(demons_fused_kernel<3, kCr, true, TX, TY>); break;
-        case 10: go(demons_fused_kernel<5, kCr, false, TX, TY>); break;
-        case 11: go(demons_fused_kernel<5, kCr, true, TX, TY>); break;
-        case 15: go(demons_fused_kernel<7, kCr, true, TX, TY>); break;
-        default: go(demons_fused_kernel<7, kCr, false, TX, TY>); break;
-    }
-    OF2D_HIP(hipGetLastError());
-    return 0;
+    return a.gs != nullptr;
 }
 
 int launch_smooth_norm(const float2 *umid, const float2 *prev, float2 *out, int dimx, int dimy,
                        int P, const float *kf, const double *kd, int kw, double wfull,
                        double *partial, hipStream_t st, const float *gs) {
-    const int c = (kw - 1) / 2;
-    const bool sep = gs && demons_separable_ok(kw, dimx);
-    ConvArgs a{kf, kd, kw, c, c, wfull, sep ? gs : nullptr};
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, conv_grid(dimx, dimy), dim3(64, kCThreadsY),
-                           conv_lds_bytes(c, c), st, umid, prev, out, dimx, dimy, P, a, partial);
-    };
-    if (sep) {
-        switch (partial ? kw : -kw) {
-#define X(W)                                                                      \
-    case W: go(smooth_norm_kernel<W, kCr, true, false, true, true>); break;       \
-    case -W: go(smooth_norm_kernel<W, kCr, true, false, false, true>); break;
-            OF2D_SEP_WIDTHS(X)
-#undef X
-            default: throw std::logic_error("smooth_norm: no separable kernel of this width");
-        }
-        OF2D_HIP(hipGetLastError());
-        return 1;
-    }
-    const bool w1 = (float)wfull == 1.0f;
-    // no partials wanted (the Logger's float sums come from seqnorm): no norms
-    if (!partial) {
-        switch (w1 ? kw : -kw) {
-            case 3: go(smooth_norm_kernel<3, kCr, true, true, false>); break;
-            case -3: go(smooth_norm_kernel<3, kCr, true, false, false>); break;
-            case 5: go(smooth_norm_kernel<5, kCr, true, true, false>); break;
-            case -5: go(smooth_norm_kernel<5, kCr, true, false, false>); break;
-            case 7: go(smooth_norm_kernel<7, kCr, true, true, false>); break;
-            case -7: go(smooth_norm_kernel<7, kCr, true, false, false>); break;
-            default: go(smooth_norm_kernel<0, kCr, true, false, false>); break;
-        }
-        OF2D_HIP(hipGetLastError());
-        return 0;
-    }
-    switch (w1 ? kw : -kw) {
-        case 3: go(smooth_norm_kernel<3, kCr, true, true>); break;
-        case -3: go(smooth_norm_kernel<3>); break;
-        case 5: go(smooth_norm_kernel<5, kCr, true, true>); break;
-        case -5: go(smooth_norm_kernel<5>); break;
-        case 7: go(smooth_norm_kernel<7, kCr, true, true>); break;
-        case -7: go(smooth_norm_kernel<7>); break;
-        default: go(smooth_norm_kernel<0>); break;
-    }
+    const ConvArgs a = conv_args(kf, kd, kw, wfull, gs, dimx);
+    dispatch_width(a, [&](auto W, auto S) {
+        constexpr int KW = decltype(W)::value;
+        constexpr bool SEP = decltype(S)::value;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, conv_grid(dimx, dimy), dim3(64, kCThreadsY),
+                               conv_lds_bytes(a.cx, a.cy), st, umid, prev, out, dimx, dimy, P, a,
+                               partial);
+        };
+        // no partials wanted (the Logger's float sums come from seqnorm): no norms
+        if (partial)
+            go(smooth_norm_kernel<KW, kCr, true, true, SEP>);
+        else
+            go(smooth_norm_kernel<KW, kCr, true, false, SEP>);
+    });
     OF2D_HIP(hipGetLastError());
-    return 0;
+    return a.gs != nullptr;
 }
 
 // ------------------------------------------------------------------ exp (diffeomorphic)
@@ -1033,18 +993,8 @@ __global__ __launch_bounds__(256) void maxabs_partial_kernel(const float2 *__res
         const float s = (float)(y * y + y * y);
         m = (m < s) ? s : m;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(m, off);
-        m = (m < o) ? o : m;
-    }
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float r = red[0];
-        for (int w = 1; w < 4; w++) r = (r < red[w]) ? red[w] : r;
-        part[blockIdx.x] = r;
-    }
+    m = block_max<4>(m, threadIdx.x >> 6, threadIdx.x & 63);
+    if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
 __global__ void exp_prepare_kernel(const float *__restrict__ part, int nparts,

@@ -62,7 +62,7 @@ void launch_motion_to_planar(const float2 *m, int P, int dimx, int dimy, double 
 
 // ------------------------------------------------------------ pyramid
 // Field<float>::downSample (src/Field.tpp:75-143): box average over the
-// integer factor dimin/dimout, ii outer / jj inner, taps past the end skipped.
+// integer factor dimin/dimout, ii outer / jj inner.
 __global__ void downsample_image_kernel(const float *__restrict__ in, int dxi, int dyi, int Pi,
                                         float *__restrict__ out, int dxo, int dyo, int Po) {
     OF2D_PX_PROLOGUE(dxo, dyo)
@@ -71,8 +71,9 @@ __global__ void downsample_image_kernel(const float *__restrict__ in, int dxi, i
     int p = 0;
     for (int ii = 0; ii < fx; ii++)
         for (int jj = 0; jj < fy; jj++) {
+            // (no tap lies past the end: j * fy + jj <= dyo * fy - 1 <= dyi - 1
+            // for fy = dyi / dyo, so the reference's k >= sizein skip never fires)
             const int y = j * fy + jj;
-            if (y >= dyi) continue;  // linear index >= sizein
             val += in[(long)y * Pi + i * fx + ii];
             p++;
         }
@@ -100,8 +101,9 @@ __global__ void downsample_motion_kernel(const float2 *__restrict__ in, int dxi,
     int p = 0;
     for (int ii = 0; ii < fx; ii++)
         for (int jj = 0; jj < fy; jj++) {
+            // (no tap lies past the end: j * fy + jj <= dyo * fy - 1 <= dyi - 1
+            // for fy = dyi / dyo, so the reference's k >= sizein skip never fires)
             const int y = j * fy + jj;
-            if (y >= dyi) continue;
             const float2 a = in[(long)y * Pi + i * fx + ii];
             vx = vx + a.x;
             vy = vy + a.y;

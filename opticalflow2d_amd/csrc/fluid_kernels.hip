@@ -79,71 +79,6 @@ __device__ __forceinline__ Grad2 motion_gradients(const float2 *__restrict__ u, 
     return d;
 }
 
-// max / min over a 64 x 4 block (result valid in thread (0,0)); the order of a
-// max or min does not change its value
-__device__ __forceinline__ float block_max(float m) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(m, off);
-        m = (m < o) ? o : m;
-    }
-    __shared__ float red[4];
-    if (threadIdx.x == 0) red[threadIdx.y] = m;
-    __syncthreads();
-    for (int w = 1; w < 4; w++) m = (m < red[w]) ? red[w] : m;
-    return m;
-}
-__device__ __forceinline__ float block_min(float m) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(m, off);
-        m = (o < m) ? o : m;
-    }
-    __shared__ float red[4];
-    if (threadIdx.x == 0) red[threadIdx.y] = m;
-    __syncthreads();
-    for (int w = 1; w < 4; w++) m = (red[w] < m) ? red[w] : m;
-    return m;
-}
-// fp64 Logger partials of a 64 x 4 block, fixed order, written by thread (0,0)
-__device__ __forceinline__ void block_sum2(double sd, double sp, double *__restrict__ partial) {
-    for (int off = 32; off > 0; off >>= 1) {
-        sd += __shfl_down(sd, off);
-        sp += __shfl_down(sp, off);
-    }
-    __shared__ double red[2][4];
-    if (threadIdx.x == 0) {
-        red[0][threadIdx.y] = sd;
-        red[1][threadIdx.y] = sp;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
-        partial[2 * blk] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        partial[2 * blk + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-    }
-}
-// max / min over a 1024-thread block (result valid in thread 0)
-__device__ __forceinline__ float wide_max(float m) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(m, off);
-        m = (m < o) ? o : m;
-    }
-    __shared__ float red[16];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    for (int w = 1; w < 16; w++) m = (m < red[w]) ? red[w] : m;
-    return m;
-}
-__device__ __forceinline__ float wide_min(float m) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_down(m, off);
-        m = (o < m) ? o : m;
-    }
-    __shared__ float red[16];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    for (int w = 1; w < 16; w++) m = (red[w] < m) ? red[w] : m;
-    return m;
-}
 }  // namespace
 
 // The sweep works on the array vb of the field being relaxed (v) and its
@@ -435,10 +370,7 @@ __device__ __attribute__((noinline)) void sor_increment_worker(const float4 *__r
                 m = (m < qq) ? qq : m;
             }
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            const float o = __shfl_down(m, off);
-            m = (m < o) ? o : m;
-        }
+        m = wave_max(m);
         if (lane == 0) w.part[(long)by * ((dimx + 63) / 64) + bx] = m;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // vt is rewritten by the next tile
     }
@@ -905,7 +837,7 @@ __global__ __launch_bounds__(256) void increment_kernel(const float2 *__restrict
         const float q = (float)(y * y + y * y);
         m = (m < q) ? q : m;
     }
-    m = block_max(m);
+    m = block_max<4>(m, threadIdx.y, threadIdx.x);
     if (threadIdx.x == 0 && threadIdx.y == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = m;
 }
 
@@ -915,7 +847,7 @@ __global__ __launch_bounds__(1024) void timestep_kernel(const float *__restrict_
     if (fluid_stopped(ctl)) return;
     float m = 0.0f;
     for (int k = threadIdx.x; k < n; k += 1024) m = (m < part[k]) ? part[k] : m;
-    m = wide_max(m);
+    m = block_max<16>(m, threadIdx.x >> 6, threadIdx.x & 63);
     if (threadIdx.x == 0) {
         const float maxabs = sqrtf(m);
         const float dumax = 0.65f;  // OpticalFlowFluid.h:32
@@ -1085,11 +1017,7 @@ __global__ __launch_bounds__(256) void fluid_step_kernel(
         const float2 m = un[r][c];
         const float2 pv = pvk[k];
         uo[idx] = m;
-        // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
-        const double ex = (double)(m.x - pv.x), ey = (double)(m.y - pv.y);
-        const double qx = (double)pv.x, qy = (double)pv.y;
-        sd += sqrt(ex * ex + ey * ey);
-        sp += sqrt(qx * qx + qy * qy);
+        logger_add(m, pv, sd, sp);
         // motion_gradients of the new u (gradients.h:9-32)
         float2 dx, dy;
         if (i == 0) {
@@ -1123,8 +1051,8 @@ __global__ __launch_bounds__(256) void fluid_step_kernel(
             H[kSorPadRows + j] = v4u{__float_as_uint(x.x), __float_as_uint(x.y), epoch, epoch};
         }
     }
-    block_sum2(sd, sp, lpart);
-    jm = block_min(jm);
+    block_logger_partial(sd, sp, lpart);
+    jm = block_min<4>(jm, threadIdx.y, threadIdx.x);
     if (threadIdx.x == 0 && threadIdx.y == 0) jpart[(long)blockIdx.y * gridDim.x + blockIdx.x] = jm;
     // 3. vb's b <- force along the skewed rows
     skew_tile_set_b(vb, i0, j0, dimx, dimy, P, [&](int ii, int jj) { return fo[jj][ii]; });
@@ -1145,46 +1073,40 @@ void launch_fluid_step(const float2 *u, const float2 *R, float2 *uo, const float
     OF2D_HIP(hipGetLastError());
 }
 
-// one 1024-thread block: the Logger sums in reduce_partials_kernel's order
-// (strided per-thread sums, wave trees, the 16 waves in order), the Jacobian
-// minimum as min_final_kernel, then the report to host memory
-__global__ __launch_bounds__(1024) void fluid_report_kernel(const double *__restrict__ p, int nb,
-                                                            const float *__restrict__ jpart,
-                                                            float *__restrict__ scal,
-                                                            const unsigned *__restrict__ status,
-                                                            FluidReport *__restrict__ rep) {
-    double a = 0.0, b = 0.0;
+// The common part of the two report kernels, by one 1024-thread block: the
+// Logger sums in the order of partial_pairs_sum (of2d_device.h), the minimum
+// of the nb Jacobian partials (into scal[2]) and the report's fields up to
+// status, written by thread 0, which also gets the sums (s) and the minimum
+// (returned).  Includes the block's barriers.
+__device__ __forceinline__ float fluid_report_common(const double *__restrict__ p, int nb,
+                                                     const float *__restrict__ jpart,
+                                                     float *__restrict__ scal,
+                                                     const unsigned *__restrict__ status,
+                                                     FluidReport *__restrict__ rep,
+                                                     double (&s)[2]) {
+    partial_pairs_sum(p, nb, s);
     float m = __builtin_inff();
-    for (int i = threadIdx.x; i < nb; i += 1024) {
-        a += p[2 * i];
-        b += p[2 * i + 1];
-        m = (jpart[i] < m) ? jpart[i] : m;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off);
-        b += __shfl_down(b, off);
-    }
-    __shared__ double red[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = a;
-        red[1][wave] = b;
-    }
-    m = wide_min(m);  // (synchronises the block)
+    for (int i = threadIdx.x; i < nb; i += 1024) m = (jpart[i] < m) ? jpart[i] : m;
+    m = block_min<16>(m, threadIdx.x >> 6, threadIdx.x & 63);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++) {
-            a += red[0][w];
-            b += red[1][w];
-        }
         scal[2] = m;
-        rep->sums[0] = a;
-        rep->sums[1] = b;
+        rep->sums[0] = s[0];
+        rep->sums[1] = s[1];
         rep->maxabs = scal[0];
         rep->dt = scal[1];
         rep->jmin = m;
         rep->status = *status;
     }
+    return m;
+}
+
+__global__ __launch_bounds__(1024) void fluid_report_kernel(const double *__restrict__ p, int nb,
+                                                            const float *__restrict__ jpart,
+                                                            float *__restrict__ scal,
+                                                            const unsigned *__restrict__ status,
+                                                            FluidReport *__restrict__ rep) {
+    double s[2];
+    fluid_report_common(p, nb, jpart, scal, status, rep, s);
 }
 
 void launch_fluid_report(const double *lpart, int nb, const float *jpart, float *scal,
@@ -1194,7 +1116,7 @@ void launch_fluid_report(const double *lpart, int nb, const float *jpart, float 
     OF2D_HIP(hipGetLastError());
 }
 
-// fluid_report_kernel's reductions and report, then the iteration's decisions
+// fluid_report_common's reductions and report, then the iteration's decisions
 // as the host loop took them (ImageRegistrationFluid.cpp:99-124 with
 // Logger::update_error, Logger.cpp:32-51): err = diffnorm / prevnorm in float
 // (Registration's logger_error) from the exact float sums or the fp64 sums;
@@ -1207,34 +1129,12 @@ __global__ __launch_bounds__(1024) void fluid_report_decide_kernel(
     float *__restrict__ scal, const float *__restrict__ seq, float npx, int fixed,
     FluidReport *__restrict__ rep, FluidCtl ctl) {
     if (fluid_stopped(ctl)) return;
-    double a = 0.0, b = 0.0;
-    float m = __builtin_inff();
-    for (int i = threadIdx.x; i < nb; i += 1024) {
-        a += p[2 * i];
-        b += p[2 * i + 1];
-        m = (jpart[i] < m) ? jpart[i] : m;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off);
-        b += __shfl_down(b, off);
-    }
-    __shared__ double red[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = a;
-        red[1][wave] = b;
-    }
-    m = wide_min(m);  // (synchronises the block)
+    double s[2];
+    const float m = fluid_report_common(p, nb, jpart, scal, ctl.w, rep, s);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-        scal[2] = m;
         // Logger::update_error's two norms as floats (logger_error: the fp64
         // sums rounded to float, or the reference's float running sums)
-        const float sd = seq ? seq[0] : (float)a, sp = seq ? seq[1] : (float)b;
+        const float sd = seq ? seq[0] : (float)s[0], sp = seq ? seq[1] : (float)s[1];
         const float prevnorm = sp / npx, diffnorm = sd / npx;
         const float err = prevnorm == 0.0f ? 0.0f : diffnorm / prevnorm;
         const bool brk = !fixed && err < 0.001f && ctl.it > 1;
@@ -1243,12 +1143,6 @@ __global__ __launch_bounds__(1024) void fluid_report_decide_kernel(
         if (brk) atomicMin(reinterpret_cast<int *>(w + kStopWord), ctl.it);
         w[kFluidRegridWord] = regrid ? 1u : 0u;
         if (regrid) w[kFluidMcurWord] ^= 1u;
-        rep->sums[0] = a;
-        rep->sums[1] = b;
-        rep->maxabs = scal[0];
-        rep->dt = scal[1];
-        rep->jmin = m;
-        rep->status = w[0];
         rep->seq[0] = sd;
         rep->seq[1] = sp;
         rep->err = err;
@@ -1287,14 +1181,10 @@ __global__ __launch_bounds__(256) void logger_kernel(const float4 *__restrict__ 
         const long idx = (long)j * P + i;
         const float2 m = vt[4 * k + threadIdx.y][threadIdx.x], pv = prev[idx];
         u[idx] = m;
-        // Motion::norm's magnitudes (Motion.cpp:42-47): fp64 squares and root
-        const double ex = (double)(m.x - pv.x), ey = (double)(m.y - pv.y);
-        const double qx = (double)pv.x, qy = (double)pv.y;
-        sd += sqrt(ex * ex + ey * ey);
-        sp += sqrt(qx * qx + qy * qy);
+        logger_add(m, pv, sd, sp);
         prev[idx] = m;
     }
-    block_sum2(sd, sp, partial);
+    block_logger_partial(sd, sp, partial);
 }
 void launch_logger(const float4 *vb, float2 *u, float2 *prev, int dimx, int dimy, int P,
                    double *partial, hipStream_t st) {

@@ -77,10 +77,13 @@ __device__ __forceinline__ float dpp_from_right(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xF, 0xF, true));
 }
 
-// |v| for the Logger sums: v_sqrt_f32 (within 1 ulp).  The norms only feed the
-// fp64 convergence sums, which already differ from the reference's sequential
-// fp32 sum in rounding (tests compare errors at a stated tolerance); the
-// motion itself never depends on them.
+// |v| for the Logger sums of the HS Jacobi kernels, the one exception to
+// logger_mag (of2d_device.h): float32 squares and v_sqrt_f32 (within 1 ulp), a
+// measured choice of the hot kernel, where two fp64 roots per pixel and
+// iteration would show.  The norms only feed the fp64 convergence sums, which
+// already differ from the reference's sequential fp32 sum in rounding (tests
+// compare errors at a stated tolerance); the motion itself never depends on
+// them.  The block reductions below follow block_sums' order (of2d_device.h).
 __device__ __forceinline__ double norm_d(float x, float y) {
     return (double)__builtin_amdgcn_sqrtf(x * x + y * y);
 }

@@ -144,37 +144,16 @@ void launch_hs_jacobi(const float2 *u_old, float2 *u_new, const float2 *dI, cons
     OF2D_HIP(hipGetLastError());
 }
 
-// partial: [C][nblocks][2]; one 1024-thread block per iteration, fixed
-// summation order (strided per-thread sums, wave trees, then the 16 waves in
-// order).
+// partial: [C][nblocks][2]; one 1024-thread block per iteration, in the fixed
+// order of partial_pairs_sum (of2d_device.h).
 __global__ __launch_bounds__(1024) void reduce_partials_kernel(const double *__restrict__ partial,
                                                                int stride, int nblocks,
                                                                double *__restrict__ sums) {
-    const double *p = partial + (size_t)blockIdx.x * stride * 2;
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 1024) {
-        a += p[2 * i];
-        b += p[2 * i + 1];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off);
-        b += __shfl_down(b, off);
-    }
-    __shared__ double red[2][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = a;
-        red[1][wave] = b;
-    }
-    __syncthreads();
+    double s[2];
+    partial_pairs_sum(partial + (size_t)blockIdx.x * stride * 2, nblocks, s);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-        sums[2 * blockIdx.x] = a;
-        sums[2 * blockIdx.x + 1] = b;
+        sums[2 * blockIdx.x] = s[0];
+        sums[2 * blockIdx.x + 1] = s[1];
     }
 }
 

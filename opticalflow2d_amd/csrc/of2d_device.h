@@ -269,6 +269,128 @@ struct PartialRuns {
     void reduce(const double *partial, int stride, double *sums, hipStream_t st) const;
 };
 
+// ---------------------------------------------------------------- Logger sums
+// The one definition of the fp64 Logger sums' arithmetic and of the fixed
+// order in which every kernel adds them (DESIGN.md "fixed order"; the
+// multi-rank path is bit-identical to one GPU because of it;
+// tests/test_gpu_logger_partials.py restates the order in numpy).
+//
+// Motion::norm's magnitude (src/Motion.cpp:42-47): the float components
+// widened, squared and added in double (-ffp-contract=off: no fused
+// multiply-add), then the correctly rounded double root.  Every kernel's
+// Logger terms are these; the one exception is the HS Jacobi kernels' norm_d
+// (hs_jacobi_impl.h), a float32 root by measurement.
+__device__ __forceinline__ double logger_mag(float x, float y) {
+    const double a = x, b = y;
+    return sqrt(a * a + b * b);
+}
+// a pixel's two terms (Logger.cpp:34-42): |cur - prev| of the float32
+// difference onto sd, |prev| onto sp
+__device__ __forceinline__ void logger_add(float2 cur, float2 prev, double &sd, double &sp) {
+    sd += logger_mag(cur.x - prev.x, cur.y - prev.y);
+    sp += logger_mag(prev.x, prev.y);
+}
+// Wave trees: lane i takes lane i + off for off = 32 ... 1; the result is in
+// lane 0 (the other lanes hold partial trees)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const T o = __shfl_down(v, off);
+        v = (o < v) ? o : v;
+    }
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const T o = __shfl_down(v, off);
+        v = (v < o) ? o : v;
+    }
+    return v;
+}
+// The N sums of a block of WAVES waves (thread = wave * 64 + lane): wave
+// trees, lane 0 of each wave to LDS, one barrier, then the block's first
+// thread adds waves 0 ... WAVES-1 in that order into its v[] (the other
+// threads' v[] hold partial trees).  Its sums start from 0.0 + wave 0, the
+// same bits as wave 0 itself for these sums (non-negative or NaN).  One call
+// per instantiation and kernel: the LDS array is the instantiation's.  The
+// tails of the three HS Jacobi kernels (hs_jacobi_impl.h) keep their own
+// copies of exactly this order, with the status word's atomicOr before the
+// barrier: moving them here changed the hot kernels' code size.
+template <int N, int WAVES>
+__device__ __forceinline__ void block_sums(double (&v)[N], int wave, int lane) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int q = 0; q < N; q++) v[q] += __shfl_down(v[q], off);
+    __shared__ double red[N][WAVES];
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < N; q++) red[q][wave] = v[q];
+    }
+    __syncthreads();
+    if (wave == 0 && lane == 0) {
+#pragma unroll
+        for (int q = 0; q < N; q++) v[q] = 0.0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w)
+#pragma unroll
+            for (int q = 0; q < N; q++) v[q] += red[q][w];
+    }
+}
+// The Logger pair of a 64 x 4 block -> partial[2 blk], partial[2 blk + 1],
+// blk = blockIdx.y * gridDim.x + blockIdx.x
+__device__ __forceinline__ void block_logger_partial(double sd, double sp,
+                                                     double *__restrict__ partial) {
+    double v[2] = {sd, sp};
+    block_sums<2, 4>(v, threadIdx.y, threadIdx.x);
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
+        partial[2 * blk] = v[0];
+        partial[2 * blk + 1] = v[1];
+    }
+}
+// nb (diff, prev) partial pairs by one 1024-thread block: thread t adds pairs
+// t, t + 1024, ... in order, then block_sums over the 16 waves; the sums are
+// thread 0's s[]
+__device__ __forceinline__ void partial_pairs_sum(const double *__restrict__ p, int nb,
+                                                  double (&s)[2]) {
+    s[0] = s[1] = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 1024) {
+        s[0] += p[2 * i];
+        s[1] += p[2 * i + 1];
+    }
+    block_sums<2, 16>(s, threadIdx.x >> 6, threadIdx.x & 63);
+}
+// min / max over a block of WAVES waves, valid in its first thread; includes
+// a barrier.  The order of a min or max does not change its value.
+template <int WAVES>
+__device__ __forceinline__ float block_min(float m, int wave, int lane) {
+    m = wave_min(m);
+    __shared__ float red[WAVES];
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    for (int w = 1; w < WAVES; w++) m = (red[w] < m) ? red[w] : m;
+    return m;
+}
+template <int WAVES>
+__device__ __forceinline__ float block_max(float m, int wave, int lane) {
+    m = wave_max(m);
+    __shared__ float red[WAVES];
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    for (int w = 1; w < WAVES; w++) m = (m < red[w]) ? red[w] : m;
+    return m;
+}
+
 // ---------------------------------------------------------------- Logger norms
 // The reference's Motion::norm (src/Motion.cpp:42-49) bit for bit: the float
 // running sum S <- (float)((double)S + sqrt((double)x^2 + (double)y^2)) over
@@ -498,7 +620,8 @@ bool demons_separable_ok(int kw, int dimx);
 // One correction update (DemonsThirions.cpp:20-38): force, sigma_fluid
 // smoothing and the motion update (mode as launch_smooth_compose) -> out.
 // One fused launch over every tile (demons_fused_kernel; the x-edge tiles hold
-// the wrapped tap pixels) for kw 3 / 5 / 7 (separable: every width it takes)
+// the wrapped tap pixels) for kw 3 / 5 / 7 with (float)wfull == 1 (separable:
+// every width it takes)
 // and dimx >= 128; otherwise the unfused kernels through corr (scratch).
 // gs (this and the two launches below): nullptr for the direct convolution;
 // otherwise the kernel's (float) row marginals then column marginals (kw

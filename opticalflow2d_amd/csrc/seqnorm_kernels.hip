@@ -127,12 +127,6 @@ __device__ __forceinline__ unsigned sn_sat(unsigned a, unsigned b) {
     const unsigned s = a + b;  // a, b <= kSnSat
     return s < kSnSat ? s : kSnSat;
 }
-// Motion::norm's magnitude: float components squared and added in double
-// (-ffp-contract=off: no fused multiply-add), double sqrt (correctly rounded)
-__device__ __forceinline__ double sn_mag(float x, float y) {
-    const double a = x, b = y;
-    return sqrt(a * a + b * b);
-}
 __device__ __forceinline__ double sn_scale(int e) {
     return __longlong_as_double((long long)(52 - e + 1023) << 52);
 }
@@ -516,7 +510,7 @@ __device__ __forceinline__ void sn_wave_pass(const SnJobs &J, unsigned N, int di
                         // keeps the fp64 work inside this rare branch.
                         float xx = x, yy = y;
                         asm volatile("" : "+v"(xx), "+v"(yy));
-                        const double dd = sn_mag(xx, yy);
+                        const double dd = logger_mag(xx, yy);
                         dv = v.ok ? dv : (float)dd;
                         const int e0 = hdr_elo(hd[i][n]);
                         if (NC > 0)
@@ -621,7 +615,7 @@ __device__ void sn_block_fix(const SnJobs &J, int j, unsigned N, int dimx, int P
 #pragma unroll
             for (int c = 0; c < kSnCand; c++) unc |= !sn_incr_est(v, sc[n][c], m[c]);
             if (sn_ballot(unc)) {
-                const double dd = sn_mag(x, y);
+                const double dd = logger_mag(x, y);
 #pragma unroll
                 for (int c = 0; c < kSnCand; c++) {
                     bool bad = false;
@@ -1058,7 +1052,7 @@ __device__ __forceinline__ unsigned long long lanes_from(int k) {
 // running sum S, term by term where the binade changes.
 __device__ float sn_raw_segment(SnSegTerms tv, float S) {
     const int lane = threadIdx.x & 63;
-    const double dv = sn_mag(tv.v.x, tv.v.y);
+    const double dv = logger_mag(tv.v.x, tv.v.y);
     int pos = 0;
     while (pos < 64) {
         const int e = sn_region(S);
@@ -1148,7 +1142,7 @@ __device__ void sn_help_part(const float2 *__restrict__ cur, const float2 *__res
         unc |= !sn_incr_est(v, sc1, m1);
         bool bad0 = false, bad1 = false;
         if (sn_ballot(unc)) {
-            const double dd = sn_mag(vx, vy);
+            const double dd = logger_mag(vx, vy);
             m0 = sn_incr(dd, sn_scale(e), bad0);
             m1 = top ? 0u : sn_incr(dd, sn_scale(e + 1), bad1);
         }
