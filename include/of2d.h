@@ -540,6 +540,66 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * field.  A timing entry for tools/analysis_bench.py, not a result. */
 int of2d_analysis_time_kernels(int dimx, int dimy, int nlaunch, double *us);
 
+/* ---- batched Horn-Schunck: many small pairs of one size in one call ----
+ * nbatch independent Diffusion registrations with the same parameters.  Each
+ * pair is run by one workgroup with the whole iteration loop inside the
+ * kernel; the passes around the loop (pyramid, warp, gradients, composition)
+ * take the pair as a grid dimension, so the kernel launches of one estimate do
+ * not depend on nbatch.  The pyramid and refine sequence, the per-pixel
+ * arithmetic and therefore the motion of every pair are those of of2d_create /
+ * of2d_estimate on that pair alone (a new context's first estimate: every
+ * of2d_batch_estimate starts from a zero motion field), bit for bit when the
+ * pair runs the same number of iterations.
+ *
+ * Convergence (the default; "fixed_iters" 0): each pair stops on its own
+ * iteration by the reference's test (error < 0.001f after iteration > 1).  The
+ * error is formed with the Logger's float arithmetic from fp64 sums added in a
+ * fixed order: the semantics of of2d_set_option "logger_fp64" = 1, not the
+ * reference's sequential float sum; two calls give the same bits.  With
+ * "fixed_iters" 1 every loop runs niter iterations and no error is recorded.
+ *
+ * A zero denominator on an image pixel (the reference's "Divide by zero
+ * exception") is per pair: of2d_batch_estimate still returns OF2D_OK,
+ * of2d_batch_status reports OF2D_ERR_RUNTIME for that pair, its motion is left
+ * zero and of2d_batch_last_error names the first such pair.
+ *
+ * of2d_batch_create refuses with OF2D_ERR_INVALID_ARGUMENT and a message
+ * (of2d_batch_last_error(NULL)), before any device work: nbatch < 1 or > 65535,
+ * a reg other than OF2D_REG_DIFFUSION, nparams != 1 (the reference's message),
+ * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
+ * Options: "fixed_iters", "device" (before first use); an unknown key is
+ * refused.  Splitting one pair over several workgroups is not offered: with
+ * fewer pairs than compute units most of the device idles. */
+typedef struct of2d_batch of2d_batch;
+#define OF2D_BATCH_MAXPX (512 * 512)
+int of2d_batch_create(of2d_batch **out, int nbatch, int dimx, int dimy, const int *niter,
+                      int nscales, int reg, const float *regparams, unsigned nparams,
+                      int nrefine);
+int of2d_batch_set_option(of2d_batch *b, const char *key, double value);
+/* Iref: nbatch images, or ONE image every pair is registered to (shared_ref =
+ * 1); Imov: nbatch images; double [dimx*dimy] each, boundary layout */
+int of2d_batch_set_images(of2d_batch *b, const double *Iref, int shared_ref, const double *Imov);
+int of2d_batch_estimate(of2d_batch *b);
+/* nbatch x planar [dimx*dimy*2], as of2d_get_motion per pair */
+int of2d_batch_get_motion(of2d_batch *b, double *out);
+/* pair k's image (Imov: nbatch images) warped by pair k's motion */
+int of2d_batch_warp(of2d_batch *b, const double *Imov, double *out);
+/* out[nbatch]: OF2D_OK or OF2D_ERR_RUNTIME per pair of the last estimate */
+int of2d_batch_status(const of2d_batch *b, int *out);
+/* iterations run, [pair][loop] with the (nscales + 1) * nrefine loops in
+ * execution order; returns nbatch * loops */
+int of2d_batch_iterations(const of2d_batch *b, int *out, int cap);
+/* the errors of the pair's last loop (none with "fixed_iters"); returns their count */
+int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap);
+/* info = {kernel launches of the last estimate, loops per pair, levels, device
+ * time of the last estimate's loop kernels in microseconds, then per level from
+ * level 0: where the iterate lives (0: global memory), threads of a pair's
+ * workgroup}; returns the number of values */
+int of2d_batch_info(const of2d_batch *b, int *info, int n);
+int of2d_batch_destroy(of2d_batch *b);
+/* b == NULL: the message of the last refused of2d_batch_create of this thread */
+const char *of2d_batch_last_error(const of2d_batch *b);
+
 /* ---- library info ---- */
 const char *of2d_version(void);
 int of2d_device_count(int *count);

@@ -151,6 +151,19 @@ SIGNATURES = {
     "of2d_image_similarity": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f64p]),
     "of2d_quality": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
     "of2d_analysis_time_kernels": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
+    "of2d_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, _i32p,
+                                    C.c_int, C.c_int, _f32p, C.c_uint, C.c_int]),
+    "of2d_batch_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "of2d_batch_set_images": (C.c_int, [C.c_void_p, _f64p, C.c_int, _f64p]),
+    "of2d_batch_estimate": (C.c_int, [C.c_void_p]),
+    "of2d_batch_get_motion": (C.c_int, [C.c_void_p, _f64p]),
+    "of2d_batch_warp": (C.c_int, [C.c_void_p, _f64p, _f64p]),
+    "of2d_batch_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "of2d_batch_iterations": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
+    "of2d_batch_last_errors": (C.c_int, [C.c_void_p, C.c_int, _f32p, C.c_int]),
+    "of2d_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "of2d_batch_destroy": (C.c_int, [C.c_void_p]),
+    "of2d_batch_last_error": (C.c_char_p, [C.c_void_p]),
     "of2d_version": (C.c_char_p, []),
     "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }

@@ -1,0 +1,156 @@
+"""Batched Horn-Schunck: many small image pairs of one size in one call.
+
+:class:`BatchRegistration` is the object-style handle on ``of2d_batch_*``
+(include/of2d.h): ``nbatch`` independent Diffusion registrations with the same
+parameters, each run by one workgroup with the whole iteration loop inside the
+kernel.  Arrays follow :class:`ImageRegistration`'s convention with a leading
+pair axis: an image is ``[dimx, dimy]`` (x first), a stack of them
+``[nbatch, dimx, dimy]`` and the motion ``[nbatch, dimx, dimy, 2]``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+
+#: most pixels a batch image may have (include/of2d.h OF2D_BATCH_MAXPX)
+BATCH_MAXPX = 512 * 512
+
+
+class BatchRegistration:
+    """``nbatch`` Horn-Schunck registrations of ``dims = (dimx, dimy)`` images.
+
+    ``niter`` (nscales+1 values, finest level first), ``nscales``, ``alpha``
+    and ``nrefine`` are :class:`ImageRegistration`'s for Diffusion.  Keyword
+    options map to ``of2d_batch_set_option``: ``fixed_iters``, ``device``.
+    With convergence on, every pair stops on its own iteration; the errors are
+    those of ``logger_fp64=1`` (fp64 sums in a fixed order).
+    """
+
+    def __init__(self, nbatch: int, dims: Sequence[int], niter: Sequence[int], nscales: int,
+                 alpha: float, nrefine: int = 1, **options):
+        L = _lib.lib()
+        self.nbatch = int(nbatch)
+        self.dimx, self.dimy = int(dims[0]), int(dims[1])
+        self.nscales, self.nrefine = int(nscales), int(nrefine)
+        nit = np.ascontiguousarray(np.asarray(niter, dtype=np.int32).reshape(-1)[: max(nscales, 0) + 1])
+        if nit.size < nscales + 1:
+            raise ValueError("niter needs nscales+1 entries")
+        p = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32).reshape(-1))
+        self._h = None
+        h = C.c_void_p()
+        st = L.of2d_batch_create(C.byref(h), self.nbatch, self.dimx, self.dimy, nit,
+                                 self.nscales, 0, p if p.size else np.zeros(1, np.float32),
+                                 int(p.size), self.nrefine)
+        check(st, L.of2d_batch_last_error(None).decode())
+        self._h = h
+        self.loops = (self.nscales + 1) * max(self.nrefine, 0)
+        self._maxn = max(int(nit.max()), 1)  # a loop records at most niter errors
+        for k, v in options.items():
+            self.set_option(k, v)
+
+    def _chk(self, st):
+        check(st, _lib.lib().of2d_batch_last_error(self._h).decode())
+
+    def set_option(self, key: str, value: float) -> None:
+        self._chk(_lib.lib().of2d_batch_set_option(self._h, key.encode(), float(value)))
+
+    def _stack(self, a, name: str) -> np.ndarray:
+        """``[nbatch, dimx, dimy]`` -> the boundary layout, x fastest per image."""
+        a = np.asarray(a, dtype=np.float64)
+        want = (self.nbatch, self.dimx, self.dimy)
+        if a.shape != want:
+            raise ValueError(f"{name} is {a.shape}, expected {want}")
+        return np.ascontiguousarray(a.transpose(0, 2, 1)).reshape(-1)
+
+    def register(self, Iref, Imov) -> None:
+        """``Iref``: ``[dimx, dimy]`` (one reference shared by every pair) or
+        ``[nbatch, dimx, dimy]``; ``Imov``: ``[nbatch, dimx, dimy]``."""
+        r = np.asarray(Iref, dtype=np.float64)
+        shared = r.ndim == 2
+        if shared:
+            if r.shape != (self.dimx, self.dimy):
+                raise ValueError(f"Iref is {r.shape}, expected {(self.dimx, self.dimy)} or "
+                                 f"{(self.nbatch, self.dimx, self.dimy)}")
+            r = np.ascontiguousarray(r.T).reshape(-1)
+        else:
+            r = self._stack(r, "Iref")
+        m = self._stack(Imov, "Imov")
+        L = _lib.lib()
+        self._chk(L.of2d_batch_set_images(self._h, r, int(shared), m))
+        self._chk(L.of2d_batch_estimate(self._h))
+
+    def motion(self) -> np.ndarray:
+        out = np.zeros(self.nbatch * 2 * self.dimx * self.dimy, np.float64)
+        self._chk(_lib.lib().of2d_batch_get_motion(self._h, out))
+        return np.ascontiguousarray(
+            out.reshape(self.nbatch, 2, self.dimy, self.dimx).transpose(0, 3, 2, 1))
+
+    def warp(self, Imov) -> np.ndarray:
+        """Pair k's image warped by pair k's motion, ``[nbatch, dimx, dimy]``."""
+        m = self._stack(Imov, "Imov")
+        out = np.zeros_like(m)
+        self._chk(_lib.lib().of2d_batch_warp(self._h, m, out))
+        return np.ascontiguousarray(
+            out.reshape(self.nbatch, self.dimy, self.dimx).transpose(0, 2, 1))
+
+    def iterations(self) -> np.ndarray:
+        """``[nbatch, loops]`` iterations run, loops in execution order
+        (coarsest level first, its refines, ...)."""
+        buf = np.zeros(max(1, self.nbatch * self.loops), np.int32)
+        n = _lib.lib().of2d_batch_iterations(self._h, buf, buf.size)
+        return buf[: max(n, 0)].reshape(self.nbatch, self.loops).copy()
+
+    def last_errors(self, pair: int) -> np.ndarray:
+        """The Logger errors of the pair's last loop (empty with ``fixed_iters``)."""
+        if not 0 <= int(pair) < self.nbatch:
+            raise ValueError(f"pair {pair} outside [0, {self.nbatch})")
+        buf = np.zeros(self._maxn, np.float32)
+        n = _lib.lib().of2d_batch_last_errors(self._h, int(pair), buf, buf.size)
+        return buf[: max(n, 0)].copy()
+
+    def status(self) -> np.ndarray:
+        """``[nbatch]`` OF2D_OK (0) or OF2D_ERR_RUNTIME (2) per pair."""
+        out = (C.c_int * self.nbatch)()
+        self._chk(_lib.lib().of2d_batch_status(self._h, out))
+        return np.array(out[:], np.int32)
+
+    def last_error(self) -> str:
+        """The first failed pair's message ("Divide by zero exception (pair k)"), or ''."""
+        return _lib.lib().of2d_batch_last_error(self._h).decode()
+
+    def info(self) -> dict:
+        """``launches`` of the last estimate (independent of nbatch), ``loops``
+        per pair, ``loop_us`` (device time of the loop kernels), and per level
+        from level 0 ``placement`` (0: the iterate in global memory) and
+        ``threads`` of a pair's workgroup."""
+        buf = (C.c_int * 256)()
+        n = _lib.lib().of2d_batch_info(self._h, buf, 256)
+        v = list(buf[: max(n, 0)])
+        nlev = v[2]
+        return {"launches": v[0], "loops": v[1], "levels": nlev, "loop_us": v[3],
+                "placement": v[4: 4 + 2 * nlev: 2], "threads": v[5: 5 + 2 * nlev: 2]}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().of2d_batch_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ["BatchRegistration", "BATCH_MAXPX"]

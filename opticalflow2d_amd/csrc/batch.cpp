@@ -1,0 +1,336 @@
+// batch.cpp — host driver of the batched Horn-Schunck registration
+// (of2d_batch.h).  The pyramid and refine sequence is that of
+// Registration::estimate / estimate_level for Diffusion (registration.cpp),
+// applied to all pairs at once: the host enqueues every level's launches and
+// reads nothing back until the estimate ends; every decision (a pair's break,
+// its divide-by-zero) is taken in the kernels.  The number of launches does
+// not depend on the number of pairs.
+#include "of2d_batch.h"
+
+#include <algorithm>
+#include <cmath>
+
+#include "of2d_host.h"
+
+namespace of2d {
+namespace batch {
+
+Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int reg,
+             const float *params, unsigned nparams, int nrefine)
+    : B_(nbatch), dimx_(dimx), dimy_(dimy), nscales_(nscales), nrefine_(nrefine) {
+    if (nbatch < 1) throw std::invalid_argument("Error: batch needs nbatch >= 1\n");
+    if (nbatch > kMaxPairs)
+        throw std::invalid_argument("Error: batch takes at most 65535 pairs per call\n");
+    if (reg != 0)
+        throw std::invalid_argument(
+            "Error: the batched registration supports Diffusion regularisation only\n");
+    if (!valid_regularisation_parameters(reg, nparams))
+        throw std::invalid_argument(
+            "Invalid number of regularisation parameters for given regularisation method.\n");
+    if (!niter) throw std::invalid_argument("niter is NULL");
+    if (!params) throw std::invalid_argument("regparams is NULL");
+    if (dimx <= 0 || dimy <= 0 || nscales < 0)
+        throw std::invalid_argument("Error: invalid image dimensions\n");
+    if (nscales > 30) throw std::invalid_argument("Error: pyramid level with zero size\n");
+    if ((long)dimx * dimy > kMaxPx)
+        throw std::invalid_argument(
+            "Error: batch images may have at most 512 * 512 pixels (OF2D_BATCH_MAXPX)\n");
+    niter_.assign(niter, niter + nscales + 1);
+    alpha_ = params[0];
+    // ImageRegistration.cpp:56-61: dim(dimin.x/scale, dimin.y/scale) with float scale
+    ldx_.resize(nscales + 1);
+    ldy_.resize(nscales + 1);
+    for (int s = nscales; s >= 0; s--) {
+        const float scale = (float)std::pow(2, s);
+        ldx_[s] = (int)(unsigned)((float)(unsigned)dimx / scale);
+        ldy_[s] = (int)(unsigned)((float)(unsigned)dimy / scale);
+        if (ldx_[s] <= 0 || ldy_[s] <= 0)
+            throw std::invalid_argument("Error: pyramid level with zero size\n");
+    }
+    nloops_ = (nscales + 1) * std::max(nrefine, 0);
+    for (int n : niter_) maxn_ = std::max(maxn_, n);
+    h_status_.assign(B_, 0u);
+    h_iters_.assign((size_t)B_ * nloops_, 0);
+}
+
+Batch::~Batch() { release_device(); }
+
+void Batch::release_device() {
+    lv_.clear();
+    if (d_stage_) (void)hipFree(d_stage_);
+    if (d_status_) (void)hipFree(d_status_);
+    if (d_iters_) (void)hipFree(d_iters_);
+    if (d_errs_) (void)hipFree(d_errs_);
+    d_stage_ = nullptr;
+    d_status_ = nullptr;
+    d_iters_ = nullptr;
+    d_errs_ = nullptr;
+    for (hipEvent_t e : ev_)
+        if (e) (void)hipEventDestroy(e);
+    ev_.clear();
+    if (st_) (void)hipStreamDestroy(st_);
+    st_ = nullptr;
+    ref_pairs_ = 0;
+    ready_ = false;
+}
+
+void Batch::set_option(const std::string &key, double v) {
+    if (key == "fixed_iters")
+        fixed_ = v != 0;
+    else if (key == "device") {
+        if (ready_) throw std::invalid_argument("option 'device' must be set before first use");
+        device_ = (int)v;
+    } else
+        throw std::invalid_argument("unknown option: " + key);
+}
+
+// pairs per staging round of the boundary copies (64 MiB of doubles at most)
+size_t Batch::chunk_pairs() const {
+    const size_t n0 = (size_t)dimx_ * dimy_;
+    return std::min<size_t>(B_, std::max<size_t>(1, ((size_t)8 << 20) / (2 * n0)));
+}
+
+void Batch::ensure_device() {
+    if (ready_) {
+        OF2D_HIP(hipSetDevice(home_));  // the entry point's DeviceScope restores the caller's
+        return;
+    }
+    // a failure partway leaves nothing behind: the next call starts afresh
+    try {
+        allocate_device();
+    } catch (...) {
+        release_device();
+        throw;
+    }
+    ready_ = true;
+}
+
+void Batch::allocate_device() {
+    if (device_ >= 0) OF2D_HIP(hipSetDevice(device_));
+    OF2D_HIP(hipGetDevice(&home_));
+    OF2D_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+    lv_.resize(nscales_ + 1);
+    for (int s = 0; s <= nscales_; s++) {
+        BLevel &L = lv_[s];
+        L.dx = ldx_[s];
+        L.dy = ldy_[s];
+        L.P = pitch_for(L.dx);
+        L.stride = pair_stride(L.dx, L.dy);
+        // Iref: set_images allocates it, one image or B (ensure_reference)
+        L.Imov.alloc(L.dx, L.dy, B_);
+        L.Iaux.alloc(L.dx, L.dy, B_);
+        L.It.alloc(L.dx, L.dy, B_);
+        L.motion[0].alloc(L.dx, L.dy, B_);
+        L.motion[1].alloc(L.dx, L.dy, B_);
+        L.dI.alloc(L.dx, L.dy, B_);
+        L.est[0].alloc(L.dx, L.dy, B_);
+        L.est[1].alloc(L.dx, L.dy, B_);
+    }
+    stage_pairs_ = chunk_pairs();
+    OF2D_HIP(hipMalloc(&d_stage_, stage_pairs_ * 2 * (size_t)dimx_ * dimy_ * sizeof(double)));
+    OF2D_HIP(hipMalloc(&d_status_, sizeof(unsigned) * B_));
+    OF2D_HIP(hipMemset(d_status_, 0, sizeof(unsigned) * B_));
+    OF2D_HIP(hipMalloc(&d_iters_, sizeof(int) * std::max<size_t>(1, (size_t)B_ * nloops_)));
+    OF2D_HIP(hipMemset(d_iters_, 0, sizeof(int) * std::max<size_t>(1, (size_t)B_ * nloops_)));
+    ev_.assign(2 * (size_t)nloops_, nullptr);
+    for (hipEvent_t &e : ev_) OF2D_HIP(hipEventCreate(&e));
+    // the null-stream memsets are unordered with the non-blocking stream
+    OF2D_HIP(hipDeviceSynchronize());
+}
+
+// Iref of every level holds npairs images: one for a shared reference, else B.
+// The stream is idle here (set_images and estimate end in a synchronise).
+void Batch::ensure_reference(int npairs) {
+    if (ref_pairs_ >= npairs) return;
+    ref_pairs_ = 0;  // a failure partway: the next call allocates every level again
+    have_images_ = false;
+    for (BLevel &L : lv_) L.Iref.alloc(L.dx, L.dy, npairs);
+    OF2D_HIP(hipDeviceSynchronize());  // null-stream memsets, as above
+    ref_pairs_ = npairs;
+}
+
+// ImageRegistration::set_reference_image / set_moving_image per pair
+void Batch::set_images(const double *ref, bool shared_ref, const double *mov) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    ensure_reference(shared_ref ? 1 : B_);
+    const size_t n0 = (size_t)dimx_ * dimy_;
+    BLevel &L0 = lv_[0];
+    for (int which = 0; which < 2; which++) {
+        const double *src = which ? mov : ref;
+        const int npairs = (!which && shared_ref) ? 1 : B_;
+        for (int k0 = 0; k0 < npairs; k0 += (int)stage_pairs_) {
+            const int nk = std::min<int>((int)stage_pairs_, npairs - k0);
+            OF2D_HIP(hipMemcpyAsync(d_stage_, src + k0 * n0, nk * n0 * sizeof(double),
+                                    hipMemcpyHostToDevice, st_));
+            BField<float> &dst0 = which ? L0.Imov : L0.Iref;
+            launch_d2f(d_stage_, nk, dimx_, dimy_, dst0.p + k0 * L0.stride, L0.stride, L0.P, st_);
+            // the staging buffer is reused by the next round
+            OF2D_HIP(hipStreamSynchronize(st_));
+        }
+        for (int s = nscales_; s >= 1; s--) {
+            BLevel &L = lv_[s];
+            launch_downsample_image((which ? L0.Imov : L0.Iref).p, L0.stride, L0.dx, L0.dy, L0.P,
+                                    (which ? L.Imov : L.Iref).p, L.stride, L.dx, L.dy, L.P, npairs,
+                                    st_);
+        }
+    }
+    OF2D_HIP(hipStreamSynchronize(st_));
+    shared_ = shared_ref;
+    have_images_ = true;
+}
+
+// ImageRegistration::estimate_motion (:133-156) for every pair, each from a
+// zero motion field (as a new ImageRegistration's first estimate)
+void Batch::estimate() {
+    DeviceScope scope;
+    ensure_device();
+    if (!have_images_) throw std::invalid_argument("of2d_batch_estimate: no images set");
+    if (!fixed_ && !d_errs_ && maxn_ > 0 && nloops_ > 0)
+        OF2D_HIP(hipMalloc(&d_errs_, sizeof(float) * (size_t)B_ * nloops_ * maxn_));
+    const bool conv = !fixed_;
+    launches_ = 0;
+    pair_err_.clear();
+    OF2D_HIP(hipMemsetAsync(d_status_, 0, sizeof(unsigned) * B_, st_));
+    for (BLevel &L : lv_) {
+        L.mcur = 0;
+        OF2D_HIP(hipMemsetAsync(L.motion[0].base, 0, L.motion[0].bytes(), st_));
+    }
+    BLevel &L0 = lv_[0];
+    int loop = 0;
+    for (int s = nscales_; s >= 0; s--) {
+        BLevel &L = lv_[s];
+        if (s > 0 && s < nscales_) {
+            launch_downsample_motion(L0.motion[L0.mcur].p, L0.stride, L0.dx, L0.dy, L0.P,
+                                     L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P, B_, d_status_,
+                                     st_);
+            launches_++;
+        }
+        // estimate_motion_at_current_resolution
+        for (int refine = 0; refine < nrefine_; refine++, loop++) {
+            // *Iaux = *Imov; Iaux->warp2d(*motion)
+            launch_warp(L.Imov.p, L.motion[L.mcur].p, L.Iaux.p, L.stride, L.dx, L.dy, L.P, B_,
+                        d_status_, st_);
+            launch_gradients(L.Iref.p, shared_ ? 0 : L.stride, L.Iaux.p, L.dI.p, L.It.p, L.stride,
+                             L.dx, L.dy, L.P, B_, d_status_, st_);
+            // motion_est starts at zero
+            OF2D_HIP(hipMemsetAsync(L.est[0].base, 0, L.est[0].bytes(), st_));
+            LoopArgs a;
+            a.u0 = L.est[0].p;
+            a.u1 = L.est[1].p;
+            a.dI = L.dI.p;
+            a.It = L.It.p;
+            a.stride = L.stride;
+            a.dx = L.dx;
+            a.dy = L.dy;
+            a.P = L.P;
+            a.niter = niter_[s];
+            a.alphasq = alpha_ * alpha_;  // OpticalFlowDiffusion.cpp:70
+            a.status = d_status_;
+            a.iters = d_iters_;
+            a.nloops = nloops_;
+            a.loop = loop;
+            a.errs = d_errs_;
+            a.maxn = maxn_;
+            OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
+            launch_hs_loop(a, B_, conv, st_);
+            OF2D_HIP(hipEventRecord(ev_[2 * loop + 1], st_));
+            // motion->accumulate(*motion_est)
+            launch_accumulate(L.motion[L.mcur].p, L.est[0].p, L.est[1].p, L.motion[1 - L.mcur].p,
+                              L.stride, L.dx, L.dy, L.P, B_, d_iters_, nloops_, loop, d_status_,
+                              st_);
+            L.mcur ^= 1;
+            launches_ += 4;
+        }
+        if (s > 0) {
+            launch_upsample_motion(L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P,
+                                   L0.motion[L0.mcur].p, L0.stride, L0.dx, L0.dy, L0.P, B_,
+                                   d_status_, st_);
+            launches_++;
+        }
+    }
+    // a divide-by-zero pair's motion is left zero
+    launch_zero_failed(L0.motion[L0.mcur].base, L0.stride, B_, d_status_, st_);
+    launches_++;
+    OF2D_HIP(hipMemcpyAsync(h_status_.data(), d_status_, sizeof(unsigned) * B_,
+                            hipMemcpyDeviceToHost, st_));
+    if (nloops_ > 0)
+        OF2D_HIP(hipMemcpyAsync(h_iters_.data(), d_iters_, sizeof(int) * h_iters_.size(),
+                                hipMemcpyDeviceToHost, st_));
+    h_errs_.clear();
+    if (conv && d_errs_) {
+        h_errs_.resize((size_t)B_ * nloops_ * maxn_);
+        OF2D_HIP(hipMemcpyAsync(h_errs_.data(), d_errs_, sizeof(float) * h_errs_.size(),
+                                hipMemcpyDeviceToHost, st_));
+    }
+    OF2D_HIP(hipStreamSynchronize(st_));
+    loop_us_ = 0.0;
+    for (int l = 0; l < nloops_; l++) {
+        float ms = 0.0f;
+        OF2D_HIP(hipEventElapsedTime(&ms, ev_[2 * l], ev_[2 * l + 1]));
+        loop_us_ += 1000.0 * (double)ms;
+    }
+    for (int k = 0; k < B_; k++)
+        if (h_status_[k] & kStatusDivZero) {
+            pair_err_ = "Divide by zero exception (pair " + std::to_string(k) + ")";
+            break;
+        }
+}
+
+void Batch::get_motion(double *out) {
+    DeviceScope scope;
+    ensure_device();
+    BLevel &L0 = lv_[0];
+    const size_t n0 = (size_t)dimx_ * dimy_;
+    for (int k0 = 0; k0 < B_; k0 += (int)stage_pairs_) {
+        const int nk = std::min<int>((int)stage_pairs_, B_ - k0);
+        launch_motion_to_planar(L0.motion[L0.mcur].p + k0 * L0.stride, L0.stride, L0.P, dimx_,
+                                dimy_, d_stage_, nk, st_);
+        OF2D_HIP(hipMemcpyAsync(out + k0 * 2 * n0, d_stage_, sizeof(double) * 2 * n0 * nk,
+                                hipMemcpyDeviceToHost, st_));
+        OF2D_HIP(hipStreamSynchronize(st_));
+    }
+}
+
+// pair k's image by pair k's motion (WrapperOpticalFlow2d.cpp:120-137 per pair);
+// level 0's Iaux and It are free between estimates and hold the images here
+void Batch::warp(const double *in, double *out) {
+    DeviceScope scope;
+    ensure_device();
+    BLevel &L0 = lv_[0];
+    const size_t n0 = (size_t)dimx_ * dimy_;
+    for (int k0 = 0; k0 < B_; k0 += (int)stage_pairs_) {
+        const int nk = std::min<int>((int)stage_pairs_, B_ - k0);
+        const long off = k0 * L0.stride;
+        OF2D_HIP(hipMemcpyAsync(d_stage_, in + k0 * n0, nk * n0 * sizeof(double),
+                                hipMemcpyHostToDevice, st_));
+        launch_d2f(d_stage_, nk, dimx_, dimy_, L0.Iaux.p + off, L0.stride, L0.P, st_);
+        launch_warp(L0.Iaux.p + off, L0.motion[L0.mcur].p + off, L0.It.p + off, L0.stride, dimx_,
+                    dimy_, L0.P, nk, nullptr, st_);
+        launch_f2d(L0.It.p + off, L0.stride, L0.P, dimx_, dimy_, d_stage_, nk, st_);
+        OF2D_HIP(hipMemcpyAsync(out + k0 * n0, d_stage_, nk * n0 * sizeof(double),
+                                hipMemcpyDeviceToHost, st_));
+        OF2D_HIP(hipStreamSynchronize(st_));
+    }
+}
+
+std::vector<float> Batch::last_errors(int pair) const {
+    std::vector<float> v;
+    if (pair < 0 || pair >= B_ || h_errs_.empty() || nloops_ == 0) return v;
+    const size_t loop = (size_t)pair * nloops_ + (nloops_ - 1);
+    const int n = std::min(h_iters_[loop], maxn_);
+    v.assign(h_errs_.begin() + loop * maxn_, h_errs_.begin() + loop * maxn_ + n);
+    return v;
+}
+
+std::vector<int> Batch::info() const {
+    std::vector<int> v = {launches_, nloops_, nscales_ + 1, (int)std::lround(loop_us_)};
+    for (int s = 0; s <= nscales_; s++) {
+        v.push_back(0);  // the iterate ping-pongs in global memory at every level
+        v.push_back(kLoopThreads);
+    }
+    return v;
+}
+
+}  // namespace batch
+}  // namespace of2d

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <string>
 
+#include "of2d_batch.h"
 #include "of2d_host.h"
 #include "of2d_solvers.h"
 
@@ -1396,6 +1397,120 @@ int of2d_gateway(int nlhs, double **plhs, int nrhs, const double *const *prhs) {
     }
     g_gateway_err = "Error: invalid number of input and output variables gives.\n";
     return OF2D_ERR_STATE;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ batched Horn-Schunck
+struct of2d_batch {
+    std::unique_ptr<of2d::batch::Batch> b;
+    std::string err;
+};
+
+static_assert(OF2D_BATCH_MAXPX == of2d::batch::kMaxPx, "include/of2d.h documents the batch's size");
+
+extern "C" {
+
+int of2d_batch_create(of2d_batch **out, int nbatch, int dimx, int dimy, const int *niter,
+                      int nscales, int reg, const float *regparams, unsigned nparams,
+                      int nrefine) {
+    if (!out) return refuse(nullptr, "of2d_batch_create: out is NULL");
+    *out = nullptr;
+    auto *c = new of2d_batch();
+    std::string err;
+    const int rc = guarded(err, [&] {
+        c->b.reset(new of2d::batch::Batch(nbatch, dimx, dimy, niter, nscales, reg, regparams,
+                                          nparams, nrefine));
+    });
+    if (rc != OF2D_OK) {
+        g_gateway_err = err;
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return OF2D_OK;
+}
+
+int of2d_batch_set_option(of2d_batch *b, const char *key, double value) {
+    if (!b || !key) return refuse(nullptr, "of2d_batch_set_option: b or key is NULL");
+    return guarded(b->err, [&] { b->b->set_option(key, value); });
+}
+
+int of2d_batch_set_images(of2d_batch *b, const double *Iref, int shared_ref, const double *Imov) {
+    if (!b) return refuse(nullptr, "of2d_batch_set_images: b is NULL");
+    if (!Iref || !Imov) {
+        b->err = "of2d_batch_set_images: Iref or Imov is NULL";
+        return OF2D_ERR_INVALID_ARGUMENT;
+    }
+    return guarded(b->err, [&] { b->b->set_images(Iref, shared_ref != 0, Imov); });
+}
+
+int of2d_batch_estimate(of2d_batch *b) {
+    if (!b) return refuse(nullptr, "of2d_batch_estimate: b is NULL");
+    return guarded(b->err, [&] { b->b->estimate(); });
+}
+
+int of2d_batch_get_motion(of2d_batch *b, double *out) {
+    if (!b) return refuse(nullptr, "of2d_batch_get_motion: b is NULL");
+    if (!out) {
+        b->err = "of2d_batch_get_motion: out is NULL";
+        return OF2D_ERR_INVALID_ARGUMENT;
+    }
+    return guarded(b->err, [&] { b->b->get_motion(out); });
+}
+
+int of2d_batch_warp(of2d_batch *b, const double *Imov, double *out) {
+    if (!b) return refuse(nullptr, "of2d_batch_warp: b is NULL");
+    if (!Imov || !out) {
+        b->err = "of2d_batch_warp: Imov or out is NULL";
+        return OF2D_ERR_INVALID_ARGUMENT;
+    }
+    return guarded(b->err, [&] { b->b->warp(Imov, out); });
+}
+
+int of2d_batch_status(const of2d_batch *b, int *out) {
+    if (!b || !out) return OF2D_ERR_INVALID_ARGUMENT;
+    const auto &s = b->b->status();
+    for (size_t k = 0; k < s.size(); k++)
+        out[k] = (s[k] & of2d::kStatusDivZero) ? OF2D_ERR_RUNTIME : OF2D_OK;
+    return OF2D_OK;
+}
+
+int of2d_batch_iterations(const of2d_batch *b, int *out, int cap) {
+    if (!b) return -1;
+    const auto &v = b->b->iterations();
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+
+int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap) {
+    if (!b || pair < 0 || pair >= b->b->nbatch()) return -1;
+    const std::vector<float> v = b->b->last_errors(pair);
+    for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+
+int of2d_batch_info(const of2d_batch *b, int *info, int n) {
+    if (!b) return -1;
+    const std::vector<int> v = b->b->info();
+    for (int i = 0; i < (int)v.size() && i < n; i++) info[i] = v[i];
+    return (int)v.size();
+}
+
+int of2d_batch_destroy(of2d_batch *b) {
+    if (!b) return OF2D_ERR_INVALID_ARGUMENT;
+    std::string err;
+    const int rc = guarded(err, [&] {
+        of2d::DeviceScope scope;
+        b->b.reset();
+    });
+    delete b;
+    return rc;
+}
+
+const char *of2d_batch_last_error(const of2d_batch *b) {
+    if (!b) return g_gateway_err.c_str();
+    return b->err.empty() ? b->b->pair_error().c_str() : b->err.c_str();
 }
 
 }  // extern "C"

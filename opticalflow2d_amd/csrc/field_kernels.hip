@@ -5,6 +5,7 @@
 // bit-identical to the reference.  All are HBM-bound gathers/streams; one
 // thread per pixel, 64-wide rows of the pitched layout per wave.
 #include "of2d_device.h"
+#include "field_px.h"
 
 namespace of2d {
 
@@ -66,18 +67,7 @@ void launch_motion_to_planar(const float2 *m, int P, int dimx, int dimy, double 
 __global__ void downsample_image_kernel(const float *__restrict__ in, int dxi, int dyi, int Pi,
                                         float *__restrict__ out, int dxo, int dyo, int Po) {
     OF2D_PX_PROLOGUE(dxo, dyo)
-    const int fx = dxi / dxo, fy = dyi / dyo;
-    float val = 0.0f;
-    int p = 0;
-    for (int ii = 0; ii < fx; ii++)
-        for (int jj = 0; jj < fy; jj++) {
-            // (no tap lies past the end: j * fy + jj <= dyo * fy - 1 <= dyi - 1
-            // for fy = dyi / dyo, so the reference's k >= sizein skip never fires)
-            const int y = j * fy + jj;
-            val += in[(long)y * Pi + i * fx + ii];
-            p++;
-        }
-    if (p != 0) out[(long)j * Po + i] = val / (float)p;
+    downsample_image_px(in, dxi, dyi, Pi, out + (long)j * Po + i, dxo, dyo, i, j);
 }
 void launch_downsample_image(const float *in, int dxi, int dyi, int Pi, float *out, int dxo,
                              int dyo, int Po, hipStream_t st) {
@@ -96,24 +86,7 @@ __global__ void downsample_motion_kernel(const float2 *__restrict__ in, int dxi,
                                          float2 *__restrict__ out, int dxo, int dyo, int Po,
                                          float rx, float ry) {
     OF2D_PX_PROLOGUE(dxo, dyo)
-    const int fx = dxi / dxo, fy = dyi / dyo;
-    float vx = 0.0f, vy = 0.0f;
-    int p = 0;
-    for (int ii = 0; ii < fx; ii++)
-        for (int jj = 0; jj < fy; jj++) {
-            // (no tap lies past the end: j * fy + jj <= dyo * fy - 1 <= dyi - 1
-            // for fy = dyi / dyo, so the reference's k >= sizein skip never fires)
-            const int y = j * fy + jj;
-            const float2 a = in[(long)y * Pi + i * fx + ii];
-            vx = vx + a.x;
-            vy = vy + a.y;
-            p++;
-        }
-    float2 o = out[(long)j * Po + i];
-    if (p != 0) o = make_float2(vx / (float)p, vy / (float)p);
-    o.x *= rx;
-    o.y *= ry;
-    out[(long)j * Po + i] = o;
+    downsample_motion_px(in, dxi, dyi, Pi, out + (long)j * Po + i, dxo, dyo, i, j, rx, ry);
 }
 void launch_downsample_motion(const float2 *in, int dxi, int dyi, int Pi, float2 *out, int dxo,
                               int dyo, int Po, hipStream_t st) {
@@ -134,41 +107,7 @@ __global__ void upsample_motion_kernel(const float2 *__restrict__ in, int dxi, i
                                        float2 *__restrict__ out, int dxo, int dyo, int Po,
                                        float rx, float ry) {
     OF2D_PX_PROLOGUE(dxo, dyo)
-    float2 o = out[(long)j * Po + i];
-    const float px = (float)i * (float)dxi / (float)dxo;
-    const int dx = (int)floorf(px);
-    const float fx = px - (float)dx;
-    const float py = (float)j * (float)dyi / (float)dyo;
-    const int dy = (int)floorf(py);
-    const float fy = py - (float)dy;
-    const unsigned lin = (unsigned)dx + (unsigned)dy * (unsigned)dxi;
-    if (lin < (unsigned)dxi * (unsigned)dyi) {
-        const float2 *b = in + (long)dy * Pi + dx;
-        float vx = (b[0].x * (1 - fx)) * (1 - fy);
-        float vy = (b[0].y * (1 - fx)) * (1 - fy);
-        float w = (1 - fx) * (1 - fy);
-        const bool ax = (unsigned)dx < (unsigned)(dxi - 1);
-        const bool ay = (unsigned)dy < (unsigned)(dyi - 1);
-        if (ax) {
-            vx = vx + (b[1].x * fx) * (1 - fy);
-            vy = vy + (b[1].y * fx) * (1 - fy);
-            w += fx * (1 - fy);
-        }
-        if (ay) {
-            vx = vx + (b[Pi].x * (1 - fx)) * fy;
-            vy = vy + (b[Pi].y * (1 - fx)) * fy;
-            w += (1 - fx) * fy;
-        }
-        if (ax && ay) {
-            vx = vx + (b[Pi + 1].x * fx) * fy;
-            vy = vy + (b[Pi + 1].y * fx) * fy;
-            w += fx * fy;
-        }
-        if (w != 0) o = make_float2(vx / w, vy / w);
-    }
-    o.x *= rx;
-    o.y *= ry;
-    out[(long)j * Po + i] = o;
+    upsample_motion_px(in, dxi, dyi, Pi, out + (long)j * Po + i, dxo, dyo, i, j, rx, ry);
 }
 void launch_upsample_motion(const float2 *in, int dxi, int dyi, int Pi, float2 *out, int dxo,
                             int dyo, int Po, hipStream_t st) {
@@ -186,40 +125,7 @@ void launch_upsample_motion(const float2 *in, int dxi, int dyi, int Pi, float2 *
 // Image::warp2d (src/Image.cpp:119-182): pull-back bilinear sample of src at
 // (i + u.x, j + u.y); out-of-range floor keeps the original pixel; at the
 // right/top edge only in-range taps are used, renormalised by their weight.
-//
-// Branch-free: the taps are loaded unconditionally (an out-of-range tap
-// pattern reads element 0; g[1], g[P], g[P+1] of an in-image pixel stay in the
-// allocation: pitch padding and the zeroed ghost j-line below the last row)
-// and the reference's conditional terms are selects.
-__device__ __forceinline__ float warp_px(const float *__restrict__ src, float2 m, float own, int i,
-                                         int j, int dimx, int dimy, int P) {
-    const float px = (float)i + m.x;
-    const int dx = (int)floorf(px);
-    const float fx = px - (float)dx;
-    const float py = (float)j + m.y;
-    const int dy = (int)floorf(py);
-    const float fy = py - (float)dy;
-    const bool ok = !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
-    const bool ax = dx < dimx - 1, ay = dy < dimy - 1;
-    const float *b = src + (ok ? ((unsigned)dy * (unsigned)P + (unsigned)dx) : 0u);
-    const float t00 = b[0], t10 = b[1], t01 = b[P], t11 = b[P + 1];
-    float val = (t00 * (1 - fx)) * (1 - fy);
-    float w = (1 - fx) * (1 - fy);
-    const float v10 = val + (t10 * fx) * (1 - fy), w10 = w + fx * (1 - fy);
-    val = ax ? v10 : val;
-    w = ax ? w10 : w;
-    const float v01 = val + (t01 * (1 - fx)) * fy, w01 = w + (1 - fx) * fy;
-    val = ay ? v01 : val;
-    w = ay ? w01 : w;
-    const float v11 = val + (t11 * fx) * fy, w11 = w + fx * fy;
-    val = (ax && ay) ? v11 : val;
-    w = (ax && ay) ? w11 : w;
-    // val / w is val itself when w rounds to exactly 1 (demons_kernels.hip
-    // warp_batch): divide only in the waves where some lane needs it
-    float q = val;
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(ok && w != 1.0f) != 0, 0)) q = val / w;
-    return (ok && w != 0) ? q : own;
-}
+// (warp_px: field_px.h, shared with batch_kernels.hip)
 __global__ void warp_kernel(const float *__restrict__ src, const float2 *__restrict__ u,
                             float *__restrict__ dst, int dimx, int dimy, int P) {
     OF2D_PX_PROLOGUE(dimx, dimy)
@@ -242,22 +148,8 @@ __global__ void gradients_kernel(const float *__restrict__ Iref, const float *__
                                  int nrows, int P, int row0, int dimy) {
     OF2D_PX_PROLOGUE(dimx, nrows)
     const long idx = (long)j * P + i;
-    const int jg = row0 + j;  // global j-line: border rule uses the global index
-    float gx, gy;
-    if (i == 0)
-        gx = Ia[idx + 1] - Ia[idx];
-    else if (i == dimx - 1)
-        gx = Ia[idx] - Ia[idx - 1];
-    else
-        gx = (Ia[idx + 1] - Ia[idx - 1]) / 2.0f;
-    if (jg == 0)
-        gy = Ia[idx + P] - Ia[idx];
-    else if (jg == dimy - 1)
-        gy = Ia[idx] - Ia[idx - P];
-    else
-        gy = (Ia[idx + P] - Ia[idx - P]) / 2.0f;
-    dI[idx] = make_float2(gx, gy);
-    It[idx] = Ia[idx] - Iref[idx];
+    // global j-line: the border rule uses the global index
+    gradients_px(Iref, Ia, dI, It, idx, i, row0 + j, dimx, dimy, P);
 }
 void launch_gradients_rows(const float *Iref, const float *Iaux, float2 *dI, float *It, int dimx,
                            int nrows, int P, int row0, int dimy, hipStream_t st) {

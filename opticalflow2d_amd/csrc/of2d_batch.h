@@ -1,0 +1,178 @@
+// of2d_batch.h — B independent Horn-Schunck registrations of one size in one
+// call (batch.cpp, batch_kernels.hip).
+//
+// Layout: the B fields of a pyramid level live in one allocation, pair k at
+// k * stride elements, each laid out exactly as a Field<T> (of2d_host.h): the
+// pitch of pitch_for(dimx), one zeroed ghost j-line above row 0 and one below
+// the last row, kPitchAlign elements of slack; stride = (dimy + 2) * P +
+// kPitchAlign for every element type.  The per-pixel code (field_px.h,
+// accumulate_px, hs::update_px) therefore sees what it sees in the one-pair
+// path.  Pointers passed to the launches address row 0 of pair 0.
+//
+// One workgroup runs the whole iteration loop of one pair; no workgroup waits
+// for another.  The passes around the loop take the pair as grid dimension z.
+// Every kernel of an estimate returns at once for a pair whose status word has
+// kStatusDivZero set, so that pair's fields stop changing and the others run on.
+#pragma once
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "of2d_device.h"
+
+namespace of2d {
+namespace batch {
+
+constexpr int kMaxPx = 512 * 512;   // OF2D_BATCH_MAXPX
+constexpr int kMaxPairs = 65535;    // the pair is grid dimension z of the passes
+
+inline long pair_stride(int dimx, int dimy) {
+    return (long)(dimy + 2) * pitch_for(dimx) + kPitchAlign;
+}
+// waves of a pair's workgroup in the loop kernel (1024 threads at every level)
+constexpr int kLoopWaves = 16;
+constexpr int kLoopThreads = 64 * kLoopWaves;
+
+struct LoopArgs {
+    float2 *u0, *u1;      // the iterate's two buffers; iteration t reads u[t & 1]
+    const float2 *dI;
+    const float *It;
+    long stride;
+    int dx, dy, P, niter;
+    float alphasq;
+    unsigned *status;     // [B]
+    int *iters;           // [B][nloops]: iterations run by this loop
+    int nloops, loop;
+    float *errs;          // [B][nloops][maxn] (convergence on)
+    int maxn;
+};
+// conv: Logger sums, errors and the reference's break (fp64 sums in a fixed
+// order: the logger_fp64 semantics); otherwise exactly niter iterations
+void launch_hs_loop(const LoopArgs &a, int B, bool conv, hipStream_t st);
+
+void launch_d2f(const double *in, int npairs, int dimx, int dimy, float *out, long so, int P,
+                hipStream_t st);
+void launch_f2d(const float *in, long si, int P, int dimx, int dimy, double *out, int npairs,
+                hipStream_t st);
+void launch_motion_to_planar(const float2 *m, long sm, int P, int dimx, int dimy, double *out,
+                             int npairs, hipStream_t st);
+void launch_downsample_image(const float *in, long si, int dxi, int dyi, int Pi, float *out,
+                             long so, int dxo, int dyo, int Po, int B, hipStream_t st);
+// status (the launches below): per-pair words, nullptr outside an estimate
+void launch_downsample_motion(const float2 *in, long si, int dxi, int dyi, int Pi, float2 *out,
+                              long so, int dxo, int dyo, int Po, int B, const unsigned *status,
+                              hipStream_t st);
+void launch_upsample_motion(const float2 *in, long si, int dxi, int dyi, int Pi, float2 *out,
+                            long so, int dxo, int dyo, int Po, int B, const unsigned *status,
+                            hipStream_t st);
+void launch_warp(const float *src, const float2 *u, float *dst, long stride, int dimx, int dimy,
+                 int P, int B, const unsigned *status, hipStream_t st);
+// sref: Iref's pair stride, 0 for one reference shared by every pair
+void launch_gradients(const float *Iref, long sref, const float *Iaux, float2 *dI, float *It,
+                      long stride, int dimx, int dimy, int P, int B, const unsigned *status,
+                      hipStream_t st);
+// m_new <- accumulate(m_old, est) with est = v[iters[pair][loop] & 1]: the
+// buffer holding the pair's last iterate
+void launch_accumulate(const float2 *m_old, const float2 *v0, const float2 *v1, float2 *m_new,
+                       long stride, int dimx, int dimy, int P, int B, const int *iters,
+                       int nloops, int loop, const unsigned *status, hipStream_t st);
+// the whole field of every pair with kStatusDivZero <- 0 (count: elements from
+// m, the allocation's base, per pair)
+void launch_zero_failed(float2 *m, long stride, int B, const unsigned *status, hipStream_t st);
+
+template <class T>
+struct BField {
+    T *base = nullptr;
+    T *p = nullptr;  // row 0 of pair 0
+    size_t count = 0;
+    BField() = default;
+    BField(const BField &) = delete;
+    BField &operator=(const BField &) = delete;
+    BField(BField &&o) noexcept { *this = std::move(o); }
+    BField &operator=(BField &&o) noexcept {
+        std::swap(base, o.base);
+        std::swap(p, o.p);
+        std::swap(count, o.count);
+        return *this;
+    }
+    ~BField() { release(); }
+    void release() {
+        if (base) (void)hipFree(base);
+        base = p = nullptr;
+        count = 0;
+    }
+    void alloc(int dimx, int dimy, int npairs) {
+        release();
+        count = (size_t)pair_stride(dimx, dimy) * npairs;
+        OF2D_HIP(hipMalloc(&base, count * sizeof(T)));
+        OF2D_HIP(hipMemset(base, 0, count * sizeof(T)));
+        p = base + pitch_for(dimx);
+    }
+    size_t bytes() const { return count * sizeof(T); }
+};
+
+struct BLevel {
+    int dx = 0, dy = 0, P = 0;
+    long stride = 0;
+    BField<float> Iref, Imov, Iaux, It;
+    BField<float2> motion[2], dI, est[2];
+    int mcur = 0;
+};
+
+class Batch {
+   public:
+    // throws std::invalid_argument for everything of2d_batch_create refuses;
+    // no device work
+    Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int reg,
+          const float *params, unsigned nparams, int nrefine);
+    ~Batch();
+    void set_option(const std::string &key, double v);
+    void set_images(const double *ref, bool shared_ref, const double *mov);
+    void estimate();
+    void get_motion(double *out);
+    void warp(const double *in, double *out);
+    int nbatch() const { return B_; }
+    int nloops() const { return nloops_; }
+    const std::vector<unsigned> &status() const { return h_status_; }
+    const std::vector<int> &iterations() const { return h_iters_; }
+    std::vector<float> last_errors(int pair) const;
+    // {launches of the last estimate, loops per pair, levels, loop kernels'
+    // device time of the last estimate in microseconds, then per level from 0:
+    // iterate placement (0: global memory), threads of the pair's workgroup}
+    std::vector<int> info() const;
+    // "" or the first pair's divide-by-zero message
+    const std::string &pair_error() const { return pair_err_; }
+
+   private:
+    void ensure_device();
+    void allocate_device();
+    void release_device();
+    void ensure_reference(int npairs);
+    size_t chunk_pairs() const;
+    int B_, dimx_, dimy_, nscales_, nrefine_, nloops_ = 0;
+    std::vector<int> niter_, ldx_, ldy_;
+    float alpha_;
+    bool fixed_ = false, shared_ = false, have_images_ = false;
+    int device_ = -1, home_ = -1;
+    bool ready_ = false;
+    int ref_pairs_ = 0;  // images Iref holds at every level: 0, 1 (shared) or B
+    hipStream_t st_ = nullptr;
+    std::vector<BLevel> lv_;
+    double *d_stage_ = nullptr;
+    size_t stage_pairs_ = 0;
+    unsigned *d_status_ = nullptr;
+    int *d_iters_ = nullptr;
+    float *d_errs_ = nullptr;
+    int maxn_ = 0;
+    std::vector<hipEvent_t> ev_;
+    int launches_ = 0;
+    double loop_us_ = 0.0;
+    std::vector<unsigned> h_status_;
+    std::vector<int> h_iters_;
+    std::vector<float> h_errs_;
+    std::string pair_err_;
+};
+
+}  // namespace batch
+}  // namespace of2d
