@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "iter_schedule.h"
 #include "of2d_device.h"
 
 namespace of2d {
@@ -117,10 +118,6 @@ struct HostScratch {
     void ensure(int n);
     ~HostScratch();
 };
-
-// Per-iteration Logger norms -> error, exactly the reference's float formula
-// (Logger.cpp:37-39, Motion.cpp:47) applied to fp64 sums.
-float logger_error(double sum_diff, double sum_prev, double npx);
 
 // The reference-exact Logger's pipeline depth (Registration, below): iterate
 // ring buffers, workspace sets and walk streams (build knobs for A/B runs)
@@ -247,6 +244,14 @@ class Registration {
     std::vector<std::shared_ptr<MultiHS>> lv_multi_;
     void check_status();
     void check_reported_status(unsigned st);
+    // a chunk's Logger errors onto last_err_ (printed when verbose) and its
+    // chunk-local breaking iteration, or -1 (sched::logger_break)
+    template <class T>
+    int logger_break(const T *sums, int C, int k0, double npx, bool fixed) {
+        return sched::logger_break(sums, C, k0, npx, fixed, last_err_, [&](int k, float err) {
+            if (verbose_) print("Iteration: %d\tError:%.4f\n", k, (double)err);
+        });
+    }
 
     int dimx_, dimy_, nscales_, nrefine_, reg_, verbose_;
     std::vector<int> niter_;
@@ -279,6 +284,8 @@ class Registration {
     // (passed: the batch's pass is already enqueued and ev_pass_[g] recorded)
     void enqueue_norms(const SeqnormBatch &B, const Level &L, int g, double npx = 0.0,
                        float *seqh_out = nullptr, bool passed = false);
+    // st_ behind the walks that read the buffers iterations [t, t + k) rewrite
+    void wait_ring_walks(const std::vector<int> &group_of, int t, int k);
     void print_sn_debug(const Level &L, const int *dbg, int k0, int lo, int hi);
     hipStream_t sn_st_ = nullptr, fx_st_ = nullptr, wk_st_[OF2D_SN_WALKERS] = {};
     int ncu_ = 256;        // compute units of the device

@@ -34,12 +34,7 @@
 
 namespace of2d {
 
-float logger_error(double sum_diff, double sum_prev, double npx) {
-    const float n = (float)npx;
-    const float prevnorm = (float)sum_prev / n;
-    const float diffnorm = (float)sum_diff / n;
-    return prevnorm == 0 ? 0.0f : diffnorm / prevnorm;
-}
+// logger_error and the loops' schedule (rotation, ring, plans, break): iter_schedule.h
 
 void HostScratch::ensure(int n) {
     if (n <= cap) return;
@@ -468,15 +463,9 @@ int Registration::run_chunked_exact(Level &L, int niter, int nb, const StepFn &s
     if (step3m) return run_exact_pipelined(L, niter, step, final_buf, step3m);
     const double npx = (double)L.dx * L.dy;
     last_err_.clear();
-    constexpr int R = kRing;
-    static_assert(R + 1 <= (int)(sizeof(L.est) / sizeof(L.est[0])), "ring");
-    for (int b = 3; b <= R; b++)
+    using Rg = sched::Ring<kRing>;
+    for (int b = 3; b <= kRing; b++)  // Level::est holds the ring (of2d_host.h)
         if (!L.est[b].p) L.est[b].alloc(L.dx, L.dy);
-    auto ring = [&](int a, int t) {  // the (t mod R)-th buffer other than a
-        const int i = t % R;
-        return i < a ? i : i + 1;
-    };
-    auto src_of = [&](int a, int t) { return t == 0 ? a : ring(a, t - 1); };
     auto ev = [](hipEvent_t *e, int g) { return e[g % kExactEv]; };
     constexpr bool sn_debug = OF2D_SN_DEBUG != 0;
     constexpr int kDbg = 10;
@@ -492,22 +481,17 @@ int Registration::run_chunked_exact(Level &L, int niter, int nb, const StepFn &s
         for (int t = 0; t < C; g++) {
             const int k = std::min(3, C - t);
             for (int m = t; m < t + k; m++) group_of[m] = g;
-            // the buffers of iterates t + 1 .. t + k held iterates t + 1 - R ..
-            // t + k - R, read by the walks of iterations t - R .. t + k - R
-            for (int q = std::max(t - R, 0), last = -1; q <= t + k - R; q++)
-                if (group_of[q] != last) {
-                    last = group_of[q];
-                    OF2D_HIP(hipStreamWaitEvent(st_, ev(ev_walk_, last), 0));
-                }
+            wait_ring_walks(group_of, t, k);
             for (int m = t; m < t + k; m++)
-                step(L.est[src_of(a, m)].p, L.est[ring(a, m)].p, d_partial_ + (size_t)m * nb * 2);
+                step(L.est[Rg::src(a, m)].p, L.est[Rg::ring(a, m)].p,
+                     d_partial_ + (size_t)m * nb * 2);
             OF2D_HIP(hipEventRecord(ev(ev_step_, g), st_));
             SeqnormBatch B;
             B.K = k;
-            B.u[0] = L.est[src_of(a, t)].p;
+            B.u[0] = L.est[Rg::src(a, t)].p;
             for (int i = 0; i < k; i++) {
                 const int w = 3 * (g % kSeqSets) + i;
-                B.u[i + 1] = L.est[ring(a, t + i)].p;
+                B.u[i + 1] = L.est[Rg::ring(a, t + i)].p;
                 B.ws[i] = d_seqws_[w].p;
                 B.use_profile[i] = walked[w] && seq_dx_[w] == L.dx && seq_dy_[w] == L.dy;
                 seq_dx_[w] = L.dx;
@@ -526,25 +510,33 @@ int Registration::run_chunked_exact(Level &L, int niter, int nb, const StepFn &s
                                 st_));
         check_status();  // synchronises st_ (and with it every norm of the chunk)
         if (sn_debug) print_sn_debug(L, dbg.p, k0, 0, C);
-        for (int t = 0; t < C; t++) {
-            const int k = k0 + t;
-            const float err = logger_error(hs_.flt[2 * t], hs_.flt[2 * t + 1], npx);
-            last_err_.push_back(err);
-            if (verbose_) print("Iteration: %d\tError:%.4f\n", k, (double)err);
-            if (err < 0.001f && k > 1) {  // ImageRegistrationOpticalFlow.cpp:131-134
-                // iteration t's buffer was reused by iteration t + R: replay
-                if (t + R <= C - 1)
-                    for (int r = 0; r <= t; r++)
-                        step(L.est[src_of(a, r)].p, L.est[ring(a, r)].p, d_partial_);
-                final_buf = ring(a, t);
-                return k + 1;
-            }
+        const int t = logger_break(hs_.flt, C, k0, npx, false);
+        if (t >= 0) {
+            if (Rg::replay_needed(t, C))
+                for (int r = 0; r <= t; r++)
+                    step(L.est[Rg::src(a, r)].p, L.est[Rg::ring(a, r)].p, d_partial_);
+            final_buf = Rg::ring(a, t);
+            return k0 + t + 1;
         }
-        a = ring(a, C - 1);
+        a = Rg::ring(a, C - 1);
         k0 += C;
     }
     final_buf = a;
     return niter;
+}
+
+// Before the steps of iterations [t, t + k) of the exact loops: their iterates
+// t + 1 .. t + k overwrite iterates t + 1 - kRing .. t + k - kRing, read by
+// the walks of iterations t - kRing .. t + k - kRing; st_ waits for the walk
+// of every distinct group among them.  Deliberately not the slab's wait
+// (run_exact in slab.cpp waits for the last of these groups only): the waits
+// decide which barrier packets go into the stream, and each loop keeps its own.
+void Registration::wait_ring_walks(const std::vector<int> &group_of, int t, int k) {
+    for (int q = std::max(t - kRing, 0), last = -1; q <= t + k - kRing; q++)
+        if (group_of[q] != last) {
+            last = group_of[q];
+            OF2D_HIP(hipStreamWaitEvent(st_, ev_walk_[last % kExactEv], 0));
+        }
 }
 
 // One group's norms behind its steps (ev_step_[g] recorded on st_): the pass
@@ -623,11 +615,9 @@ int Registration::run_exact_pipelined_on(Level &L, int niter, const StepFn &step
                                          const StepFn3M &step3m) {
     const double npx = (double)L.dx * L.dy;
     last_err_.clear();
-    constexpr int R = kRing;
-    static_assert(R + 1 <= (int)(sizeof(L.est) / sizeof(L.est[0])), "ring");
-    for (int b = 1; b <= R; b++)
+    for (int b = 1; b <= kRing; b++)  // Level::est holds the ring (of2d_host.h)
         if (!L.est[b].p) L.est[b].alloc(L.dx, L.dy);
-    auto slot = [](int j) { return j == 0 ? 0 : 1 + (j - 1) % R; };
+    auto slot = [](int j) { return sched::Ring<kRing>::slot(j); };
     auto ev = [](hipEvent_t *e, int q) { return e[q % kExactEv]; };
     int *stop = reinterpret_cast<int *>(d_status_ + kStopWord);
     OF2D_HIP(hipMemsetAsync(stop, 0x7f, sizeof(int), st_));  // no break yet
@@ -638,7 +628,7 @@ int Registration::run_exact_pipelined_on(Level &L, int niter, const StepFn &step
     // profiles/r05q_ahead_ab.log)
     constexpr int kInFlight = 2;
     const int cb = chunk_set_ ? chunk_ : OF2D_SN_BLOCK;
-    const int blk = std::min(3 * ((cb + 2) / 3), 3 * (kExactEv / kInFlight - 4));
+    const int blk = sched::pipelined_block(cb, kExactEv, kInFlight);
     const int ring2 = kInFlight * blk;  // the sums' ring: the blocks in flight
     hs_.ensure(std::max(std::max(chunk_, 64), ring2));
     if (d_seq_.n < 2 * (size_t)ring2) d_seq_.alloc(2 * (size_t)ring2);
@@ -655,13 +645,7 @@ int Registration::run_exact_pipelined_on(Level &L, int niter, const StepFn &step
     // iterations [t, t + k) as group g (t a multiple of three)
     auto enqueue_group = [&](int t, int k) {
         for (int m = t; m < t + k; m++) grp_of[m] = g;
-        // iterates t + 1 .. t + k overwrite iterates t + 1 - R .. t + k - R,
-        // read by the walks of iterations t - R .. t + k - R
-        for (int q = std::max(t - R, 0), last = -1; q <= t + k - R; q++)
-            if (grp_of[q] != last) {
-                last = grp_of[q];
-                OF2D_HIP(hipStreamWaitEvent(st_, ev(ev_walk_, last), 0));
-            }
+        wait_ring_walks(grp_of, t, k);
         if (k == 3)
             step3m(L.est[slot(t)].p, L.est[slot(t + 1)].p, L.est[slot(t + 2)].p,
                    L.est[slot(t + 3)].p, t, -1, -1);
@@ -690,18 +674,17 @@ int Registration::run_exact_pipelined_on(Level &L, int niter, const StepFn &step
         enqueue_norms(B, L, g, npx, hs_.seqh + 2 * (size_t)(t % ring2));
         g++;
     };
-    const int ntrip = niter / 3 * 3;
-    const int nbt = (ntrip + blk - 1) / blk;  // blocks of triples
-    const int nblocks = nbt + (niter > ntrip ? 1 : 0);  // and the tail
-    auto lo_of = [&](int b) { return b < nbt ? b * blk : ntrip; };
-    auto hi_of = [&](int b) { return b < nbt ? std::min((b + 1) * blk, ntrip) : niter; };
+    const std::vector<sched::Block> blocks = sched::plan_blocks(niter, blk);
+    const int nblocks = (int)blocks.size();
+    const int nbt = nblocks - (nblocks > 0 && blocks.back().tail ? 1 : 0);  // blocks of triples
     std::vector<int> gbeg(nblocks + 1, 0);
     auto enqueue_block = [&](int b) {
+        const sched::Block &bl = blocks[b];
         gbeg[b] = g;
-        if (b < nbt)
-            for (int t = lo_of(b); t < hi_of(b); t += 3) enqueue_group(t, 3);
+        if (!bl.tail)
+            for (int t = bl.lo; t < bl.hi; t += 3) enqueue_group(t, 3);
         else
-            enqueue_group(ntrip, niter - ntrip);
+            enqueue_group(bl.lo, bl.hi - bl.lo);
         gbeg[b + 1] = g;
     };
     // the other streams' work before st_'s next (the next loop rewrites the
@@ -730,28 +713,15 @@ int Registration::run_exact_pipelined_on(Level &L, int niter, const StepFn &step
         // block b's sums: the last walk of each walk stream, then its decide
         for (int q = std::max(gbeg[b + 1] - kWalkers, gbeg[b]); q < gbeg[b + 1]; q++)
             OF2D_HIP(hipEventSynchronize(ev(ev_walk_, q)));
-        if (sn_debug) {
-            for (int t = lo_of(b); t < hi_of(b); t++) {
-                std::vector<int> h(kDbg);
-                OF2D_HIP(hipMemcpy(h.data(), dbg.p + kDbg * (size_t)(t % ring2), kDbg * sizeof(int),
-                                   hipMemcpyDeviceToHost));
-                std::fprintf(stderr,
-                             "seqnorm %dx%d it %d: resolves %d %d raw %d %d listed %d walk %d %d "
-                             "res %d made %d %d\n",
-                             L.dx, L.dy, t, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8],
-                             h[9]);
-            }
-        }
-        for (int t = lo_of(b); t < hi_of(b); t++) {
-            const float *sm = hs_.seqh + 2 * (size_t)(t % ring2);
-            const float err = logger_error(sm[0], sm[1], npx);
-            last_err_.push_back(err);
-            if (verbose_) print("Iteration: %d\tError:%.4f\n", t, (double)err);
-            if (err < 0.001f && t > 1) {  // ImageRegistrationOpticalFlow.cpp:131-134
-                finish(t);
-                final_buf = slot(t + 1);
-                return t + 1;
-            }
+        // a block's sums and counters are contiguous in their rings (a block
+        // starts on a multiple of blk, the tail on a multiple of three)
+        const int lo = blocks[b].lo, n = blocks[b].hi - lo, at = lo % ring2;
+        if (sn_debug) print_sn_debug(L, dbg.p + kDbg * (size_t)at, lo, 0, n);
+        const int tb = logger_break(hs_.seqh + 2 * (size_t)at, n, lo, npx, false);
+        if (tb >= 0) {
+            finish(lo + tb);
+            final_buf = slot(lo + tb + 1);
+            return lo + tb + 1;
         }
         if (b + 1 == nbt && nblocks > nbt) enqueue_block(nbt);  // the tail, after the rest
     }
@@ -763,12 +733,11 @@ int Registration::run_exact_pipelined_on(Level &L, int niter, const StepFn &step
 // Speculative chunked iteration loop shared by every solver whose iteration
 // reads motion_est from one buffer and writes the next iterate to another
 // (HS, Demons, Elastic, Curvature).  step(src, dst, partial) enqueues one
-// get_update plus the fused Logger partials (nb blocks x {diff, prev}).  With
-// step2 (HS), iterations run in pairs fused into one pass, alternating between
-// the two buffers other than the chunk's start buffer a, and a single step
-// fills an odd tail.  a is never written inside a chunk, so a break at
-// iteration t is replayed from it with single steps (iteration t reads
-// src_of(a, t) and writes dst_of(a, t)).
+// get_update plus the fused Logger partials (nb blocks x {diff, prev}).  The
+// chunk's launches are sched::plan_fused's: single steps, or with step2 / step3
+// (HS) fused pairs / triples.  The chunk's start buffer a is never written
+// inside a chunk, so a break at iteration t is replayed from it with single
+// steps (iteration t reads single_src(a, t) and writes single_dst(a, t)).
 int Registration::run_chunked(Level &L, int niter, int nb, const StepFn &step, int &final_buf,
                               const StepFn2 &step2, const StepFn3 &step3, const int *nblk,
                               const StepFn3M &step3m) {
@@ -781,45 +750,26 @@ int Registration::run_chunked(Level &L, int niter, int nb, const StepFn &step, i
     }
     const bool use2 = bool(step2), use3 = bool(step3);
     int a = 0, k0 = 0;
-    auto src_of = [](int a_, int t) { return t == 0 ? a_ : (t % 2 == 1 ? (a_ + 1) % 3 : (a_ + 2) % 3); };
-    auto dst_of = [](int a_, int t) { return t % 2 == 0 ? (a_ + 1) % 3 : (a_ + 2) % 3; };
     while (k0 < niter) {
         const int C = std::min(chunk_, niter - k0);
         auto part = [&](int t) { return d_partial_ + (size_t)t * nb * 2; };
-        int end = -1;  // pairs: the buffer holding the chunk's last iterate
+        const sched::FusedPlan plan = sched::plan_fused(a, C, use3, use2);
         PartialRuns runs;  // which kernel wrote how many block partials per row
-        if (use2) {
-            // fused launches (triples, then a pair / single tail) alternate
-            // between the two buffers other than a
-            auto other = [&](int b) { return b == (a + 1) % 3 ? (a + 2) % 3 : (a + 1) % 3; };
-            int cur = a, t = 0;
-            while (t < C) {
-                const int nxt = other(cur);
-                if (use3 && C - t >= 3) {
-                    step3(L.est[cur].p, L.est[nxt].p, part(t), part(t + 1), part(t + 2));
-                    runs.add(t, 3, nblk ? nblk[2] : nb);
-                    t += 3;
-                } else if (C - t >= 2) {
-                    step2(L.est[cur].p, L.est[nxt].p, part(t), part(t + 1));
-                    runs.add(t, 2, nblk ? nblk[1] : nb);
-                    t += 2;
-                } else {
-                    step(L.est[cur].p, L.est[nxt].p, part(t));
-                    runs.add(t, 1, nblk ? nblk[0] : nb);
-                    t += 1;
-                }
-                cur = nxt;
-            }
-            end = cur;
-        } else {
-            for (int t = 0; t < C; t++) step(L.est[src_of(a, t)].p, L.est[dst_of(a, t)].p, part(t));
-            runs.add(0, C, nblk ? nblk[0] : nb);
+        for (const sched::Launch &l : plan.launches) {
+            float2 *in = L.est[l.in].p, *out = L.est[l.out].p;
+            if (l.K == 3)
+                step3(in, out, part(l.t), part(l.t + 1), part(l.t + 2));
+            else if (l.K == 2)
+                step2(in, out, part(l.t), part(l.t + 1));
+            else
+                step(in, out, part(l.t));
+            runs.add(l.t, l.K, nblk ? nblk[l.K - 1] : nb);
         }
         if (fixed_) {
             // no break to decide: every chunk's sums stay on the device and are
             // read back once after the loop (no host round trip per chunk)
             runs.reduce(d_partial_, nb, d_all_.p + 2 * (size_t)k0, st_);
-            a = use2 ? end : dst_of(a, C - 1);
+            a = plan.end;
             k0 += C;
             continue;
         }
@@ -827,33 +777,23 @@ int Registration::run_chunked(Level &L, int niter, int nb, const StepFn &step, i
         OF2D_HIP(hipMemcpyAsync(hs_.sums, d_sums_, sizeof(double) * 2 * C, hipMemcpyDeviceToHost,
                                 st_));
         check_status();  // synchronises the stream; throws the reference's runtime_error
-        for (int t = 0; t < C; t++) {
-            const int k = k0 + t;
-            const float err = logger_error(hs_.sums[2 * t], hs_.sums[2 * t + 1], npx);
-            last_err_.push_back(err);
-            if (verbose_) print("Iteration: %d\tError:%.4f\n", k, (double)err);
-            if (!fixed_ && err < 0.001f && k > 1) {  // ImageRegistrationOpticalFlow.cpp:131-134
-                // dst(t) was overwritten by iteration t+2, or (pairs) never
-                // written: replay single steps from the chunk's start buffer a
-                if (use2 || t + 2 <= C - 1)
-                    for (int r = 0; r <= t; r++)
-                        step(L.est[src_of(a, r)].p, L.est[dst_of(a, r)].p, d_partial_);
-                final_buf = dst_of(a, t);
-                return k + 1;
-            }
+        const int t = logger_break(hs_.sums, C, k0, npx, false);
+        if (t >= 0) {
+            if (sched::fused_replay_needed(use2, t, C))
+                for (int r = 0; r <= t; r++)
+                    step(L.est[sched::single_src(a, r)].p, L.est[sched::single_dst(a, r)].p,
+                         d_partial_);
+            final_buf = sched::single_dst(a, t);
+            return k0 + t + 1;
         }
-        a = use2 ? end : dst_of(a, C - 1);
+        a = plan.end;
         k0 += C;
     }
     if (fixed_ && niter > 0) {
         OF2D_HIP(hipMemcpyAsync(hs_.sums, d_all_.p, sizeof(double) * 2 * niter,
                                 hipMemcpyDeviceToHost, st_));
         check_status();
-        for (int k = 0; k < niter; k++) {
-            const float err = logger_error(hs_.sums[2 * k], hs_.sums[2 * k + 1], npx);
-            last_err_.push_back(err);
-            if (verbose_) print("Iteration: %d\tError:%.4f\n", k, (double)err);
-        }
+        logger_break(hs_.sums, niter, 0, npx, true);
     }
     final_buf = a;
     return niter;

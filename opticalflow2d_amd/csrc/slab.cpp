@@ -460,10 +460,11 @@ bool exact_logger(const of2d_slab *s) {
 // The reference's Logger norms over the slabs (Motion.cpp:42-49 as
 // Logger::update_error takes them, Logger.cpp:32-51): one float running sum in
 // the global linear order, which crosses the slabs in rank order.  As on one
-// device (Registration::run_chunked_exact) every iterate stays in memory: the
-// iterations run in groups of up to three (a triple launch that stores all
-// three iterates, with its 3-line halo, or single steps with 1-line halos)
-// into a ring of kExR buffers, and each group's norms are one batch of
+// device every iterate stays in memory: the iterations run in groups of up to
+// three (a triple launch that stores all three iterates, with its 3-line halo,
+// or single steps with 1-line halos) into a ring of kExR buffers (the ring and
+// its replay rule: sched::Ring, iter_schedule.h, as Registration's loops with
+// kRing), and each group's norms are one batch of
 // seqnorm launches (seqnorm_kernels.hip) over this slab's rows:
 //   sn  the pass, the slab's fp64 totals, the prediction offsets chained in
 //       rank order (rank r receives r - 1's running fp64 totals and sends its
@@ -541,8 +542,21 @@ void exact_setup(of2d_slab *s) {
     }
 }
 
+// The status word after the stream's work so far (behind whatever the caller
+// has enqueued on s->st): the reference's divide-by-zero exception
+void check_status(of2d_slab *s) {
+    OF2D_HIP(hipMemcpyAsync(s->hs.status, s->d_status, sizeof(unsigned), hipMemcpyDeviceToHost,
+                            s->st));
+    OF2D_HIP(hipStreamSynchronize(s->st));
+    if (s->hs.status[0] & of2d::kStatusDivZero)
+        throw std::runtime_error("Divide by zero exception");
+}
+
 // in-process group: wait until rank r has enqueued group g's record of `done`
 void wait_rank(const std::atomic<long> &done, long g) { wait_count(done, g, "Logger chain"); }
+
+// the slabs print no line per iteration (sched::logger_break's callback)
+constexpr auto no_report = [](int, float) {};
 
 // The convergence-on run with the reference's Logger; *done = iterations
 int run_exact(of2d_slab *s, int niter) {
@@ -558,11 +572,7 @@ int run_exact(of2d_slab *s, int niter) {
     unsigned *range_flag = s->d_status + of2d::kRangeFlagWord;
     const float *ia = use_gi_exact(s) ? s->Imov.p : nullptr;
     for (bool &w : E.walked) w = false;  // a new loop: no profile yet
-    auto ring = [](int a, int t) {  // the (t mod kExR)-th buffer other than a
-        const int i = t % kExR;
-        return i < a ? i : i + 1;
-    };
-    auto src_of = [&](int a, int t) { return t == 0 ? a : ring(a, t - 1); };
+    using Rg = of2d::sched::Ring<kExR>;
     auto ev = [](hipEvent_t *e, long g) { return e[g % kExEv]; };
     auto part = [&](int t) { return s->d_partial + (size_t)t * nb * 2; };
     // one step from buffer `in` to `out` with its 1-line halo (chunk tails, replays)
@@ -582,30 +592,34 @@ int run_exact(of2d_slab *s, int niter) {
             g = E.gseq++;
             for (int m = t; m < t + k; m++) group_of[m] = g;
             // the buffers of iterates t .. t + k - 1 held iterates t - kExR ..,
-            // last read by the walk of iterate t + k - kExR's group
+            // last read by the walk of iterate t + k - kExR's group.
+            // Deliberately not Registration's wait (wait_ring_walks: every
+            // distinct group back to iteration t - R): this group only, whose
+            // walk is behind the earlier ones on the one walk stream; the
+            // waits decide which barrier packets go into the stream
             if (t + k - kExR >= 0)
                 OF2D_HIP(hipStreamWaitEvent(s->st, ev(E.ev_walk, group_of[t + k - kExR]), 0));
             if (k == 3) {
-                float2 *uin = exbuf(s, src_of(a, t)).p;
+                float2 *uin = exbuf(s, Rg::src(a, t)).p;
                 halo_exchange(s, uin, 3, s->st);
-                of2d::launch_hs_jacobi3(uin, exbuf(s, ring(a, t + 2)).p, s->dI.p, s->It.p, s->P,
+                of2d::launch_hs_jacobi3(uin, exbuf(s, Rg::ring(a, t + 2)).p, s->dI.p, s->It.p, s->P,
                                         s->dimx, s->nrows, s->rb, s->dimy, alphasq, -3,
                                         s->nrows + 3, part(t), part(t + 1), part(t + 2),
                                         s->d_status, range_flag, s->st, -1, -1, ia,
-                                        exbuf(s, ring(a, t)).p, exbuf(s, ring(a, t + 1)).p,
+                                        exbuf(s, Rg::ring(a, t)).p, exbuf(s, Rg::ring(a, t + 1)).p,
                                         nullptr, 0, slab_geometry(s).slots);
             } else {
-                for (int m = t; m < t + k; m++) single(src_of(a, m), ring(a, m), part(m));
+                for (int m = t; m < t + k; m++) single(Rg::src(a, m), Rg::ring(a, m), part(m));
             }
             OF2D_HIP(hipEventRecord(ev(E.ev_step, g), s->st));
             // the group's norms as one batch on this slab's rows
             of2d::SeqnormBatch B;
             B.K = k;
-            B.u[0] = exbuf(s, src_of(a, t)).p;
+            B.u[0] = exbuf(s, Rg::src(a, t)).p;
             const double *tot[3];
             for (int i = 0; i < k; i++) {
                 const int w = 3 * (int)(g & 1) + i;
-                B.u[i + 1] = exbuf(s, ring(a, t + i)).p;
+                B.u[i + 1] = exbuf(s, Rg::ring(a, t + i)).p;
                 B.ws[i] = E.ws[w].p;
                 B.use_profile[i] = E.walked[w];
                 E.walked[w] = true;
@@ -665,25 +679,16 @@ int run_exact(of2d_slab *s, int niter) {
         OF2D_HIP(hipMemcpy(s->hs.flt, last->ex->seq.p, sizeof(float) * 2 * C,
                            hipMemcpyDeviceToHost));
         if (grp) grp->barrier();  // read before the last rank's next chunk rewrites it
-        OF2D_HIP(hipMemcpyAsync(s->hs.status, s->d_status, sizeof(unsigned),
-                                hipMemcpyDeviceToHost, s->st));
-        OF2D_HIP(hipStreamSynchronize(s->st));
-        if (s->hs.status[0] & of2d::kStatusDivZero)
-            throw std::runtime_error("Divide by zero exception");
-        for (int t = 0; t < C; t++) {
-            const int kk = k0 + t;
-            const float e = of2d::logger_error(s->hs.flt[2 * t], s->hs.flt[2 * t + 1], npx);
-            s->errs.push_back(e);
-            if (e < 0.001f && kk > 1) {  // ImageRegistrationOpticalFlow.cpp:131-134
-                // iteration t's buffer was reused by iteration t + kExR: replay
-                // (every rank: the sums are global)
-                if (t + kExR <= C - 1)
-                    for (int q = 0; q <= t; q++) single(src_of(a, q), ring(a, q), s->d_partial);
-                s->fin = ring(a, t);
-                return kk + 1;
-            }
+        check_status(s);
+        const int t = of2d::sched::logger_break(s->hs.flt, C, k0, npx, false, s->errs, no_report);
+        if (t >= 0) {
+            // every rank replays: the sums are global
+            if (Rg::replay_needed(t, C))
+                for (int q = 0; q <= t; q++) single(Rg::src(a, q), Rg::ring(a, q), s->d_partial);
+            s->fin = Rg::ring(a, t);
+            return k0 + t + 1;
         }
-        a = ring(a, C - 1);
+        a = Rg::ring(a, C - 1);
         k0 += C;
     }
     s->fin = a;
@@ -929,15 +934,14 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
         // partial rows long enough for every kernel; each row is reduced over
         // the blocks of the kernel that wrote it
         const int nb = G.nb;
-        const int n1 = of2d::hs_nblocks(s->P, s->nrows), n2 = of2d::hs2_nblocks(s->dimx, s->nrows),
-                  n3 = G.n3;
+        const int nblk[3] = {of2d::hs_nblocks(s->P, s->nrows),  // single, pair, triple
+                             of2d::hs2_nblocks(s->dimx, s->nrows), G.n3};
         const double npx = (double)s->dimx * s->dimy;
         unsigned *range_flag = s->d_status + of2d::kRangeFlagWord;
         // Iaux == Imov (zero initial motion); its three ghost j-lines hold the
         // neighbours' image rows, as the gradients of the halo rows need
         const float *ia = use_gi(s) ? s->Imov.p : nullptr;
-        auto src_of = [](int a, int t) { return t == 0 ? a : (t % 2 == 1 ? (a + 1) % 3 : (a + 2) % 3); };
-        auto dst_of = [](int a, int t) { return t % 2 == 0 ? (a + 1) % 3 : (a + 2) % 3; };
+        namespace sched = of2d::sched;
         // st runs after the latest edge launches / comm_st after the latest st
         // work.  Only split launches use comm_st: without them a wait and a
         // record around every launch would put two barrier packets between
@@ -1008,9 +1012,6 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
                                    s->rb, s->dimy, alphasq, partial, s->d_status, s->st);
             mark_st();
         };
-        auto step = [&](int a, int t, double *partial) {
-            single(src_of(a, t), dst_of(a, t), partial);
-        };
         if (!s->P) throw std::invalid_argument("slab: set_images first");
         if (!s->divzero_voted) {
             s->divzero = any_rank(s, s->divzero_local);
@@ -1046,40 +1047,30 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
         while (k0 < niter && done < 0) {
             const int C = std::min(fixed_iters ? s->chunk_fixed : s->chunk, niter - k0);
             auto part = [&](int t) { return s->d_partial + (size_t)t * nb * 2; };
-            // triples (then a pair / single tail) alternate between the two
-            // buffers other than the chunk's start buffer a, which stays intact
-            // for a replay
+            // the slab always fuses: triples, then a pair / single tail
+            // (sched::plan_fused); the chunk's start buffer a stays intact for
+            // a replay
+            const sched::FusedPlan plan = sched::plan_fused(a, C, true, true);
             of2d::PartialRuns runs;
-            auto other = [&](int b) { return b == (a + 1) % 3 ? (a + 2) % 3 : (a + 1) % 3; };
-            int cur = a, tp = 0;
             // time this chunk's triples (the first kTriTimed chunks of the run)
             const bool timed = C >= 3 && s->tri_pairs < of2d_slab::kTriTimed;
             if (timed) {
                 join_st();
                 OF2D_HIP(hipEventRecord(s->ev_tri[2 * s->tri_pairs], s->st));
             }
-            while (tp < C) {
-                const int nxt = other(cur);
-                if (C - tp >= 3) {
-                    fused(3, cur, nxt, part(tp), part(tp + 1), part(tp + 2));
-                    runs.add(tp, 3, n3);
-                    tp += 3;
-                    if (timed && C - tp < 3) {  // the chunk's last triple
-                        join_st();
-                        OF2D_HIP(hipEventRecord(s->ev_tri[2 * s->tri_pairs + 1], s->st));
-                        s->tri_pairs++;
-                        s->tri_launches += C / 3;
-                    }
-                } else if (C - tp == 2) {
-                    fused(2, cur, nxt, part(tp), part(tp + 1), nullptr);
-                    runs.add(tp, 2, n2);
-                    tp += 2;
-                } else {
-                    single(cur, nxt, part(tp));
-                    runs.add(tp, 1, n1);
-                    tp += 1;
+            for (const sched::Launch &l : plan.launches) {
+                if (l.K == 1)
+                    single(l.in, l.out, part(l.t));
+                else
+                    fused(l.K, l.in, l.out, part(l.t), part(l.t + 1),
+                          l.K == 3 ? part(l.t + 2) : nullptr);
+                runs.add(l.t, l.K, nblk[l.K - 1]);
+                if (timed && l.K == 3 && C - (l.t + 3) < 3) {  // the chunk's last triple
+                    join_st();
+                    OF2D_HIP(hipEventRecord(s->ev_tri[2 * s->tri_pairs + 1], s->st));
+                    s->tri_pairs++;
+                    s->tri_launches += C / 3;
                 }
-                cur = nxt;
             }
             if (fixed_iters) {
                 // no break to decide: keep every chunk's sums on the device and
@@ -1088,7 +1079,7 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
                 join_st();  // the edge launches' partials
                 runs.reduce(s->d_partial, nb, sums, s->st);
                 allreduce_sums(s, sums, 2 * (size_t)C, s->st);
-                a = cur;
+                a = plan.end;
                 k0 += C;
                 continue;
             }
@@ -1097,27 +1088,19 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
             allreduce_sums(s, s->d_sums, 2 * (size_t)C, s->st);
             OF2D_HIP(hipMemcpyAsync(s->hs.sums, s->d_sums, sizeof(double) * 2 * C,
                                     hipMemcpyDeviceToHost, s->st));
-            OF2D_HIP(hipMemcpyAsync(s->hs.status, s->d_status, sizeof(unsigned),
-                                    hipMemcpyDeviceToHost, s->st));
-            OF2D_HIP(hipStreamSynchronize(s->st));
-            if (s->hs.status[0] & of2d::kStatusDivZero)
-                throw std::runtime_error("Divide by zero exception");
-            for (int t = 0; t < C; t++) {
-                const int k = k0 + t;
-                const float e = of2d::logger_error(s->hs.sums[2 * t], s->hs.sums[2 * t + 1], npx);
-                s->errs.push_back(e);
-                if (!fixed_iters && e < 0.001f && k > 1) {
-                    // replay single steps from the chunk's start buffer up to the
-                    // break (pairs never wrote iteration t's own buffer; all ranks
-                    // agree: the sums are global)
-                    for (int r = 0; r <= t; r++) step(a, r, s->d_partial);
-                    s->fin = dst_of(a, t);
-                    done = k + 1;
-                    break;
-                }
-            }
-            if (done < 0) {
-                a = cur;
+            check_status(s);
+            const int t = sched::logger_break(s->hs.sums, C, k0, npx, false, s->errs, no_report);
+            if (t >= 0) {
+                // replay single steps from the chunk's start buffer up to the
+                // break (fused launches never wrote iteration t's own buffer:
+                // the pairs case of the rule; all ranks agree: the sums are global)
+                if (sched::fused_replay_needed(true, t, C))
+                    for (int r = 0; r <= t; r++)
+                        single(sched::single_src(a, r), sched::single_dst(a, r), s->d_partial);
+                s->fin = sched::single_dst(a, t);
+                done = k0 + t + 1;
+            } else {
+                a = plan.end;
                 k0 += C;
             }
         }
@@ -1129,14 +1112,8 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
         if (fixed_iters && niter > 0) {
             OF2D_HIP(hipMemcpyAsync(s->hs.sums, s->d_all, sizeof(double) * 2 * niter,
                                     hipMemcpyDeviceToHost, s->st));
-            OF2D_HIP(hipMemcpyAsync(s->hs.status, s->d_status, sizeof(unsigned),
-                                    hipMemcpyDeviceToHost, s->st));
-            OF2D_HIP(hipStreamSynchronize(s->st));
-            if (s->hs.status[0] & of2d::kStatusDivZero)
-                throw std::runtime_error("Divide by zero exception");
-            for (int t = 0; t < niter; t++)
-                s->errs.push_back(
-                    of2d::logger_error(s->hs.sums[2 * t], s->hs.sums[2 * t + 1], npx));
+            check_status(s);
+            sched::logger_break(s->hs.sums, niter, 0, npx, true, s->errs, no_report);
         }
         OF2D_HIP(hipEventRecord(s->ev1, s->st));
         // ImageRegistrationOpticalFlow.cpp:141 motion_est->reset() after the

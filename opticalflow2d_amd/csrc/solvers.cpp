@@ -279,7 +279,6 @@ int Registration::loop_elastic(Level &L, int niter, int &final_buf) {
     const float mu = params_[0], lambda = params_[1];
     const float omega = params_.size() == 3 ? params_[2] : 0.66f;  // OpticalFlowElastic.h:9
     float2 *est = L.est[0].p;
-    float2 *snap = L.est[1].p;
     float2 *prev = L.tmp.p;
     L.tmp.zero(st_);
     const int nb = increment_nblocks(L.dx, L.dy);
@@ -320,25 +319,19 @@ int Registration::loop_elastic(Level &L, int niter, int &final_buf) {
                                     hipMemcpyDeviceToHost, st_));
         }
         check_status();
-        for (int t = 0; t < C; t++) {
-            const int k = k0 + t;
-            const float err = exact ? logger_error(hs_.flt[2 * t], hs_.flt[2 * t + 1], npx)
-                                    : logger_error(hs_.sums[2 * t], hs_.sums[2 * t + 1], npx);
-            last_err_.push_back(err);
-            if (verbose_) print("Iteration: %d\tError:%.4f\n", k, (double)err);
-            if (!fixed_ && err < 0.001f && k > 1) {
-                if (t < C - 1) {  // replay up to the break from the chunk's start state
-                    OF2D_HIP(hipMemcpyAsync(L.est[0].base, L.est[1].base, L.est[0].bytes(),
-                                            hipMemcpyDeviceToDevice, st_));
-                    for (int r = 0; r <= t; r++) {
-                        update();
-                        launch_logger(L.vb.p, est, prev, L.dx, L.dy, L.P, d_partial_, st_);
-                    }
-                    check_status();
+        const int t = exact ? logger_break(hs_.flt, C, k0, npx, fixed_)
+                            : logger_break(hs_.sums, C, k0, npx, fixed_);
+        if (t >= 0) {
+            if (t < C - 1) {  // replay up to the break from the chunk's start state
+                OF2D_HIP(hipMemcpyAsync(L.est[0].base, L.est[1].base, L.est[0].bytes(),
+                                        hipMemcpyDeviceToDevice, st_));
+                for (int r = 0; r <= t; r++) {
+                    update();
+                    launch_logger(L.vb.p, est, prev, L.dx, L.dy, L.P, d_partial_, st_);
                 }
-                (void)snap;
-                return k + 1;
+                check_status();
             }
+            return k0 + t + 1;
         }
         k0 += C;
     }
