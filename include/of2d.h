@@ -600,6 +600,78 @@ int of2d_batch_destroy(of2d_batch *b);
 /* b == NULL: the message of the last refused of2d_batch_create of this thread */
 const char *of2d_batch_last_error(const of2d_batch *b);
 
+/* ---- device-resident I/O: images in, motion and warped images out, as
+ * arrays that already live on the context's device ----
+ * An of2d_darray describes a strided device array of float or double by its
+ * element strides on the axes pair, x, y, component.  An entry looks only at
+ * the axes its array has (an image of a context: x and y; a stack of a batch:
+ * pair, x, y; a motion: also the component, x then y).  Pixel (i, j) of pair
+ * k, component c, is ptr[k*stride[0] + i*stride[1] + j*stride[2] +
+ * c*stride[3]]; every offset is computed in 64 bits.  The boundary layout of
+ * the host entries is stride = {dimx*dimy, 1, dimx, 0} for an image and
+ * {2*dimx*dimy, 1, dimx, dimx*dimy} for a motion; a contiguous [dimx][dimy]
+ * array (C order) is {dimx*dimy, dimy, 1, 0}, a [dimx][dimy][2] motion
+ * {2*dimx*dimy, 2*dimy, 2, 1}.  Both are moved with coalesced accesses on both
+ * sides (the second through a transposing tile); any other strides are
+ * correct.  An input may repeat elements (a stride of 0 reads one image for
+ * every pair); an output's elements must be distinct.
+ *
+ * Values: an input's (float) in[...] is Image::set_image's conversion for
+ * double and the value itself for float; an output receives the field's float
+ * or its (double) widening.  So a double array gives and receives exactly what
+ * the host entries do, bit for bit.
+ *
+ * Stream contract.  `stream` is the caller's hipStream_t (NULL: the null
+ * stream).  The library works on non-blocking streams of its own, so on entry
+ * it records an event on `stream` and makes its stream wait for it: work the
+ * caller enqueued on `stream` before the call (filling an input, the last
+ * reader of an output) is finished before the library touches the arrays.
+ * After its last kernel that touches the caller's arrays it records an event
+ * on its stream and makes `stream` wait for it: the caller may reuse or free
+ * the arrays in stream order as soon as the call returns, and work enqueued on
+ * `stream` afterwards sees the results without a host synchronise.  The calls
+ * may still synchronise internally where their host counterparts do
+ * (of2d_set_images_device and of2d_warp_device wait for their own stream), and
+ * they are not for use while `stream` is being captured into a graph.
+ *
+ * Refused with OF2D_ERR_INVALID_ARGUMENT and a message, before any device
+ * work: a NULL of2d_darray or ptr, a dtype other than OF2D_F32 / OF2D_F64, a
+ * negative stride, and for an output a zero stride on an axis of extent > 1.
+ * Once the device is known (first use), a ptr that hipPointerGetAttributes
+ * does not place on the context's device is refused the same way. */
+#define OF2D_F32 0
+#define OF2D_F64 1
+typedef struct of2d_darray {
+    void *ptr;           /* device pointer on the context's device */
+    int dtype;           /* OF2D_F32 | OF2D_F64 */
+    long long stride[4]; /* element strides: pair, x, y, component (unused ones ignored) */
+} of2d_darray;
+/* of2d_set_images, of2d_get_motion, of2d_warp on device arrays; everything
+ * after the level-0 images are in place is the host entries' code */
+int of2d_set_images_device(of2d_ctx *ctx, const of2d_darray *Iref, const of2d_darray *Imov,
+                           void *stream);
+int of2d_get_motion_device(of2d_ctx *ctx, const of2d_darray *out, void *stream);
+int of2d_warp_device(of2d_ctx *ctx, const of2d_darray *Imov, const of2d_darray *out,
+                     void *stream);
+/* of2d_batch_set_images, _get_motion, _warp on device arrays: one launch moves
+ * all nbatch pairs, without the host entries' staging rounds.  With shared_ref
+ * Iref is one image and its pair stride is ignored. */
+int of2d_batch_set_images_device(of2d_batch *b, const of2d_darray *Iref, int shared_ref,
+                                 const of2d_darray *Imov, void *stream);
+int of2d_batch_get_motion_device(of2d_batch *b, const of2d_darray *out, void *stream);
+int of2d_batch_warp_device(of2d_batch *b, const of2d_darray *Imov, const of2d_darray *out,
+                           void *stream);
+/* One launch each of the kernels behind them, on the null stream (tests):
+ * pack `in` into npairs pitched fields and download them dense, float
+ * [npairs][dimy][dimx]; upload dense fields (m_host interleaved x, y as the
+ * other primitives' motion) and unpack them into `out`.  Refusals as above,
+ * with the message in of2d_gateway_last_error. */
+int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host);
+int of2d_prim_unpack_image(const float *in_host, int npairs, int dimx, int dimy,
+                           const of2d_darray *out);
+int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
+                            const of2d_darray *out);
+
 /* ---- library info ---- */
 const char *of2d_version(void);
 int of2d_device_count(int *count);

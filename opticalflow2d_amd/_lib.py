@@ -39,6 +39,17 @@ class _f32p_opt(_f32p):
 
 PRINT_FN = C.CFUNCTYPE(None, C.c_char_p, C.c_void_p)
 
+OF2D_F32 = 0
+OF2D_F64 = 1
+
+
+class DArray(C.Structure):
+    """``of2d_darray``: a strided device array (include/of2d.h)."""
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("stride", C.c_longlong * 4)]
+
+
+_darr = C.POINTER(DArray)
+
 # name -> (restype, argtypes); the list IS the exported surface of include/of2d.h
 SIGNATURES = {
     "of2d_set_print_hook": (None, [PRINT_FN, C.c_void_p]),
@@ -164,6 +175,15 @@ SIGNATURES = {
     "of2d_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "of2d_batch_destroy": (C.c_int, [C.c_void_p]),
     "of2d_batch_last_error": (C.c_char_p, [C.c_void_p]),
+    "of2d_set_images_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
+    "of2d_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_batch_set_images_device": (C.c_int, [C.c_void_p, _darr, C.c_int, _darr, C.c_void_p]),
+    "of2d_batch_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
+    "of2d_batch_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_prim_pack_image": (C.c_int, [_darr, C.c_int, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_unpack_image": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
+    "of2d_prim_unpack_motion": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
     "of2d_version": (C.c_char_p, []),
     "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }

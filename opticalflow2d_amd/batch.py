@@ -14,7 +14,7 @@ from typing import Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 from ._lib import check
 
 #: most pixels a batch image may have (include/of2d.h OF2D_BATCH_MAXPX)
@@ -48,6 +48,7 @@ class BatchRegistration:
                                  int(p.size), self.nrefine)
         check(st, L.of2d_batch_last_error(None).decode())
         self._h = h
+        self._device = None  # option "device": where motion_device allocates
         self.loops = (self.nscales + 1) * max(self.nrefine, 0)
         self._maxn = max(int(nit.max()), 1)  # a loop records at most niter errors
         for k, v in options.items():
@@ -58,6 +59,8 @@ class BatchRegistration:
 
     def set_option(self, key: str, value: float) -> None:
         self._chk(_lib.lib().of2d_batch_set_option(self._h, key.encode(), float(value)))
+        if key == "device":
+            self._device = int(value)
 
     def _stack(self, a, name: str) -> np.ndarray:
         """``[nbatch, dimx, dimy]`` -> the boundary layout, x fastest per image."""
@@ -69,7 +72,26 @@ class BatchRegistration:
 
     def register(self, Iref, Imov) -> None:
         """``Iref``: ``[dimx, dimy]`` (one reference shared by every pair) or
-        ``[nbatch, dimx, dimy]``; ``Imov``: ``[nbatch, dimx, dimy]``."""
+        ``[nbatch, dimx, dimy]``; ``Imov``: ``[nbatch, dimx, dimy]``.  Two
+        torch CUDA tensors (float32 or float64, any strides) are read where
+        they are, in the order of their device's current stream
+        (of2d_batch_set_images_device); mixing one with a host array is a
+        ``ValueError``."""
+        if _device.all_cuda(Iref=Iref, Imov=Imov):
+            stack = (self.nbatch, self.dimx, self.dimy)
+            shared = Iref.dim() == 2
+            if shared:
+                r = _device.darray(Iref, stack[1:], (1, 2), "Iref")
+            elif tuple(Iref.shape) == stack:
+                r = _device.darray(Iref, stack, (0, 1, 2), "Iref")
+            else:
+                raise ValueError(f"Iref is {tuple(Iref.shape)}, expected {stack[1:]} or {stack}")
+            m = _device.darray(Imov, stack, (0, 1, 2), "Imov")
+            L = _lib.lib()
+            self._chk(L.of2d_batch_set_images_device(self._h, C.byref(r), int(shared), C.byref(m),
+                                                     _device.stream_of(Imov)))
+            self._chk(L.of2d_batch_estimate(self._h))
+            return
         r = np.asarray(Iref, dtype=np.float64)
         shared = r.ndim == 2
         if shared:
@@ -90,8 +112,32 @@ class BatchRegistration:
         return np.ascontiguousarray(
             out.reshape(self.nbatch, 2, self.dimy, self.dimx).transpose(0, 3, 2, 1))
 
-    def warp(self, Imov) -> np.ndarray:
-        """Pair k's image warped by pair k's motion, ``[nbatch, dimx, dimy]``."""
+    def motion_device(self, dtype=None, out=None):
+        """The motion as a CUDA tensor ``[nbatch, dimx, dimy, 2]`` of ``dtype``
+        (``torch.float32``, the default, or ``torch.float64``), or written into
+        ``out`` (a CUDA tensor of that shape, any strides), in the order of the
+        device's current stream (of2d_batch_get_motion_device)."""
+        shape = (self.nbatch, self.dimx, self.dimy, 2)
+        out = _device.output(out, shape, dtype, self._device)
+        a = _device.darray(out, shape, (0, 1, 2, 3), "out")
+        self._chk(_lib.lib().of2d_batch_get_motion_device(self._h, C.byref(a),
+                                                          _device.stream_of(out)))
+        return out
+
+    def warp(self, Imov, out=None):
+        """Pair k's image warped by pair k's motion, ``[nbatch, dimx, dimy]``.
+        A CUDA tensor gives a CUDA tensor of its dtype, or ``out``
+        (of2d_batch_warp_device)."""
+        if _device.all_cuda(**({"Imov": Imov} if out is None else {"Imov": Imov, "out": out})):
+            shape, axes = (self.nbatch, self.dimx, self.dimy), (0, 1, 2)
+            m = _device.darray(Imov, shape, axes, "Imov")
+            out = _device.output(out, shape, Imov.dtype, Imov.device)
+            o = _device.darray(out, shape, axes, "out")
+            self._chk(_lib.lib().of2d_batch_warp_device(self._h, C.byref(m), C.byref(o),
+                                                        _device.stream_of(Imov)))
+            return out
+        if out is not None:
+            raise ValueError("out= is for CUDA tensors")
         m = self._stack(Imov, "Imov")
         out = np.zeros_like(m)
         self._chk(_lib.lib().of2d_batch_warp(self._h, m, out))

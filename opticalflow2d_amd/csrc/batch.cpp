@@ -68,6 +68,10 @@ void Batch::release_device() {
     for (hipEvent_t e : ev_)
         if (e) (void)hipEventDestroy(e);
     ev_.clear();
+    for (hipEvent_t &e : ev_io_) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
     if (st_) (void)hipStreamDestroy(st_);
     st_ = nullptr;
     ref_pairs_ = 0;
@@ -134,6 +138,7 @@ void Batch::allocate_device() {
     OF2D_HIP(hipMemset(d_iters_, 0, sizeof(int) * std::max<size_t>(1, (size_t)B_ * nloops_)));
     ev_.assign(2 * (size_t)nloops_, nullptr);
     for (hipEvent_t &e : ev_) OF2D_HIP(hipEventCreate(&e));
+    for (hipEvent_t &e : ev_io_) OF2D_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     // the null-stream memsets are unordered with the non-blocking stream
     OF2D_HIP(hipDeviceSynchronize());
 }
@@ -168,13 +173,44 @@ void Batch::set_images(const double *ref, bool shared_ref, const double *mov) {
             // the staging buffer is reused by the next round
             OF2D_HIP(hipStreamSynchronize(st_));
         }
-        for (int s = nscales_; s >= 1; s--) {
-            BLevel &L = lv_[s];
-            launch_downsample_image((which ? L0.Imov : L0.Iref).p, L0.stride, L0.dx, L0.dy, L0.P,
-                                    (which ? L.Imov : L.Iref).p, L.stride, L.dx, L.dy, L.P, npairs,
-                                    st_);
-        }
+        downsample_levels(which, npairs);
     }
+    images_in_place(shared_ref);
+}
+
+// the same from the caller's device arrays (include/of2d.h, the stream
+// contract): one pack launch per stack, no staging
+void Batch::set_images_device(const DArrayView &ref, bool shared_ref, const DArrayView &mov,
+                              hipStream_t user) {
+    DeviceScope scope;
+    ensure_device();
+    check_device_pointer(ref.ptr, home_, "of2d_batch_set_images_device: Iref");
+    check_device_pointer(mov.ptr, home_, "of2d_batch_set_images_device: Imov");
+    const int nref = shared_ref ? 1 : B_;
+    ensure_reference(nref);
+    BLevel &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_image(ref, nref, dimx_, dimy_, L0.Iref.p, L0.stride, L0.P, st_);
+    launch_pack_image(mov, B_, dimx_, dimy_, L0.Imov.p, L0.stride, L0.P, st_);
+    stream_after(user, st_, ev_io_[1]);  // the caller's arrays are free again
+    downsample_levels(0, nref);
+    downsample_levels(1, B_);
+    images_in_place(shared_ref);
+}
+
+// the pyramid of the reference (0) or moving (1) images below level 0
+void Batch::downsample_levels(int which, int npairs) {
+    BLevel &L0 = lv_[0];
+    for (int s = nscales_; s >= 1; s--) {
+        BLevel &L = lv_[s];
+        launch_downsample_image((which ? L0.Imov : L0.Iref).p, L0.stride, L0.dx, L0.dy, L0.P,
+                                (which ? L.Imov : L.Iref).p, L.stride, L.dx, L.dy, L.P, npairs,
+                                st_);
+    }
+}
+
+// what set_images does once both pyramids are enqueued
+void Batch::images_in_place(bool shared_ref) {
     OF2D_HIP(hipStreamSynchronize(st_));
     shared_ = shared_ref;
     have_images_ = true;
@@ -312,6 +348,31 @@ void Batch::warp(const double *in, double *out) {
                                 hipMemcpyDeviceToHost, st_));
         OF2D_HIP(hipStreamSynchronize(st_));
     }
+}
+
+void Batch::get_motion_device(const DArrayView &out, hipStream_t user) {
+    DeviceScope scope;
+    ensure_device();
+    check_device_pointer(out.ptr, home_, "of2d_batch_get_motion_device: out");
+    BLevel &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_unpack_motion(L0.motion[L0.mcur].p, L0.stride, L0.P, B_, dimx_, dimy_, out, st_);
+    stream_after(user, st_, ev_io_[1]);
+}
+
+// as warp: level 0's Iaux and It hold the images
+void Batch::warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user) {
+    DeviceScope scope;
+    ensure_device();
+    check_device_pointer(in.ptr, home_, "of2d_batch_warp_device: Imov");
+    check_device_pointer(out.ptr, home_, "of2d_batch_warp_device: out");
+    BLevel &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_image(in, B_, dimx_, dimy_, L0.Iaux.p, L0.stride, L0.P, st_);
+    launch_warp(L0.Iaux.p, L0.motion[L0.mcur].p, L0.It.p, L0.stride, dimx_, dimy_, L0.P, B_,
+                nullptr, st_);
+    launch_unpack_image(L0.It.p, L0.stride, L0.P, B_, dimx_, dimy_, out, st_);
+    stream_after(user, st_, ev_io_[1]);
 }
 
 std::vector<float> Batch::last_errors(int pair) const {

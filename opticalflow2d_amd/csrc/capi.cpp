@@ -1514,3 +1514,197 @@ const char *of2d_batch_last_error(const of2d_batch *b) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ device-resident I/O
+namespace {
+// the axes of a call's array: pair, x, y, component (0: the axis is not used)
+struct Extents {
+    int n[4];
+};
+// "" or why the array is refused; no device work.  Unused axes' strides are
+// not looked at.
+std::string darray_refusal(const of2d_darray *a, const char *name, bool output, const Extents &e) {
+    const std::string n(name);
+    if (!a) return n + " is NULL";
+    if (!a->ptr) return n + ".ptr is NULL";
+    if (a->dtype != OF2D_F32 && a->dtype != OF2D_F64)
+        return n + ".dtype is neither OF2D_F32 nor OF2D_F64";
+    for (int k = 0; k < 4; k++) {
+        if (e.n[k] <= 0) continue;
+        if (a->stride[k] < 0) return n + " has a negative stride";
+        if (output && a->stride[k] == 0 && e.n[k] > 1)
+            return n + " has a zero stride on an axis of extent > 1";
+    }
+    return "";
+}
+of2d::DArrayView view_of(const of2d_darray *a, const Extents &e) {
+    of2d::DArrayView v;
+    v.ptr = a->ptr;
+    v.f64 = a->dtype == OF2D_F64;
+    v.sp = e.n[0] > 0 ? a->stride[0] : 0;
+    v.sx = a->stride[1];
+    v.sy = a->stride[2];
+    v.sc = e.n[3] > 0 ? a->stride[3] : 0;
+    return v;
+}
+// an entry's arrays, checked in order; the first refusal is the message
+struct DArrayArg {
+    const of2d_darray *a;
+    const char *name;
+    bool output;
+    Extents e;
+};
+std::string first_refusal(const char *fn, std::initializer_list<DArrayArg> args) {
+    for (const DArrayArg &g : args) {
+        const std::string why = darray_refusal(g.a, g.name, g.output, g.e);
+        if (!why.empty()) return std::string(fn) + ": " + why;
+    }
+    return "";
+}
+template <class F>
+int device_io(of2d_ctx *ctx, const char *fn, std::initializer_list<DArrayArg> args, F &&f) {
+    if (!ctx) return refuse(nullptr, (std::string(fn) + ": ctx is NULL").c_str());
+    const std::string why = first_refusal(fn, args);
+    if (!why.empty()) return refuse(ctx, why.c_str());
+    return guarded(ctx->err, f);
+}
+template <class F>
+int device_io(of2d_batch *b, const char *fn, std::initializer_list<DArrayArg> args, F &&f) {
+    if (!b) return refuse(nullptr, (std::string(fn) + ": b is NULL").c_str());
+    const std::string why = first_refusal(fn, args);
+    if (!why.empty()) {
+        b->err = why;
+        return OF2D_ERR_INVALID_ARGUMENT;
+    }
+    return guarded(b->err, f);
+}
+// dense host fields <-> npairs pitched fields (the primitives below)
+template <class T>
+void upload_pairs(of2d::batch::BField<T> &f, const float *host, int npairs, int dimx, int dimy) {
+    f.alloc(dimx, dimy, npairs);
+    const size_t row = (size_t)dimx * sizeof(T), P = (size_t)of2d::pitch_for(dimx);
+    const long stride = of2d::batch::pair_stride(dimx, dimy);
+    const size_t per = (size_t)dimx * dimy * (sizeof(T) / sizeof(float));
+    for (int k = 0; host && k < npairs; k++)
+        OF2D_HIP(hipMemcpy2D(f.p + k * stride, P * sizeof(T), host + k * per, row, row, dimy,
+                             hipMemcpyHostToDevice));
+}
+}  // namespace
+
+extern "C" {
+
+int of2d_set_images_device(of2d_ctx *ctx, const of2d_darray *Iref, const of2d_darray *Imov,
+                           void *stream) {
+    const Extents e = {{0, ctx ? ctx->reg->dimx() : 0, ctx ? ctx->reg->dimy() : 0, 0}};
+    return device_io(ctx, "of2d_set_images_device", {{Iref, "Iref", false, e}, {Imov, "Imov", false, e}},
+                     [&] {
+                         ctx->reg->set_images_device(view_of(Iref, e), view_of(Imov, e),
+                                                     static_cast<hipStream_t>(stream));
+                     });
+}
+
+int of2d_get_motion_device(of2d_ctx *ctx, const of2d_darray *out, void *stream) {
+    const Extents e = {{0, ctx ? ctx->reg->dimx() : 0, ctx ? ctx->reg->dimy() : 0, 2}};
+    return device_io(ctx, "of2d_get_motion_device", {{out, "out", true, e}}, [&] {
+        ctx->reg->get_motion_device(view_of(out, e), static_cast<hipStream_t>(stream));
+    });
+}
+
+int of2d_warp_device(of2d_ctx *ctx, const of2d_darray *Imov, const of2d_darray *out,
+                     void *stream) {
+    const Extents e = {{0, ctx ? ctx->reg->dimx() : 0, ctx ? ctx->reg->dimy() : 0, 0}};
+    return device_io(ctx, "of2d_warp_device", {{Imov, "Imov", false, e}, {out, "out", true, e}},
+                     [&] {
+                         ctx->reg->warp_device(view_of(Imov, e), view_of(out, e),
+                                               static_cast<hipStream_t>(stream));
+                     });
+}
+
+int of2d_batch_set_images_device(of2d_batch *b, const of2d_darray *Iref, int shared_ref,
+                                 const of2d_darray *Imov, void *stream) {
+    const int dx = b ? b->b->dimx() : 0, dy = b ? b->b->dimy() : 0, nb = b ? b->b->nbatch() : 0;
+    const Extents er = {{shared_ref ? 0 : nb, dx, dy, 0}}, em = {{nb, dx, dy, 0}};
+    return device_io(b, "of2d_batch_set_images_device",
+                     {{Iref, "Iref", false, er}, {Imov, "Imov", false, em}}, [&] {
+                         b->b->set_images_device(view_of(Iref, er), shared_ref != 0,
+                                                 view_of(Imov, em),
+                                                 static_cast<hipStream_t>(stream));
+                     });
+}
+
+int of2d_batch_get_motion_device(of2d_batch *b, const of2d_darray *out, void *stream) {
+    const Extents e = {{b ? b->b->nbatch() : 0, b ? b->b->dimx() : 0, b ? b->b->dimy() : 0, 2}};
+    return device_io(b, "of2d_batch_get_motion_device", {{out, "out", true, e}}, [&] {
+        b->b->get_motion_device(view_of(out, e), static_cast<hipStream_t>(stream));
+    });
+}
+
+int of2d_batch_warp_device(of2d_batch *b, const of2d_darray *Imov, const of2d_darray *out,
+                           void *stream) {
+    const Extents e = {{b ? b->b->nbatch() : 0, b ? b->b->dimx() : 0, b ? b->b->dimy() : 0, 0}};
+    return device_io(b, "of2d_batch_warp_device",
+                     {{Imov, "Imov", false, e}, {out, "out", true, e}}, [&] {
+                         b->b->warp_device(view_of(Imov, e), view_of(out, e),
+                                           static_cast<hipStream_t>(stream));
+                     });
+}
+
+// ---- one launch each of io_kernels.hip, on the null stream
+int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host) {
+    const Extents e = {{npairs, dimx, dimy, 0}};
+    const bool ok = out_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
+                    dimy > 0;
+    const std::string why =
+        ok ? first_refusal("of2d_prim_pack_image", {{in, "in", false, e}})
+           : std::string("of2d_prim_pack_image: out_host is NULL or a size is out of range");
+    if (!why.empty()) return refuse(nullptr, why.c_str());
+    return prim(true, [&] {
+        of2d::batch::BField<float> f;
+        upload_pairs(f, nullptr, npairs, dimx, dimy);
+        const long stride = of2d::batch::pair_stride(dimx, dimy);
+        const int P = of2d::pitch_for(dimx);
+        of2d::launch_pack_image(view_of(in, e), npairs, dimx, dimy, f.p, stride, P, nullptr);
+        for (int k = 0; k < npairs; k++)
+            download(out_host + (size_t)k * dimx * dimy, f.p + k * stride, P, dimx, dimy);
+    });
+}
+
+int of2d_prim_unpack_image(const float *in_host, int npairs, int dimx, int dimy,
+                           const of2d_darray *out) {
+    const Extents e = {{npairs, dimx, dimy, 0}};
+    const bool ok = in_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
+                    dimy > 0;
+    const std::string why =
+        ok ? first_refusal("of2d_prim_unpack_image", {{out, "out", true, e}})
+           : std::string("of2d_prim_unpack_image: in_host is NULL or a size is out of range");
+    if (!why.empty()) return refuse(nullptr, why.c_str());
+    return prim(true, [&] {
+        of2d::batch::BField<float> f;
+        upload_pairs(f, in_host, npairs, dimx, dimy);
+        of2d::launch_unpack_image(f.p, of2d::batch::pair_stride(dimx, dimy),
+                                  of2d::pitch_for(dimx), npairs, dimx, dimy, view_of(out, e),
+                                  nullptr);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
+int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
+                            const of2d_darray *out) {
+    const Extents e = {{npairs, dimx, dimy, 2}};
+    const bool ok = m_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
+                    dimy > 0;
+    const std::string why =
+        ok ? first_refusal("of2d_prim_unpack_motion", {{out, "out", true, e}})
+           : std::string("of2d_prim_unpack_motion: m_host is NULL or a size is out of range");
+    if (!why.empty()) return refuse(nullptr, why.c_str());
+    return prim(true, [&] {
+        of2d::batch::BField<float2> f;
+        upload_pairs(f, m_host, npairs, dimx, dimy);
+        of2d::launch_unpack_motion(f.p, of2d::batch::pair_stride(dimx, dimy),
+                                   of2d::pitch_for(dimx), npairs, dimx, dimy, view_of(out, e),
+                                   nullptr);
+        OF2D_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
+}  // extern "C"

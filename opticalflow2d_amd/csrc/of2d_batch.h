@@ -132,7 +132,15 @@ class Batch {
     void estimate();
     void get_motion(double *out);
     void warp(const double *in, double *out);
+    // the same three on the caller's device arrays, ordered with the caller's
+    // stream `user` (include/of2d.h, of2d_batch_set_images_device)
+    void set_images_device(const DArrayView &ref, bool shared_ref, const DArrayView &mov,
+                           hipStream_t user);
+    void get_motion_device(const DArrayView &out, hipStream_t user);
+    void warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user);
     int nbatch() const { return B_; }
+    int dimx() const { return dimx_; }
+    int dimy() const { return dimy_; }
     int nloops() const { return nloops_; }
     const std::vector<unsigned> &status() const { return h_status_; }
     const std::vector<int> &iterations() const { return h_iters_; }
@@ -149,6 +157,8 @@ class Batch {
     void allocate_device();
     void release_device();
     void ensure_reference(int npairs);
+    void downsample_levels(int which, int npairs);
+    void images_in_place(bool shared_ref);
     size_t chunk_pairs() const;
     int B_, dimx_, dimy_, nscales_, nrefine_, nloops_ = 0;
     std::vector<int> niter_, ldx_, ldy_;
@@ -166,6 +176,7 @@ class Batch {
     float *d_errs_ = nullptr;
     int maxn_ = 0;
     std::vector<hipEvent_t> ev_;
+    hipEvent_t ev_io_[2] = {};  // the caller's stream before / after the device-array launches
     int launches_ = 0;
     double loop_us_ = 0.0;
     std::vector<unsigned> h_status_;

@@ -476,6 +476,28 @@ void launch_d2f(const double *in, int dimx, int dimy, float *out, int P, int row
 void launch_f2d(const float *in, int P, int dimx, int dimy, double *out, hipStream_t st);
 void launch_motion_to_planar(const float2 *m, int P, int dimx, int dimy, double *out,
                              hipStream_t st);
+// A caller's strided device array (include/of2d.h of2d_darray, validated):
+// element strides of the pair, x, y and component axes
+struct DArrayView {
+    void *ptr = nullptr;
+    bool f64 = false;
+    long long sp = 0, sx = 0, sy = 0, sc = 0;
+};
+// io_kernels.hip: npairs images or motion fields in one launch; the pitched
+// side holds pair k at k * so (si, sm) elements, pitch P
+void launch_pack_image(const DArrayView &in, int npairs, int dimx, int dimy, float *out, long so,
+                       int P, hipStream_t st);
+void launch_unpack_image(const float *in, long si, int P, int npairs, int dimx, int dimy,
+                         const DArrayView &out, hipStream_t st);
+void launch_unpack_motion(const float2 *m, long sm, int P, int npairs, int dimx, int dimy,
+                          const DArrayView &out, hipStream_t st);
+// `waiter` behind everything enqueued on `signal` so far
+inline void stream_after(hipStream_t waiter, hipStream_t signal, hipEvent_t ev) {
+    OF2D_HIP(hipEventRecord(ev, signal));
+    OF2D_HIP(hipStreamWaitEvent(waiter, ev, 0));
+}
+// refuses (std::invalid_argument) a pointer that is not device memory of `dev`
+void check_device_pointer(const void *p, int dev, const char *what);
 void launch_downsample_image(const float *in, int dxi, int dyi, int Pi, float *out, int dxo,
                              int dyo, int Po, hipStream_t st);
 void launch_downsample_motion(const float2 *in, int dxi, int dyi, int Pi, float2 *out, int dxo,

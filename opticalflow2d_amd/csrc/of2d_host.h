@@ -190,6 +190,11 @@ class Registration {
     void estimate();
     void get_motion(double *out);
     void warp(const double *in, double *out);
+    // the same three on the caller's device arrays, ordered with the caller's
+    // stream `user` (include/of2d.h, of2d_set_images_device)
+    void set_images_device(const DArrayView &ref, const DArrayView &mov, hipStream_t user);
+    void get_motion_device(const DArrayView &out, hipStream_t user);
+    void warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user);
     // Deformation analysis of the level-0 motion, on the device (include/of2d.h
     // of2d_jacobian, of2d_invert_motion, of2d_quality); the motion is only read
     void jacobian(double *jac, double *stats);
@@ -224,6 +229,8 @@ class Registration {
                     const StepFn2 &step2 = nullptr, const StepFn3 &step3 = nullptr,
                     const int *nblk = nullptr, const StepFn3M &step3m = nullptr);
     void ensure_device();
+    void downsample_levels(int which);
+    void images_in_place();
     void estimate_level(int s);
     int loop_hs(Level &L, int niter, float alpha, int &final_buf);
     int loop_demons(Level &L, int niter, int &final_buf);
@@ -318,6 +325,7 @@ class Registration {
     bool ready_ = false;
     hipStream_t st_ = nullptr;
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
+    hipEvent_t ev_io_[2] = {};  // the caller's stream before / after the device-array launches
     double *d_stage_ = nullptr;  // double staging for boundary copies
     size_t stage_count_ = 0;
     double *d_partial_ = nullptr;

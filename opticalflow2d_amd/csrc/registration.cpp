@@ -170,6 +170,8 @@ Registration::~Registration() {
     lv_.clear();
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_join_) (void)hipEventDestroy(ev_join_);
+    for (hipEvent_t e : ev_io_)
+        if (e) (void)hipEventDestroy(e);
     if (sn_st_) (void)hipStreamDestroy(sn_st_);
     if (fx_st_) (void)hipStreamDestroy(fx_st_);
     for (hipStream_t w : wk_st_)
@@ -285,6 +287,7 @@ void Registration::ensure_device() {
     }
     OF2D_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
     OF2D_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+    for (hipEvent_t &e : ev_io_) OF2D_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     lv_.resize(nscales_ + 1);
     size_t maxnb = 1;
     for (int s = 0; s <= nscales_; s++) {
@@ -327,14 +330,42 @@ void Registration::set_images(const double *ref, const double *mov) {
     for (int which = 0; which < 2; which++) {
         const double *src = which ? mov : ref;
         OF2D_HIP(hipMemcpyAsync(d_stage_, src, n0 * sizeof(double), hipMemcpyHostToDevice, st_));
-        Field<float> &dst0 = which ? L0.Imov : L0.Iref;
-        launch_d2f(d_stage_, dimx_, dimy_, dst0.p, L0.P, 0, st_);
-        for (int s = nscales_; s >= 1; s--) {
-            Field<float> &dst = which ? lv_[s].Imov : lv_[s].Iref;
-            launch_downsample_image(dst0.p, L0.dx, L0.dy, L0.P, dst.p, lv_[s].dx, lv_[s].dy,
-                                    lv_[s].P, st_);
-        }
+        launch_d2f(d_stage_, dimx_, dimy_, (which ? L0.Imov : L0.Iref).p, L0.P, 0, st_);
+        downsample_levels(which);
     }
+    images_in_place();
+}
+
+// the same from the caller's device arrays (include/of2d.h, the stream contract)
+void Registration::set_images_device(const DArrayView &ref, const DArrayView &mov,
+                                     hipStream_t user) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    check_device_pointer(ref.ptr, home_, "of2d_set_images_device: Iref");
+    check_device_pointer(mov.ptr, home_, "of2d_set_images_device: Imov");
+    Level &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_image(ref, 1, dimx_, dimy_, L0.Iref.p, 0, L0.P, st_);
+    launch_pack_image(mov, 1, dimx_, dimy_, L0.Imov.p, 0, L0.P, st_);
+    stream_after(user, st_, ev_io_[1]);  // the caller's arrays are free again
+    downsample_levels(0);
+    downsample_levels(1);
+    images_in_place();
+}
+
+// the pyramid of the reference (0) or moving (1) image below level 0
+void Registration::downsample_levels(int which) {
+    Level &L0 = lv_[0];
+    Field<float> &dst0 = which ? L0.Imov : L0.Iref;
+    for (int s = nscales_; s >= 1; s--) {
+        Field<float> &dst = which ? lv_[s].Imov : lv_[s].Iref;
+        launch_downsample_image(dst0.p, L0.dx, L0.dy, L0.P, dst.p, lv_[s].dx, lv_[s].dy,
+                                lv_[s].P, st_);
+    }
+}
+
+// what set_images does once both pyramids are enqueued
+void Registration::images_in_place() {
     // Horn-Schunck's iterate ring for the exact Logger (run_exact_pipelined),
     // allocated here rather than inside the first estimate's loop: 13 more
     // fields per level (the other solvers allocate theirs at first use)
@@ -343,6 +374,20 @@ void Registration::set_images(const double *ref, const double *mov) {
             for (int b = 3; b <= kRing; b++)
                 if (!L.est[b].p) L.est[b].alloc(L.dx, L.dy);
     OF2D_HIP(hipStreamSynchronize(st_));
+}
+
+void check_device_pointer(const void *p, int dev, const char *what) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        throw std::invalid_argument(std::string(what) + ".ptr is not a device pointer");
+    }
+    if (a.type == hipMemoryTypeUnregistered)
+        throw std::invalid_argument(std::string(what) + ".ptr is not a device pointer");
+    if (a.type == hipMemoryTypeDevice && a.device != dev)
+        throw std::invalid_argument(std::string(what) + ".ptr is on device " +
+                                    std::to_string(a.device) + ", the context on device " +
+                                    std::to_string(dev));
 }
 
 void Registration::check_status() {
@@ -879,6 +924,34 @@ void Registration::warp(const double *in, double *out) {
     launch_f2d(b.p, L0.P, dimx_, dimy_, d_stage_, st_);
     OF2D_HIP(hipMemcpyAsync(out, d_stage_, n0 * sizeof(double), hipMemcpyDeviceToHost, st_));
     OF2D_HIP(hipStreamSynchronize(st_));
+}
+
+// get_motion and warp on the caller's device arrays
+void Registration::get_motion_device(const DArrayView &out, hipStream_t user) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    check_device_pointer(out.ptr, home_, "of2d_get_motion_device: out");
+    Level &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_unpack_motion(L0.cur_motion(), 0, L0.P, 1, dimx_, dimy_, out, st_);
+    stream_after(user, st_, ev_io_[1]);
+}
+
+void Registration::warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    check_device_pointer(in.ptr, home_, "of2d_warp_device: Imov");
+    check_device_pointer(out.ptr, home_, "of2d_warp_device: out");
+    Level &L0 = lv_[0];
+    Field<float> a, b;
+    a.alloc(dimx_, dimy_);
+    b.alloc(dimx_, dimy_);
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_image(in, 1, dimx_, dimy_, a.p, 0, L0.P, st_);
+    launch_warp(a.p, L0.cur_motion(), b.p, dimx_, dimy_, L0.P, st_);
+    launch_unpack_image(b.p, 0, L0.P, 1, dimx_, dimy_, out, st_);
+    stream_after(user, st_, ev_io_[1]);
+    OF2D_HIP(hipStreamSynchronize(st_));  // a and b are freed on return
 }
 
 // ------------------------------------------------------------ analysis

@@ -23,7 +23,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib
 from ._lib import Of2dError, check
 
 
@@ -398,6 +398,41 @@ class prim:
         cls._call("of2d_prim_motion_to_planar", m, m.shape[1], m.shape[0], out)
         return out
 
+    # Device-resident I/O (io_kernels.hip), one launch each.  ``t`` / ``out``
+    # are torch CUDA tensors whose dimension d is the of2d_darray axis
+    # ``axes[d]`` (0 pair, 1 x, 2 y, 3 component); the host side is float32 in
+    # the layout above with a leading pair axis.
+    @classmethod
+    def pack_image(cls, t, axes=(0, 1, 2)):
+        ext = dict(zip(axes, t.shape))
+        npairs, dimx, dimy = ext[0], ext[1], ext[2]
+        out = np.zeros((npairs, dimy, dimx), np.float32)
+        a = _device.darray(t, t.shape, axes, "in")
+        cls._call("of2d_prim_pack_image", C.byref(a), npairs, dimx, dimy, out)
+        return out
+
+    @classmethod
+    def unpack_image(cls, a, out, axes=(0, 1, 2)):
+        a = cls._f(a)
+        npairs, dimy, dimx = a.shape
+        shape = [0, 0, 0]
+        for d, ax in enumerate(axes):
+            shape[d] = (npairs, dimx, dimy)[ax]
+        o = _device.darray(out, shape, axes, "out")
+        cls._call("of2d_prim_unpack_image", a, npairs, dimx, dimy, C.byref(o))
+        return out
+
+    @classmethod
+    def unpack_motion(cls, m, out, axes=(0, 1, 2, 3)):
+        m = cls._f(m)
+        npairs, dimy, dimx, _ = m.shape
+        shape = [0, 0, 0, 0]
+        for d, ax in enumerate(axes):
+            shape[d] = (npairs, dimx, dimy, 2)[ax]
+        o = _device.darray(out, shape, axes, "out")
+        cls._call("of2d_prim_unpack_motion", m, npairs, dimx, dimy, C.byref(o))
+        return out
+
     # Curvature, one call each (include/of2d.h).  curv_rhs and curv_construct
     # take fields in the layout above; curv_eigen and curv_dct2d speak
     # ``[dimx, dimy]`` arrays as :func:`dct2d` does.
@@ -683,6 +718,7 @@ class ImageRegistration:
                            npar, int(nrefine), int(verbose))
         check(st, L.of2d_last_error(None).decode())
         self._h = h
+        self._device = None  # option "device": where motion_device allocates
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -691,13 +727,26 @@ class ImageRegistration:
 
     def set_option(self, key: str, value: float) -> None:
         self._chk(_lib.lib().of2d_set_option(self._h, key.encode(), float(value)))
+        if key == "device":
+            self._device = int(value)
 
     def register(self, Iref, Imov) -> None:
         self.set_images(Iref, Imov)
         self.estimate()
 
     def set_images(self, Iref, Imov) -> None:
-        """Upload the image pair (the first half of register)."""
+        """Upload the image pair (the first half of register).  Two torch CUDA
+        tensors ``[dimx, dimy]`` (float32 or float64, any strides) are read
+        where they are, in the order of their device's current stream
+        (of2d_set_images_device); mixing one with a host array is a
+        ``ValueError``."""
+        if _device.all_cuda(Iref=Iref, Imov=Imov):
+            shape, axes = (self.dimx, self.dimy), (1, 2)
+            r = _device.darray(Iref, shape, axes, "Iref")
+            m = _device.darray(Imov, shape, axes, "Imov")
+            self._chk(_lib.lib().of2d_set_images_device(self._h, C.byref(r), C.byref(m),
+                                                        _device.stream_of(Imov)))
+            return
         n = self.dimx * self.dimy
         r, m = _col(Iref, n), _col(Imov, n)
         self._chk(_lib.lib().of2d_set_images(self._h, r, m))
@@ -711,7 +760,30 @@ class ImageRegistration:
         self._chk(_lib.lib().of2d_get_motion(self._h, out))
         return out.reshape((self.dimx, self.dimy, 2), order="F")
 
-    def warp(self, Imov) -> np.ndarray:
+    def motion_device(self, dtype=None, out=None):
+        """The motion as a CUDA tensor ``[dimx, dimy, 2]`` of ``dtype``
+        (``torch.float32``, the default, or ``torch.float64``), or written into
+        ``out`` (a CUDA tensor of that shape, any strides), in the order of the
+        device's current stream (of2d_get_motion_device)."""
+        shape = (self.dimx, self.dimy, 2)
+        out = _device.output(out, shape, dtype, self._device)
+        a = _device.darray(out, shape, (1, 2, 3), "out")
+        self._chk(_lib.lib().of2d_get_motion_device(self._h, C.byref(a), _device.stream_of(out)))
+        return out
+
+    def warp(self, Imov, out=None):
+        """``Imov`` warped by the current motion.  A CUDA tensor gives a CUDA
+        tensor of its dtype, or ``out`` (of2d_warp_device)."""
+        if _device.all_cuda(**({"Imov": Imov} if out is None else {"Imov": Imov, "out": out})):
+            shape, axes = (self.dimx, self.dimy), (1, 2)
+            m = _device.darray(Imov, shape, axes, "Imov")
+            out = _device.output(out, shape, Imov.dtype, Imov.device)
+            o = _device.darray(out, shape, axes, "out")
+            self._chk(_lib.lib().of2d_warp_device(self._h, C.byref(m), C.byref(o),
+                                                  _device.stream_of(Imov)))
+            return out
+        if out is not None:
+            raise ValueError("out= is for CUDA tensors")
         n = self.dimx * self.dimy
         m = _col(Imov, n)
         out = np.zeros(n, np.float64)
