@@ -7,7 +7,8 @@ loop runs in hand-written gfx950 HIP kernels (``opticalflow2d_amd/csrc``).
 """
 from ._lib import Of2dError, InvalidArgument, build, lib
 from .registration import (ImageRegistration, MotionAccumulation, OpticalFlow2d,
-                           Regularisation, Verbose, dct2d, field, prim, set_print_sink)
+                           Regularisation, Verbose, field, set_print_sink)
+from .prims import dct2d, prim
 from .batch import BatchRegistration
 from .slab import SlabGroup, SlabSolver, slab_bounds
 

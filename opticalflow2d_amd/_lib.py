@@ -1,4 +1,5 @@
-"""ctypes binding of libof2d.so (include/of2d.h).
+"""ctypes binding of libof2d.so (include/of2d.h and, for the test entries,
+csrc/of2d_prims.h).
 
 The shared library is built in-tree (``opticalflow2d_amd/libof2d.so``) by
 ``opticalflow2d_amd/csrc/Makefile``.  There is no CPU fallback: if the library
@@ -51,7 +52,7 @@ class DArray(C.Structure):
 _darr = C.POINTER(DArray)
 
 # name -> (restype, argtypes); the list IS the exported surface of include/of2d.h
-SIGNATURES = {
+PRODUCT_SIGNATURES = {
     "of2d_set_print_hook": (None, [PRINT_FN, C.c_void_p]),
     "of2d_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, _i32p, C.c_int, C.c_int,
                               _f32p, C.c_uint, C.c_int, C.c_int]),
@@ -66,8 +67,6 @@ SIGNATURES = {
     "of2d_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "of2d_curvature_paths": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "of2d_demons_paths": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
-    "of2d_dct2d": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p]),
-    "of2d_dct_time_passes": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
     "of2d_gateway": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     "of2d_gateway_output_numel": (C.c_size_t, [C.c_int, C.c_int]),
     "of2d_gateway_output_dims": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t),
@@ -98,8 +97,42 @@ SIGNATURES = {
     "of2d_slab_group_destroy": (C.c_int, [C.c_void_p]),
     "of2d_slab_create_local": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_float,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "of2d_field_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_void_p, _f64p]),
+    "of2d_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, _f64p]),
+    "of2d_field_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_double, _f32p, _f64p,
+                                    C.c_void_p]),
+    "of2d_invert_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f64p, _f64p]),
+    "of2d_image_similarity": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f64p]),
+    "of2d_quality": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
+    "of2d_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, _i32p,
+                                    C.c_int, C.c_int, _f32p, C.c_uint, C.c_int]),
+    "of2d_batch_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+    "of2d_batch_set_images": (C.c_int, [C.c_void_p, _f64p, C.c_int, _f64p]),
+    "of2d_batch_estimate": (C.c_int, [C.c_void_p]),
+    "of2d_batch_get_motion": (C.c_int, [C.c_void_p, _f64p]),
+    "of2d_batch_warp": (C.c_int, [C.c_void_p, _f64p, _f64p]),
+    "of2d_batch_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "of2d_batch_iterations": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
+    "of2d_batch_last_errors": (C.c_int, [C.c_void_p, C.c_int, _f32p, C.c_int]),
+    "of2d_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "of2d_batch_destroy": (C.c_int, [C.c_void_p]),
+    "of2d_batch_last_error": (C.c_char_p, [C.c_void_p]),
+    "of2d_set_images_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
+    "of2d_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_batch_set_images_device": (C.c_int, [C.c_void_p, _darr, C.c_int, _darr, C.c_void_p]),
+    "of2d_batch_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
+    "of2d_batch_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_version": (C.c_char_p, []),
+    "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
+}
+
+# the test and diagnostic entries of the same library (csrc/of2d_prims.h)
+PRIM_SIGNATURES = {
     "of2d_motion_norms": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
     "of2d_motion_norms_chain": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _i32p]),
+    "of2d_dct2d": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p]),
+    "of2d_dct_time_passes": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
     "of2d_prim_warp": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p]),
     "of2d_prim_accumulate": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p]),
     "of2d_prim_regrid": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p]),
@@ -111,21 +144,14 @@ SIGNATURES = {
     "of2d_prim_demons_force": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
                                          C.c_float, _f32p, C.POINTER(C.c_uint)]),
     "of2d_prim_smooth_compose": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                           C.c_int, _f32p, C.POINTER(C.c_double)]),
+                                           C.c_int, _f32p, C.POINTER(C.c_double), C.c_int,
+                                           C.POINTER(C.c_int)]),
     "of2d_prim_smooth_norm": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                        _f32p, C.POINTER(C.c_double)]),
+                                        _f32p, C.POINTER(C.c_double), C.c_int,
+                                        C.POINTER(C.c_int)]),
     "of2d_prim_demons_update": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
                                           C.c_float, C.c_int, C.c_float, C.c_int, _f32p,
-                                          C.POINTER(C.c_uint)]),
-    "of2d_prim_smooth_compose_m": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                             C.c_int, _f32p, C.POINTER(C.c_double), C.c_int,
-                                             C.POINTER(C.c_int)]),
-    "of2d_prim_smooth_norm_m": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                          _f32p, C.POINTER(C.c_double), C.c_int,
-                                          C.POINTER(C.c_int)]),
-    "of2d_prim_demons_update_m": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
-                                            C.c_float, C.c_int, C.c_float, C.c_int, _f32p,
-                                            C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int)]),
+                                          C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int)]),
     "of2d_prim_motion_exp": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_float, C.c_float,
                                        C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "of2d_prim_d2f": (C.c_int, [_f64p, C.c_int, C.c_int, _f32p]),
@@ -154,39 +180,13 @@ SIGNATURES = {
     "of2d_prim_fluid_decide": (C.c_int, [_f64p, _f32p, C.c_int, _f32p_opt, C.c_double, C.c_int,
                                          C.c_int, _f32p, _u32p, _f64p, _f32p, _u32p]),
     "of2d_prim_elastic_logger": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f64p]),
-    "of2d_field_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_void_p, _f64p]),
-    "of2d_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, _f64p]),
-    "of2d_field_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_double, _f32p, _f64p,
-                                    C.c_void_p]),
-    "of2d_invert_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f64p, _f64p]),
-    "of2d_image_similarity": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f64p]),
-    "of2d_quality": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
     "of2d_analysis_time_kernels": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
-    "of2d_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, _i32p,
-                                    C.c_int, C.c_int, _f32p, C.c_uint, C.c_int]),
-    "of2d_batch_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
-    "of2d_batch_set_images": (C.c_int, [C.c_void_p, _f64p, C.c_int, _f64p]),
-    "of2d_batch_estimate": (C.c_int, [C.c_void_p]),
-    "of2d_batch_get_motion": (C.c_int, [C.c_void_p, _f64p]),
-    "of2d_batch_warp": (C.c_int, [C.c_void_p, _f64p, _f64p]),
-    "of2d_batch_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
-    "of2d_batch_iterations": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
-    "of2d_batch_last_errors": (C.c_int, [C.c_void_p, C.c_int, _f32p, C.c_int]),
-    "of2d_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
-    "of2d_batch_destroy": (C.c_int, [C.c_void_p]),
-    "of2d_batch_last_error": (C.c_char_p, [C.c_void_p]),
-    "of2d_set_images_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
-    "of2d_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
-    "of2d_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
-    "of2d_batch_set_images_device": (C.c_int, [C.c_void_p, _darr, C.c_int, _darr, C.c_void_p]),
-    "of2d_batch_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
-    "of2d_batch_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
     "of2d_prim_pack_image": (C.c_int, [_darr, C.c_int, C.c_int, C.c_int, _f32p]),
     "of2d_prim_unpack_image": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
     "of2d_prim_unpack_motion": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
-    "of2d_version": (C.c_char_p, []),
-    "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }
+
+SIGNATURES = {**PRODUCT_SIGNATURES, **PRIM_SIGNATURES}  # everything lib() binds
 
 _lib = None
 

@@ -3,20 +3,20 @@
 // Every entry point catches the C++ exceptions of the driver and turns them
 // into a status code plus the reference's message, so nothing throws across
 // the ABI.  The gateway reproduces mexFunction's five modes over the same
-// process-global singleton (WrapperOpticalFlow2d.cpp:13-155).
+// process-global singleton (WrapperOpticalFlow2d.cpp:13-155).  The test and
+// diagnostic entries (of2d_prims.h) are in capi_prims.cpp.
 #include "../../include/of2d.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <mutex>
 #include <string>
 
+#include "capi_internal.h"
 #include "of2d_batch.h"
-#include "of2d_host.h"
-#include "of2d_solvers.h"
+
+using namespace of2d::capi;
 
 struct of2d_ctx {
     std::unique_ptr<of2d::Registration> reg;
@@ -28,30 +28,19 @@ of2d_print_fn g_print = nullptr;
 void *g_print_user = nullptr;
 std::mutex g_print_mu;
 thread_local std::string g_gateway_err;
-
-template <class F>
-int guarded(std::string &err, F &&f) {
-    try {
-        f();
-        err.clear();
-        return OF2D_OK;
-    } catch (const std::invalid_argument &e) {
-        err = e.what();
-        return OF2D_ERR_INVALID_ARGUMENT;
-    } catch (const of2d::DeviceError &e) {
-        err = e.what();
-        return OF2D_ERR_DEVICE;
-    } catch (const std::exception &e) {
-        err = e.what();
-        return OF2D_ERR_RUNTIME;
-    } catch (...) {
-        err = "unknown error";
-        return OF2D_ERR_RUNTIME;
-    }
-}
 }  // namespace
 
 namespace of2d {
+namespace capi {
+void set_gateway_error(const std::string &msg) { g_gateway_err = msg; }
+int refuse(of2d_ctx *ctx, const char *why) {
+    g_gateway_err = why;
+    if (ctx) ctx->err = why;
+    return OF2D_ERR_INVALID_ARGUMENT;
+}
+}  // namespace capi
+
+
 void print(const char *fmt, ...) {
     char buf[2048];
     va_list ap;
@@ -177,618 +166,10 @@ static_assert(OF2D_SEP_KW_MAX == of2d::kSepKwMax,
 static_assert(OF2D_DCT_NMIN == of2d::kDctMinN && OF2D_DCT_NMAX == of2d::kDctMaxN,
               "include/of2d.h documents the fast transform's lengths");
 
-int of2d_dct2d(double *a, int dimx, int dimy, int kind, int method, int *paths) {
-    if (!a || !paths || dimx <= 0 || dimy <= 0 || (kind != 10 && kind != 1) ||
-        (method != 0 && method != 1))
-        return OF2D_ERR_INVALID_ARGUMENT;
-    std::string err;
-    int rc = guarded(err, [&] {
-        // a level of the solver with nothing but Curvature's buffers and tables
-        of2d::Level L;
-        L.dx = dimx;
-        L.dy = dimy;
-        L.P = of2d::pitch_for(dimx);
-        of2d::solvers::alloc_level(L, OF2D_REG_CURVATURE);
-        of2d::solvers::build_curvature(L, 0.0f, 0.0f, method, nullptr);
-        paths[0] = L.cpath & 1;
-        paths[1] = (L.cpath >> 1) & 1;
-        const size_t row = (size_t)dimx * sizeof(double), pitch = (size_t)L.P * sizeof(double);
-        OF2D_HIP(hipMemcpy2D(L.cbuf[0].p, pitch, a, row, row, dimy, hipMemcpyHostToDevice));
-        const double *res = of2d::solvers::curvature_dct2d(L, kind == 1, L.cbuf[0].p,
-                                                           L.cbuf[1].p, nullptr, nullptr);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy2D(a, row, res, pitch, row, dimy, hipMemcpyDeviceToHost));
-    });
-    if (rc != OF2D_OK) g_gateway_err = err;
-    return rc;
-}
-
-int of2d_dct_time_passes(int dimx, int dimy, int nlaunch, double *us) {
-    if (!us || nlaunch <= 0 || !of2d::dct_fast_length(dimx) || !of2d::dct_fast_length(dimy))
-        return OF2D_ERR_INVALID_ARGUMENT;
-    std::string err;
-    int rc = guarded(err, [&] {
-        of2d::Level L;
-        L.dx = dimx;
-        L.dy = dimy;
-        L.P = of2d::pitch_for(dimx);
-        of2d::solvers::alloc_level(L, OF2D_REG_CURVATURE);
-        of2d::solvers::build_curvature(L, 0.0f, 0.0f, 1, nullptr);
-        const int P = L.P, Pt = of2d::pitch_for(dimy);
-        const long plane = (long)P * dimy, planeT = (long)Pt * dimx;
-        double *X = L.cbuf[0].p, *T = L.cbuf[1].p;
-        hipEvent_t e0, e1;
-        OF2D_HIP(hipEventCreate(&e0));
-        OF2D_HIP(hipEventCreate(&e1));
-        // the buffers hold zeros: the transforms' cost does not depend on the data
-        for (int which = 0; which < 4; which++) {
-            for (int k = -1; k < nlaunch; k++) {  // k = -1: one untimed launch
-                if (k == 0) OF2D_HIP(hipEventRecord(e0, nullptr));
-                if (which == 0)
-                    of2d::launch_dct_lines(X, plane, P, dimy, dimx, 0, L.ctwx.p, L.cE.p, nullptr);
-                else if (which == 1)
-                    of2d::launch_dct_lines(X, plane, P, dimy, dimx, 1, L.ctwx.p, nullptr, nullptr);
-                else if (which == 2)
-                    of2d::launch_transpose_pair(X, P, plane, T, Pt, planeT, dimx, dimy, nullptr);
-                else
-                    of2d::launch_dct_lines(T, planeT, Pt, dimx, dimy, 0, L.ctwy.p, nullptr,
-                                           nullptr);
-            }
-            OF2D_HIP(hipEventRecord(e1, nullptr));
-            OF2D_HIP(hipEventSynchronize(e1));
-            float ms = 0.0f;
-            OF2D_HIP(hipEventElapsedTime(&ms, e0, e1));
-            us[which] = 1000.0 * (double)ms / nlaunch;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    });
-    if (rc != OF2D_OK) g_gateway_err = err;
-    return rc;
-}
-
-int of2d_motion_norms(const float *cur, const float *prev, int dimx, int dimy, int npairs,
-                      float *sums, int *stats) {
-    if (!cur || !prev || !sums || dimx <= 0 || dimy <= 0 || npairs <= 0)
-        return OF2D_ERR_INVALID_ARGUMENT;
-    std::string err;
-    int rc = guarded(err, [&] {
-        of2d::Field<float2> c, p;
-        c.alloc(dimx, dimy);
-        p.alloc(dimx, dimy);
-        const size_t n = (size_t)dimx * dimy * 2;
-        const size_t row = (size_t)dimx * sizeof(float2), pitch = (size_t)c.P * sizeof(float2);
-        of2d::DevArray<unsigned char> ws;
-        ws.alloc(of2d::seqnorm_workspace_bytes(dimx, dimy));
-        of2d::DevArray<float> out;
-        out.alloc(2 * (size_t)npairs);
-        // the walk's counters: the 8 of the ABI, then 2 more (tools)
-        constexpr int kSnDbg = 10;
-        of2d::DevArray<int> dbg;
-        dbg.alloc(kSnDbg * (size_t)npairs);
-        for (int k = 0; k < npairs; k++) {
-            // one workspace: each pair's walk predicts the next (its profile)
-            OF2D_HIP(hipMemcpy2D(c.p, pitch, cur + k * n, row, row, dimy, hipMemcpyHostToDevice));
-            OF2D_HIP(hipMemcpy2D(p.p, pitch, prev + k * n, row, row, dimy, hipMemcpyHostToDevice));
-            of2d::launch_seqnorm(c.p, p.p, dimx, dimy, c.P, ws.p, k > 0, out.p + 2 * k,
-                                 dbg.p + kSnDbg * k, nullptr);
-        }
-        OF2D_HIP(hipMemcpy(sums, out.p, 2 * sizeof(float) * npairs, hipMemcpyDeviceToHost));
-        if (stats)
-            OF2D_HIP(hipMemcpy2D(stats, 8 * sizeof(int), dbg.p, kSnDbg * sizeof(int),
-                                 8 * sizeof(int), npairs, hipMemcpyDeviceToHost));
-    });
-    if (rc != OF2D_OK) g_gateway_err = err;
-    return rc;
-}
-
-int of2d_motion_norms_chain(const float *u, int dimx, int dimy, int niter, int batch,
-                            float *sums, int *stats) {
-    if (!u || !sums || dimx <= 0 || dimy <= 0 || niter <= 0 || batch < 1 || batch > 3)
-        return OF2D_ERR_INVALID_ARGUMENT;
-    std::string err;
-    int rc = guarded(err, [&] {
-        const size_t n = (size_t)dimx * dimy * 2;
-        std::vector<of2d::Field<float2>> f((size_t)niter + 1);
-        for (size_t k = 0; k <= (size_t)niter; k++) {
-            f[k].alloc(dimx, dimy);
-            const size_t row = (size_t)dimx * sizeof(float2), pitch = (size_t)f[k].P * sizeof(float2);
-            OF2D_HIP(hipMemcpy2D(f[k].p, pitch, u + k * n, row, row, dimy, hipMemcpyHostToDevice));
-        }
-        // four sets of three workspaces rotated per batch, as the registration
-        // loops (Registration::kSeqSets): batch g's profile is batch g - 4's
-        constexpr int kSets = 4;
-        of2d::DevArray<unsigned char> ws[3 * kSets];
-        bool used[3 * kSets] = {};
-        for (auto &w : ws) w.alloc(of2d::seqnorm_workspace_bytes(dimx, dimy));
-        of2d::DevArray<float> out;
-        out.alloc(2 * (size_t)niter);
-        constexpr int kSnDbg = 10;
-        of2d::DevArray<int> dbg;
-        dbg.alloc(kSnDbg * (size_t)niter);
-        for (int t = 0, g = 0; t < niter; g++) {
-            of2d::SeqnormBatch B;
-            B.K = std::min(batch, niter - t);
-            for (int i = 0; i <= B.K; i++) B.u[i] = f[(size_t)t + i].p;
-            for (int i = 0; i < B.K; i++) {
-                const int w = 3 * (g % kSets) + i;
-                B.ws[i] = ws[w].p;
-                B.use_profile[i] = used[w];
-                used[w] = true;
-                B.out[i] = out.p + 2 * (size_t)(t + i);
-                B.dbg[i] = dbg.p + kSnDbg * (size_t)(t + i);
-            }
-            of2d::launch_seqnorm_pass(B, dimx, dimy, f[0].P, nullptr);
-            of2d::launch_seqnorm_refine(B, dimx, dimy, f[0].P, nullptr);
-            of2d::launch_seqnorm_walk(B, dimx, dimy, f[0].P, nullptr);
-            t += B.K;
-        }
-        OF2D_HIP(hipMemcpy(sums, out.p, 2 * sizeof(float) * niter, hipMemcpyDeviceToHost));
-        if (stats)
-            OF2D_HIP(hipMemcpy2D(stats, 8 * sizeof(int), dbg.p, kSnDbg * sizeof(int),
-                                 8 * sizeof(int), niter, hipMemcpyDeviceToHost));
-    });
-    if (rc != OF2D_OK) g_gateway_err = err;
-    return rc;
-}
-
-// ------------------------------------------------------------------ primitives
-// One launch of the function the solvers call, on host arrays: dense float
-// images (idx = i + j*dimx) and interleaved float2 motion fields.
-}  // extern "C"
-
-namespace {
-// a zeroed pitched field holding the dense host array (none: zeros)
-template <class T>
-void upload(of2d::Field<T> &f, const float *host, int dimx, int dimy) {
-    f.alloc(dimx, dimy);
-    const size_t row = (size_t)dimx * sizeof(T);
-    if (host)
-        OF2D_HIP(hipMemcpy2D(f.p, (size_t)f.P * sizeof(T), host, row, row, dimy,
-                             hipMemcpyHostToDevice));
-}
-template <class T>
-void download(float *host, const T *p, int P, int dimx, int dimy) {
-    const size_t row = (size_t)dimx * sizeof(T);
-    OF2D_HIP(hipStreamSynchronize(nullptr));
-    OF2D_HIP(hipMemcpy2D(host, row, p, (size_t)P * sizeof(T), row, dimy, hipMemcpyDeviceToHost));
-}
-// the status word of a context (kStatus* bits), zeroed
-struct StatusWord {
-    of2d::DevArray<unsigned> w;
-    StatusWord() { w.alloc(64); }
-    unsigned read() {
-        unsigned v = 0;
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(&v, w.p, sizeof v, hipMemcpyDeviceToHost));
-        return v;
-    }
-};
-// a Gaussian of the product on the device, as Registration::loop_demons holds
-// kfluid_ / kdiff_: float and double weights, the full weight sum
-struct DeviceGaussian {
-    of2d::DevArray<float> kf;
-    of2d::DevArray<double> kd;
-    of2d::DevArray<float> gs;  // gaussian_marginals
-    double wfull = 0;
-    // the launches' gs argument for `method`
-    const float *factors(int method) const { return method ? gs.p : nullptr; }
-    DeviceGaussian(int kw, float sigma) {
-        const std::vector<double> k = of2d::gaussian_kernel(kw, sigma);
-        std::vector<float> f(k.size());
-        for (size_t t = 0; t < k.size(); t++) f[t] = (float)k[t];
-        kf.alloc(k.size());
-        kd.alloc(k.size());
-        OF2D_HIP(hipMemcpy(kf.p, f.data(), sizeof(float) * f.size(), hipMemcpyHostToDevice));
-        OF2D_HIP(hipMemcpy(kd.p, k.data(), sizeof(double) * k.size(), hipMemcpyHostToDevice));
-        wfull = of2d::full_weight(k, kw);
-        const std::vector<float> g = of2d::gaussian_marginals(k, kw);
-        gs.alloc(g.size());
-        OF2D_HIP(hipMemcpy(gs.p, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
-    }
-};
-template <class F>
-int prim(bool args_ok, F &&f) {
-    if (!args_ok) return OF2D_ERR_INVALID_ARGUMENT;
-    std::string err;
-    const int rc = guarded(err, f);
-    if (rc != OF2D_OK) g_gateway_err = err;
-    return rc;
-}
-}  // namespace
-
-extern "C" {
-
-int of2d_prim_warp(const float *src, const float *u, int dimx, int dimy, float *out) {
-    return prim(src && u && out && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float> s, d;
-        of2d::Field<float2> m;
-        upload(s, src, dimx, dimy);
-        upload(m, u, dimx, dimy);
-        upload(d, nullptr, dimx, dimy);
-        of2d::launch_warp(s.p, m.p, d.p, dimx, dimy, s.P, nullptr);
-        download(out, d.p, d.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_accumulate(const float *m_old, const float *v, int dimx, int dimy, float *out) {
-    return prim(m_old && v && out && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> mo, c, mn;
-        upload(mo, m_old, dimx, dimy);
-        upload(c, v, dimx, dimy);
-        upload(mn, nullptr, dimx, dimy);
-        of2d::launch_accumulate(mo.p, c.p, mn.p, dimx, dimy, mo.P, nullptr);
-        download(out, mn.p, mn.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_regrid(const float *m_old, const float *est, const float *Imov, int dimx, int dimy,
-                     float *m_new, float *est0, float *Iaux) {
-    return prim(m_old && est && Imov && m_new && est0 && Iaux && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> mo, e, e0, mn;
-        of2d::Field<float> im, ia;
-        upload(mo, m_old, dimx, dimy);
-        upload(e, est, dimx, dimy);
-        upload(e0, est, dimx, dimy);  // not zero: the launch has to clear it
-        upload(mn, nullptr, dimx, dimy);
-        upload(im, Imov, dimx, dimy);
-        upload(ia, nullptr, dimx, dimy);
-        of2d::launch_regrid(mo.p, e.p, e0.p, mn.p, im.p, ia.p, dimx, dimy, mo.P, nullptr);
-        download(m_new, mn.p, mn.P, dimx, dimy);
-        download(est0, e0.p, e0.P, dimx, dimy);
-        download(Iaux, ia.p, ia.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_compose_zero(const float *v, int dimx, int nrows, int row0, int dimy, float *out) {
-    return prim(v && out && dimx > 0 && nrows > 0 && row0 >= 0 && row0 + nrows <= dimy, [&] {
-        of2d::Field<float2> c, o;
-        upload(c, v, dimx, nrows);
-        upload(o, nullptr, dimx, nrows);
-        of2d::launch_compose_zero(c.p, o.p, dimx, nrows, c.P, row0, dimy, nullptr);
-        download(out, o.p, o.P, dimx, nrows);
-    });
-}
-
-int of2d_prim_add_motion(const float *a, const float *b, int dimx, int dimy, float *out) {
-    return prim(a && b && out && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> x, y, o;
-        upload(x, a, dimx, dimy);
-        upload(y, b, dimx, dimy);
-        upload(o, nullptr, dimx, dimy);
-        of2d::launch_add_motion(x.p, y.p, o.p, dimx, dimy, x.P, nullptr);
-        download(out, o.p, o.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_resample(int what, const float *in, int dxi, int dyi, float *out, int dxo, int dyo) {
-    return prim(in && out && dxi > 0 && dyi > 0 && what >= 0 && what <= 2, [&] {
-        // the launches refuse the sizes the reference refuses, before any field
-        if (what == 0) {
-            of2d::Field<float> a, o;
-            if (dxo > 0 && dyo > 0) {
-                upload(a, in, dxi, dyi);
-                upload(o, out, dxo, dyo);
-            }
-            of2d::launch_downsample_image(a.p, dxi, dyi, a.P, o.p, dxo, dyo, o.P, nullptr);
-            download(out, o.p, o.P, dxo, dyo);
-            return;
-        }
-        of2d::Field<float2> a, o;
-        if (dxo > 0 && dyo > 0) {
-            upload(a, in, dxi, dyi);
-            upload(o, out, dxo, dyo);
-        }
-        if (what == 1)
-            of2d::launch_downsample_motion(a.p, dxi, dyi, a.P, o.p, dxo, dyo, o.P, nullptr);
-        else
-            of2d::launch_upsample_motion(a.p, dxi, dyi, a.P, o.p, dxo, dyo, o.P, nullptr);
-        download(out, o.p, o.P, dxo, dyo);
-    });
-}
-
-int of2d_prim_gradients(const float *Iref, const float *Iaux, int dimx, int dimy, int row0,
-                        int nrows, float *dI, float *It) {
-    return prim(Iref && Iaux && dI && It && dimx > 0 && nrows > 0 && row0 >= 0 &&
-                    row0 + nrows <= dimy,
-                [&] {
-                    // the slab's rows, and in its ghost j-lines the neighbours' image rows
-                    of2d::Field<float> r, a, t;
-                    of2d::Field<float2> g;
-                    upload(r, Iref + (size_t)row0 * dimx, dimx, nrows);
-                    upload(a, nullptr, dimx, nrows);
-                    upload(g, nullptr, dimx, nrows);
-                    upload(t, nullptr, dimx, nrows);
-                    const int lo = row0 > 0 ? row0 - 1 : row0;
-                    const int hi = row0 + nrows < dimy ? row0 + nrows + 1 : row0 + nrows;
-                    const size_t row = (size_t)dimx * sizeof(float);
-                    OF2D_HIP(hipMemcpy2D(a.p + (long)(lo - row0) * a.P, (size_t)a.P * sizeof(float),
-                                         Iaux + (size_t)lo * dimx, row, row, hi - lo,
-                                         hipMemcpyHostToDevice));
-                    of2d::launch_gradients_rows(r.p, a.p, g.p, t.p, dimx, nrows, r.P, row0, dimy,
-                                                nullptr);
-                    download(dI, g.p, g.P, dimx, nrows);
-                    download(It, t.p, t.P, dimx, nrows);
-                });
-}
-
-int of2d_prim_demons_force(const float *Iref, const float *Imov, const float *u, int dimx,
-                           int dimy, float sigma_i, float sigma_x, float *corr,
-                           unsigned *status) {
-    return prim(Iref && Imov && u && corr && status && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float> r, m;
-        of2d::Field<float2> f, c;
-        upload(r, Iref, dimx, dimy);
-        upload(m, Imov, dimx, dimy);
-        upload(f, u, dimx, dimy);
-        upload(c, nullptr, dimx, dimy);
-        StatusWord st;
-        // Demons.cpp:48-49
-        of2d::launch_demons_force(r.p, m.p, f.p, c.p, dimx, dimy, r.P, sigma_i * sigma_i,
-                                  sigma_x * sigma_x, st.w.p, nullptr);
-        download(corr, c.p, c.P, dimx, dimy);
-        *status = st.read();
-    });
-}
-
-int of2d_prim_smooth_compose(const float *corr, const float *u, int dimx, int dimy, int kw,
-                             float sigma, int mode, float *out, double *wfull) {
-    int path = 0;
-    return of2d_prim_smooth_compose_m(corr, u, dimx, dimy, kw, sigma, mode, out, wfull, 0, &path);
-}
-
-int of2d_prim_smooth_compose_m(const float *corr, const float *u, int dimx, int dimy, int kw,
-                               float sigma, int mode, float *out, double *wfull, int method,
-                               int *path) {
-    return prim(corr && u && out && dimx > 0 && dimy > 0 && kw >= 1 && mode >= 0 && mode <= 3 &&
-                    path && (method == 0 || method == 1),
-                [&] {
-                    of2d::Field<float2> c, f, o;
-                    upload(c, corr, dimx, dimy);
-                    upload(f, u, dimx, dimy);
-                    upload(o, nullptr, dimx, dimy);
-                    DeviceGaussian g(kw, sigma);
-                    if (wfull) *wfull = g.wfull;
-                    *path = of2d::launch_smooth_compose(c.p, f.p, o.p, dimx, dimy, c.P, g.kf.p,
-                                                        g.kd.p, kw, g.wfull, mode, nullptr,
-                                                        g.factors(method));
-                    download(out, o.p, o.P, dimx, dimy);
-                });
-}
-
-int of2d_prim_smooth_norm(const float *umid, const float *prev, int dimx, int dimy, int kw,
-                          float sigma, float *out, double *sums) {
-    int path = 0;
-    return of2d_prim_smooth_norm_m(umid, prev, dimx, dimy, kw, sigma, out, sums, 0, &path);
-}
-
-int of2d_prim_smooth_norm_m(const float *umid, const float *prev, int dimx, int dimy, int kw,
-                            float sigma, float *out, double *sums, int method, int *path) {
-    return prim(umid && prev && out && dimx > 0 && dimy > 0 && kw >= 1 && path &&
-                    (method == 0 || method == 1), [&] {
-        of2d::Field<float2> m, p, o;
-        upload(m, umid, dimx, dimy);
-        upload(p, prev, dimx, dimy);
-        upload(o, nullptr, dimx, dimy);
-        DeviceGaussian g(kw, sigma);
-        const int nb = of2d::conv_nblocks(dimx, dimy);
-        of2d::DevArray<double> part, red;
-        part.alloc(2 * (size_t)nb);
-        red.alloc(2);
-        // sums: the Logger partials reduced as the fp64 Logger mode reduces
-        // them; none: the launch of the default mode, without partials
-        *path = of2d::launch_smooth_norm(m.p, p.p, o.p, dimx, dimy, m.P, g.kf.p, g.kd.p, kw,
-                                         g.wfull, sums ? part.p : nullptr, nullptr,
-                                         g.factors(method));
-        if (sums) {
-            of2d::launch_reduce_partials(part.p, nb, 1, red.p, nullptr);
-            OF2D_HIP(hipStreamSynchronize(nullptr));
-            OF2D_HIP(hipMemcpy(sums, red.p, 2 * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        download(out, o.p, o.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_demons_update(const float *Iref, const float *Imov, const float *u, int dimx,
-                            int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
-                            int mode, float *out, unsigned *status) {
-    int path = 0;
-    return of2d_prim_demons_update_m(Iref, Imov, u, dimx, dimy, sigma_i, sigma_x, kw, sigma_fluid,
-                                     mode, out, status, 0, &path);
-}
-
-int of2d_prim_demons_update_m(const float *Iref, const float *Imov, const float *u, int dimx,
-                              int dimy, float sigma_i, float sigma_x, int kw, float sigma_fluid,
-                              int mode, float *out, unsigned *status, int method, int *path) {
-    return prim(Iref && Imov && u && out && status && dimx > 0 && dimy > 0 && kw >= 1 &&
-                    mode >= 0 && mode <= 3 && path && (method == 0 || method == 1),
-                [&] {
-                    of2d::Field<float> r, m;
-                    of2d::Field<float2> f, c, o;
-                    upload(r, Iref, dimx, dimy);
-                    upload(m, Imov, dimx, dimy);
-                    upload(f, u, dimx, dimy);
-                    upload(c, nullptr, dimx, dimy);
-                    upload(o, nullptr, dimx, dimy);
-                    DeviceGaussian g(kw, sigma_fluid);
-                    StatusWord st;
-                    *path = of2d::launch_demons_update(
-                        r.p, m.p, f.p, c.p, o.p, dimx, dimy, r.P, sigma_i * sigma_i,
-                        sigma_x * sigma_x, g.kf.p, g.kd.p, kw, g.wfull, mode, st.w.p, nullptr,
-                        g.factors(method));
-                    download(out, o.p, o.P, dimx, dimy);
-                    *status = st.read();
-                });
-}
-
-int of2d_prim_motion_exp(float *f, int dimx, int dimy, float sigma_i, float sigma_x, int *nsq,
-                         unsigned *status) {
-    return prim(f && nsq && status && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> a, b;
-        upload(a, f, dimx, dimy);
-        upload(b, nullptr, dimx, dimy);
-        constexpr int nparts = 256;  // Registration::loop_demons
-        of2d::DevArray<float> part, maxabs;
-        of2d::DevArray<int> n;
-        part.alloc(nparts);
-        maxabs.alloc(1);
-        n.alloc(1);
-        StatusWord st;
-        float2 *res = nullptr;
-        of2d::launch_motion_exp(a.p, b.p, dimx, dimy, a.P,
-                                of2d::exp_squarings_bound(sigma_i * sigma_i, sigma_x * sigma_x),
-                                part.p, nparts, n.p, maxabs.p, st.w.p, &res, nullptr);
-        download(f, res, a.P, dimx, dimy);
-        OF2D_HIP(hipMemcpy(nsq, n.p, sizeof(int), hipMemcpyDeviceToHost));
-        *status = st.read();
-    });
-}
-
-int of2d_prim_d2f(const double *in, int dimx, int dimy, float *out) {
-    return prim(in && out && dimx > 0 && dimy > 0, [&] {
-        of2d::DevArray<double> d;
-        d.alloc((size_t)dimx * dimy);
-        OF2D_HIP(hipMemcpy(d.p, in, sizeof(double) * d.n, hipMemcpyHostToDevice));
-        of2d::Field<float> o;
-        upload(o, nullptr, dimx, dimy);
-        of2d::launch_d2f(d.p, dimx, dimy, o.p, o.P, 0, nullptr);
-        download(out, o.p, o.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_f2d(const float *in, int dimx, int dimy, double *out) {
-    return prim(in && out && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float> a;
-        upload(a, in, dimx, dimy);
-        of2d::DevArray<double> d;
-        d.alloc((size_t)dimx * dimy);
-        of2d::launch_f2d(a.p, a.P, dimx, dimy, d.p, nullptr);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(out, d.p, sizeof(double) * d.n, hipMemcpyDeviceToHost));
-    });
-}
-
-int of2d_prim_motion_to_planar(const float *m, int dimx, int dimy, double *out) {
-    return prim(m && out && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> a;
-        upload(a, m, dimx, dimy);
-        of2d::DevArray<double> d;
-        d.alloc(2 * (size_t)dimx * dimy);
-        of2d::launch_motion_to_planar(a.p, a.P, dimx, dimy, d.p, nullptr);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(out, d.p, sizeof(double) * d.n, hipMemcpyDeviceToHost));
-    });
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ Curvature primitives
-namespace {
-// a level of the solver with nothing but Curvature's buffers, tables and
-// eigenvalues (as of2d_dct2d)
-void curvature_level(of2d::Level &L, int dimx, int dimy, float alpha, float tau, int method) {
-    L.dx = dimx;
-    L.dy = dimy;
-    L.P = of2d::pitch_for(dimx);
-    of2d::solvers::alloc_level(L, OF2D_REG_CURVATURE);
-    of2d::solvers::build_curvature(L, alpha, tau, method, nullptr);
-}
-void upload_plane(double *dev, int P, const double *host, int dimx, int dimy) {
-    const size_t row = (size_t)dimx * sizeof(double);
-    OF2D_HIP(hipMemcpy2D(dev, (size_t)P * sizeof(double), host, row, row, dimy,
-                         hipMemcpyHostToDevice));
-}
-void download_plane(double *host, const double *dev, int P, int dimx, int dimy) {
-    const size_t row = (size_t)dimx * sizeof(double);
-    OF2D_HIP(hipStreamSynchronize(nullptr));
-    OF2D_HIP(hipMemcpy2D(host, row, dev, (size_t)P * sizeof(double), row, dimy,
-                         hipMemcpyDeviceToHost));
-}
-}  // namespace
-
-extern "C" {
-
-int of2d_prim_curv_rhs(const float *u, const float *dI, const float *It, float tau, int dimx,
-                       int dimy, double *out_x, double *out_y) {
-    return prim(u && dI && It && out_x && out_y && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> m, g;
-        of2d::Field<float> t;
-        upload(m, u, dimx, dimy);
-        upload(g, dI, dimx, dimy);
-        upload(t, It, dimx, dimy);
-        const long plane = (long)m.P * dimy;
-        of2d::DevArray<double> X;
-        X.alloc(2 * (size_t)plane);
-        of2d::launch_curv_rhs(m.p, g.p, t.p, tau, dimx, dimy, m.P, X.p, plane, nullptr);
-        download_plane(out_x, X.p, m.P, dimx, dimy);
-        download_plane(out_y, X.p + plane, m.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_curv_eigen(int dimx, int dimy, float alpha, float tau, int method, double *out) {
-    return prim(out && dimx > 0 && dimy > 0 && (method == 0 || method == 1), [&] {
-        of2d::Level L;
-        curvature_level(L, dimx, dimy, alpha, tau, method);
-        download_plane(out, L.cE.p, L.P, dimx, dimy);
-    });
-}
-
-int of2d_prim_curv_dct2d(double *ax, double *ay, int dimx, int dimy, int kind, int method,
-                         int with_eig, float alpha, float tau, int *paths) {
-    return prim(ax && ay && paths && dimx > 0 && dimy > 0 && (kind == 10 || kind == 1) &&
-                    (method == 0 || method == 1) && (with_eig == 0 || (with_eig == 1 && kind == 10)),
-                [&] {
-                    of2d::Level L;
-                    curvature_level(L, dimx, dimy, alpha, tau, method);
-                    paths[0] = L.cpath & 1;
-                    paths[1] = (L.cpath >> 1) & 1;
-                    const long plane = (long)L.P * dimy;
-                    upload_plane(L.cbuf[0].p, L.P, ax, dimx, dimy);
-                    upload_plane(L.cbuf[0].p + plane, L.P, ay, dimx, dimy);
-                    const double *res = of2d::solvers::curvature_dct2d(
-                        L, kind == 1, L.cbuf[0].p, L.cbuf[1].p, with_eig ? L.cE.p : nullptr,
-                        nullptr);
-                    download_plane(ax, res, L.P, dimx, dimy);
-                    download_plane(ay, res + plane, L.P, dimx, dimy);
-                });
-}
-
-int of2d_prim_curv_construct(const double *zx, const double *zy, const float *u, float div,
-                             int dimx, int dimy, float *out, double *sums) {
-    return prim(zx && zy && u && out && sums && dimx > 0 && dimy > 0, [&] {
-        of2d::Field<float2> m, o;
-        upload(m, u, dimx, dimy);
-        upload(o, nullptr, dimx, dimy);
-        const long plane = (long)m.P * dimy;
-        of2d::DevArray<double> Z, part;
-        Z.alloc(2 * (size_t)plane);
-        upload_plane(Z.p, m.P, zx, dimx, dimy);
-        upload_plane(Z.p + plane, m.P, zy, dimx, dimy);
-        const int nb = of2d::curv_nblocks(dimx, dimy);
-        part.alloc(2 * (size_t)nb);
-        of2d::launch_curv_construct(Z.p, plane, m.p, o.p, div, dimx, dimy, m.P, part.p, nullptr);
-        download(out, o.p, o.P, dimx, dimy);
-        std::vector<double> h(2 * (size_t)nb);
-        OF2D_HIP(hipMemcpy(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        sums[0] = sums[1] = 0.0;
-        for (int b = 0; b < nb; b++) {
-            sums[0] += h[2 * (size_t)b];
-            sums[1] += h[2 * (size_t)b + 1];
-        }
-    });
-}
-
 // ------------------------------------------------------------------ analysis
 }  // extern "C"
 
 namespace {
-// a refusal before any device work, with its reason for of2d_gateway_last_error
-// (and of2d_last_error of the context, where there is one)
-int refuse(of2d_ctx *ctx, const char *why) {
-    g_gateway_err = why;
-    if (ctx) ctx->err = why;
-    return OF2D_ERR_INVALID_ARGUMENT;
-}
 // the analysis of a context's motion: its own error string, mirrored for
 // of2d_gateway_last_error
 template <class F>
@@ -826,8 +207,7 @@ int of2d_field_jacobian(const float *u, int dimx, int dimy, float *jac, double *
         ds.alloc(5);
         of2d::launch_jacobian(f.p, dimx, dimy, f.P, j.p, part.p, ds.p, nullptr);
         if (jac) download(jac, j.p, j.P, dimx, dimy);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(stats, ds.p, 5 * sizeof(double), hipMemcpyDeviceToHost));
+        fetch(stats, ds.p, 5);
     });
 }
 
@@ -879,8 +259,7 @@ int of2d_image_similarity(const float *a, const float *b, int dimx, int dimy, do
         of2d::DevArray<double> ds;
         ds.alloc(2);
         of2d::launch_similarity(x.p, y.p, dimx, dimy, x.P, part.p, ds.p, nullptr);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(out, ds.p, 2 * sizeof(double), hipMemcpyDeviceToHost));
+        fetch(out, ds.p, 2);
     });
 }
 
@@ -888,419 +267,6 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
     if (!ctx || !Iref || !Imov || !out)
         return refuse(ctx, "of2d_quality: ctx, Iref, Imov or out is NULL");
     return analysis(ctx, [&] { ctx->reg->quality(Iref, Imov, out); });
-}
-
-int of2d_analysis_time_kernels(int dimx, int dimy, int nlaunch, double *us) {
-    if (!us || nlaunch <= 0) return refuse(nullptr, "of2d_analysis_time_kernels: us, nlaunch");
-    if (dimx < 2 || dimy < 2)
-        return refuse(nullptr, "analysis timing: the field needs dimx >= 2 and dimy >= 2");
-    return prim(true, [&] {
-        // the inverse's test field (tests/test_gpu_analysis.py), amplitude 3
-        std::vector<float> hu((size_t)dimx * dimy * 2);
-        const double tp = 6.283185307179586;
-        for (int j = 0; j < dimy; j++)
-            for (int i = 0; i < dimx; i++) {
-                float *p = &hu[((size_t)j * dimx + i) * 2];
-                p[0] = (float)(3.0 * sin(tp * i / dimx + 0.3) * cos(tp * j / dimy));
-                p[1] = (float)(2.1 * cos(2 * tp * i / dimx) * sin(tp * j / dimy + 0.5));
-            }
-        of2d::Field<float2> f, v0, v1;
-        of2d::Field<float> jm;
-        upload(f, hu.data(), dimx, dimy);
-        upload(v0, nullptr, dimx, dimy);
-        upload(v1, nullptr, dimx, dimy);
-        upload(jm, nullptr, dimx, dimy);
-        of2d::DevArray<of2d::JacPartial> part;
-        part.alloc((size_t)of2d::jacobian_nblocks(dimx, dimy));
-        of2d::DevArray<double> ds;
-        ds.alloc(5);
-        of2d::DevArray<unsigned> ctl;
-        ctl.alloc(of2d::invert_ctl_words(4));
-        // an iterate near the fixed point: the gather pattern of a real update
-        const of2d::InvertResult r =
-            of2d::invert_field(f.p, v0.p, v1.p, dimx, dimy, f.P, 4, 1e-3f, ctl.p, nullptr, nullptr);
-        float2 *vin = r.v, *vout = r.v == v0.p ? v1.p : v0.p;
-        hipEvent_t e0, e1;
-        OF2D_HIP(hipEventCreate(&e0));
-        OF2D_HIP(hipEventCreate(&e1));
-        for (int which = 0; which < 2; which++) {
-            for (int k = -1; k < nlaunch; k++) {  // k = -1: one untimed launch
-                if (k == 0) OF2D_HIP(hipEventRecord(e0, nullptr));
-                if (which == 0)
-                    of2d::launch_jacobian(f.p, dimx, dimy, f.P, jm.p, part.p, ds.p, nullptr);
-                else  // update 0 reads no control word: every launch does the work
-                    of2d::launch_invert_step(f.p, vin, vout, dimx, dimy, f.P, 0, 1e-3f, ctl.p, 4,
-                                             nullptr);
-            }
-            OF2D_HIP(hipEventRecord(e1, nullptr));
-            OF2D_HIP(hipEventSynchronize(e1));
-            float ms = 0.0f;
-            OF2D_HIP(hipEventElapsedTime(&ms, e0, e1));
-            us[which] = 1000.0 * (double)ms / nlaunch;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    });
-}
-
-// ------------------------------------------------------------------ SOR / Fluid / Elastic primitives
-}  // extern "C"
-
-namespace {
-constexpr unsigned kNoStop = 0x7f7f7f7fu;  // the stop word before any break (loop_fluid)
-
-// A level with nothing but the buffers solvers::alloc_level gives Elastic
-// (reg 2) or Fluid (reg 5), the 64-word status / control buffer of a context,
-// and the host side of the skewed working array and the hand-off granules.
-struct SorLevel {
-    of2d::Level L;
-    StatusWord st;
-    std::vector<float2> hvb;   // the whole vb allocation (from L.vb.base)
-    std::vector<unsigned> hH;  // every granule region
-    SorLevel(int dimx, int dimy, int reg) {
-        L.dx = dimx;
-        L.dy = dimy;
-        L.P = of2d::pitch_for(dimx);
-        of2d::solvers::alloc_level(L, reg);
-        hvb.assign(2 * L.vb.count, make_float2(0.0f, 0.0f));
-        hH.assign(2 * L.sorH.n, 0u);
-    }
-    float2 &cell(long k) { return hvb[(size_t)(2L * L.P + k)]; }  // k: sor_v / sor_b
-    unsigned *granule0(int j) { return &hH[4 * (size_t)(of2d::kSorPadRows + j)]; }
-    // every word of both allocations (the padding cells, the never-published
-    // granule rows), before put() writes the image's cells
-    void fill(unsigned word) {
-        float f;
-        memcpy(&f, &word, sizeof f);
-        std::fill(hvb.begin(), hvb.end(), make_float2(f, f));
-        std::fill(hH.begin(), hH.end(), word);
-    }
-    // v and b of the image pixels (a null plane keeps the fill) and the
-    // region-0 granules: column 0 of v tagged with `epoch` (gran non-null: those
-    // dimy x 4 words instead)
-    void put(const float *v, const float *b, unsigned epoch, const unsigned *gran = nullptr) {
-        const float2 *v2 = reinterpret_cast<const float2 *>(v);
-        const float2 *b2 = reinterpret_cast<const float2 *>(b);
-        for (int j = 0; j < L.dy; j++) {
-            for (int i = 0; i < L.dx; i++) {
-                if (v) cell(of2d::sor_v(i, j, L.P)) = v2[(size_t)j * L.dx + i];
-                if (b) cell(of2d::sor_b(i, j, L.P)) = b2[(size_t)j * L.dx + i];
-            }
-            unsigned *g = granule0(j);
-            if (gran) {
-                memcpy(g, gran + 4 * (size_t)j, 16);
-            } else {
-                memcpy(g, &cell(of2d::sor_v(0, j, L.P)), 8);
-                g[2] = g[3] = epoch;
-            }
-        }
-        OF2D_HIP(hipMemcpy(L.vb.base, hvb.data(), L.vb.bytes(), hipMemcpyHostToDevice));
-        OF2D_HIP(hipMemcpy(L.sorH.p, hH.data(), hH.size() * sizeof(unsigned),
-                           hipMemcpyHostToDevice));
-    }
-    // the region-0 granules' tags for the next sweep (their values, column 0
-    // of v, are never relaxed)
-    void retag(unsigned epoch) {
-        for (int j = 0; j < L.dy; j++) granule0(j)[2] = granule0(j)[3] = epoch;
-        OF2D_HIP(hipMemcpy(reinterpret_cast<unsigned *>(L.sorH.p) + 4 * (size_t)of2d::kSorPadRows,
-                           granule0(0), 16 * (size_t)L.dy, hipMemcpyHostToDevice));
-    }
-    void control(unsigned status, unsigned stop, unsigned regrid, unsigned mcur) {
-        unsigned w[64] = {};
-        w[0] = status;
-        w[of2d::kStopWord] = stop;
-        w[of2d::kFluidRegridWord] = regrid;
-        w[of2d::kFluidMcurWord] = mcur;
-        OF2D_HIP(hipMemcpy(st.w.p, w, sizeof w, hipMemcpyHostToDevice));
-    }
-    void words(unsigned *out) {  // status, stop, regrid, mcur
-        unsigned w[64];
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(w, st.w.p, sizeof w, hipMemcpyDeviceToHost));
-        out[0] = w[0];
-        out[1] = w[of2d::kStopWord];
-        out[2] = w[of2d::kFluidRegridWord];
-        out[3] = w[of2d::kFluidMcurWord];
-    }
-    // the unskewed planes and the region-0 granules (dimy x 4 words)
-    void get(float *v, float *b, unsigned *gran) {
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-        OF2D_HIP(hipMemcpy(hvb.data(), L.vb.base, L.vb.bytes(), hipMemcpyDeviceToHost));
-        OF2D_HIP(hipMemcpy(hH.data(), L.sorH.p, hH.size() * sizeof(unsigned),
-                           hipMemcpyDeviceToHost));
-        float2 *v2 = reinterpret_cast<float2 *>(v), *b2 = reinterpret_cast<float2 *>(b);
-        for (int j = 0; j < L.dy; j++) {
-            for (int i = 0; i < L.dx; i++) {
-                if (v) v2[(size_t)j * L.dx + i] = cell(of2d::sor_v(i, j, L.P));
-                if (b) b2[(size_t)j * L.dx + i] = cell(of2d::sor_b(i, j, L.P));
-            }
-            if (gran) memcpy(gran + 4 * (size_t)j, granule0(j), 16);
-        }
-    }
-};
-template <class T>
-void fetch(T *host, const T *dev, size_t n) {
-    OF2D_HIP(hipStreamSynchronize(nullptr));
-    OF2D_HIP(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
-}
-// a FluidReport where the Fluid loop keeps its ring: host memory the device
-// writes; every byte 0xAB until a kernel writes it
-struct HostReport {
-    of2d::FluidReport *p = nullptr;
-    HostReport() {
-        OF2D_HIP(hipHostMalloc(&p, sizeof(of2d::FluidReport),
-                               hipHostMallocCoherent | hipHostMallocMapped));
-        memset(p, 0xAB, sizeof(of2d::FluidReport));
-    }
-    ~HostReport() {
-        if (p) (void)hipHostFree(p);
-    }
-    HostReport(const HostReport &) = delete;
-    HostReport &operator=(const HostReport &) = delete;
-};
-}  // namespace
-
-extern "C" {
-
-int of2d_prim_sor_pack(const float *u, const float *dI, const float *It, const float *v0,
-                       int elastic, int dimx, int dimy, unsigned epoch, float *v, float *b,
-                       unsigned *gran) {
-    if (!u || !dI || !It || !v || !b || !gran)
-        return refuse(nullptr, "of2d_prim_sor_pack: u, dI, It, v, b or gran is NULL");
-    if (elastic != 0 && elastic != 1) return refuse(nullptr, "of2d_prim_sor_pack: elastic is 0 or 1");
-    if (!elastic && !v0)
-        return refuse(nullptr, "of2d_prim_sor_pack: the force-only mode takes the prior v plane");
-    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_sor_pack: dimx, dimy < 1");
-    return prim(true, [&] {
-        SorLevel S(dimx, dimy, elastic ? 2 : 5);
-        of2d::Field<float2> m, g;
-        of2d::Field<float> t;
-        upload(m, u, dimx, dimy);
-        upload(g, dI, dimx, dimy);
-        upload(t, It, dimx, dimy);
-        S.put(elastic ? nullptr : v0, nullptr, 0u);  // stale granules: tag 0
-        of2d::launch_sor_pack(S.L.vb.p, m.p, g.p, t.p, elastic ? m.p : nullptr, dimx, dimy,
-                              S.L.P, S.L.sorH.p, epoch, nullptr);
-        S.get(v, b, gran);
-    });
-}
-
-int of2d_prim_regrid_pack(const float *Iref, const float *Iaux, const float *v0, int regridded,
-                          int dimx, int dimy, unsigned epoch, float *dI, float *It, float *b,
-                          unsigned *gran) {
-    if (!Iref || !Iaux || !v0 || !dI || !It || !b || !gran)
-        return refuse(nullptr, "of2d_prim_regrid_pack: Iref, Iaux, v0, dI, It, b or gran is NULL");
-    if (regridded != 0 && regridded != 1)
-        return refuse(nullptr, "of2d_prim_regrid_pack: regridded is 0 or 1");
-    if (dimx < 2 || dimy < 2)
-        return refuse(nullptr, "of2d_prim_regrid_pack: the gradients need dimx >= 2 and dimy >= 2");
-    return prim(true, [&] {
-        SorLevel S(dimx, dimy, 5);
-        of2d::Field<float> ir, ia, t;
-        of2d::Field<float2> g;
-        upload(ir, Iref, dimx, dimy);
-        upload(ia, Iaux, dimx, dimy);
-        upload(g, dI, dimx, dimy);
-        upload(t, It, dimx, dimy);
-        S.put(v0, b, 0u, gran);
-        S.control(0u, kNoStop, (unsigned)regridded, 0u);
-        of2d::launch_regrid_pack(ir.p, ia.p, g.p, t.p, S.L.vb.p, dimx, dimy, S.L.P, S.L.sorH.p,
-                                 epoch, nullptr, of2d::FluidCtl{S.st.w.p, 1});
-        download(dI, g.p, g.P, dimx, dimy);
-        download(It, t.p, t.P, dimx, dimy);
-        S.get(nullptr, b, gran);
-    });
-}
-
-int of2d_prim_sor_sweep(const float *v, const float *b, const float *u, int dimx, int dimy,
-                        float mu, float lambda, float omega, int method, int nsweeps,
-                        int zero_est, int skip_at, int poison, unsigned poison_word,
-                        float *v_out, float *R, float *scal, float *part, int *path,
-                        unsigned long long *words, unsigned *status) {
-    if (!v || !b || !v_out || !words || !status || !path)
-        return refuse(nullptr, "of2d_prim_sor_sweep: v, b, v_out, path, words or status is NULL");
-    if (method != 0 && method != 1)
-        return refuse(nullptr, "of2d_prim_sor_sweep: method is 0 (launch_sor) or 1 "
-                               "(launch_sor_increment)");
-    if (method == 1 && (!u || !R || !scal || !part))
-        return refuse(nullptr, "of2d_prim_sor_sweep: method 1 takes u and returns R, scal, part");
-    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_sor_sweep: dimx, dimy < 1");
-    if (nsweeps < 1) return refuse(nullptr, "of2d_prim_sor_sweep: nsweeps < 1");
-    if (skip_at < -1 || skip_at >= nsweeps)
-        return refuse(nullptr, "of2d_prim_sor_sweep: skip_at is -1 or a sweep of the call");
-    return prim(true, [&] {
-        SorLevel S(dimx, dimy, method ? 5 : 2);
-        of2d::Level &L = S.L;
-        of2d::Field<float2> m;
-        of2d::DevArray<float> sc;
-        sc.alloc(4);
-        upload(m, method ? u : nullptr, dimx, dimy);
-        if (poison) S.fill(poison_word);
-        const unsigned ep0 = 1u;
-        S.put(v, b, ep0);
-        // the stop word of a loop that broke at iteration 0: sweep skip_at runs
-        // as iteration 1, every other sweep as iteration 0
-        S.control(0u, skip_at >= 0 ? 0u : kNoStop, zero_est ? 1u : 0u, 0u);
-        *path = method ? (of2d::sor_increment_plan(dimx, dimy) > 0 ? 1 : 0) : 0;
-        for (int s = 0; s < nsweeps; s++) {
-            const of2d::FluidCtl c{S.st.w.p, s == skip_at ? 1 : 0};
-            if (s) S.retag(ep0 + (unsigned)s);
-            if (method)
-                of2d::launch_sor_increment(L.vb.p, dimx, dimy, L.P, mu, lambda, omega, L.sorH.p,
-                                           ep0 + (unsigned)s, L.sorTicket.p, L.sorCtr.p, m.p,
-                                           L.increment.p, L.part.p, sc.p, S.st.w.p, nullptr, c);
-            else
-                of2d::launch_sor(L.vb.p, dimx, dimy, L.P, mu, lambda, omega, L.sorH.p,
-                                 ep0 + (unsigned)s, L.sorTicket.p, S.st.w.p, nullptr, c);
-        }
-        S.get(v_out, nullptr, nullptr);
-        unsigned w[4];
-        S.words(w);
-        *status = w[0];
-        unsigned t = 0;
-        fetch(&t, L.sorTicket.p, 1);
-        words[0] = t;
-        words[1] = words[2] = 0;
-        if (method) {
-            fetch(words + 1, L.sorCtr.p, 2);
-            download(R, L.increment.p, L.increment.P, dimx, dimy);
-            fetch(scal, sc.p, 2);
-            fetch(part, L.part.p, (size_t)of2d::increment_nblocks(dimx, dimy));
-        }
-    });
-}
-
-int of2d_prim_fluid_increment(const float *u, const float *v, int dimx, int dimy, int zero_est,
-                              float *R, float *scal, float *part) {
-    if (!u || !v || !R || !scal || !part)
-        return refuse(nullptr, "of2d_prim_fluid_increment: u, v, R, scal or part is NULL");
-    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_fluid_increment: dimx, dimy < 1");
-    return prim(true, [&] {
-        SorLevel S(dimx, dimy, 5);
-        of2d::Level &L = S.L;
-        of2d::Field<float2> m;
-        of2d::DevArray<float> sc;
-        sc.alloc(4);
-        upload(m, u, dimx, dimy);
-        S.put(v, nullptr, 0u);
-        S.control(0u, kNoStop, zero_est ? 1u : 0u, 0u);
-        of2d::launch_increment(m.p, L.vb.p, L.increment.p, dimx, dimy, L.P, L.part.p, sc.p,
-                               nullptr, of2d::FluidCtl{S.st.w.p, 0});
-        download(R, L.increment.p, L.increment.P, dimx, dimy);
-        fetch(scal, sc.p, 2);
-        fetch(part, L.part.p, (size_t)of2d::increment_nblocks(dimx, dimy));
-    });
-}
-
-int of2d_prim_fluid_step(const float *u, const float *R, const float *prev, const float *dI,
-                         const float *It, const float *v0, float dt, int zero_est, int dimx,
-                         int dimy, unsigned epoch, float *uo, double *sums, float *jmin, float *b,
-                         unsigned *gran) {
-    if (!u || !R || !dI || !It || !v0 || !uo || !sums || !jmin || !b || !gran)
-        return refuse(nullptr, "of2d_prim_fluid_step: an array other than prev is NULL");
-    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_fluid_step: dimx, dimy < 1");
-    return prim(true, [&] {
-        SorLevel S(dimx, dimy, 5);
-        of2d::Level &L = S.L;
-        of2d::Field<float2> m, r, o, pv, g;
-        of2d::Field<float> t;
-        upload(m, u, dimx, dimy);
-        upload(r, R, dimx, dimy);
-        upload(o, nullptr, dimx, dimy);
-        if (prev) upload(pv, prev, dimx, dimy);
-        upload(g, dI, dimx, dimy);
-        upload(t, It, dimx, dimy);
-        const int nb = of2d::increment_nblocks(dimx, dimy);
-        of2d::DevArray<double> lpart;
-        of2d::DevArray<float> sc;
-        lpart.alloc(2 * (size_t)nb);
-        sc.alloc(4);
-        const float s[2] = {0.0f, dt};
-        OF2D_HIP(hipMemcpy(sc.p, s, sizeof s, hipMemcpyHostToDevice));
-        S.put(v0, nullptr, 0u);
-        S.control(0u, kNoStop, zero_est ? 1u : 0u, 0u);
-        HostReport rep;
-        // the next sweep's epoch, as loop_fluid passes it
-        of2d::launch_fluid_step(m.p, r.p, o.p, prev ? pv.p : nullptr, sc.p, g.p, t.p, L.vb.p,
-                                dimx, dimy, L.P, L.sorH.p, epoch + 1, lpart.p, L.part.p, nullptr,
-                                of2d::FluidCtl{S.st.w.p, 0});
-        of2d::launch_fluid_report(lpart.p, nb, L.part.p, sc.p, S.st.w.p, rep.p, nullptr);
-        download(uo, o.p, o.P, dimx, dimy);
-        S.get(nullptr, b, gran);
-        sums[0] = rep.p->sums[0];
-        sums[1] = rep.p->sums[1];
-        *jmin = rep.p->jmin;
-    });
-}
-
-int of2d_prim_fluid_decide(const double *lpart, const float *jpart, int nb, const float *seq,
-                           double npx, int fixed, int it, const float *scal, unsigned *words,
-                           double *sums, float *repf, unsigned *repu) {
-    if (!lpart || !jpart || !scal || !words || !sums || !repf || !repu)
-        return refuse(nullptr, "of2d_prim_fluid_decide: an array other than seq is NULL");
-    if (nb < 1) return refuse(nullptr, "of2d_prim_fluid_decide: nb < 1");
-    if (!(npx >= 1.0)) return refuse(nullptr, "of2d_prim_fluid_decide: npx < 1");
-    if (it < 0) return refuse(nullptr, "of2d_prim_fluid_decide: it < 0");
-    return prim(true, [&] {
-        StatusWord st;
-        of2d::DevArray<double> lp;
-        of2d::DevArray<float> jp, sq, sc;
-        lp.alloc(2 * (size_t)nb);
-        jp.alloc((size_t)nb);
-        sq.alloc(2);
-        sc.alloc(4);
-        OF2D_HIP(hipMemcpy(lp.p, lpart, 2 * (size_t)nb * sizeof(double), hipMemcpyHostToDevice));
-        OF2D_HIP(hipMemcpy(jp.p, jpart, (size_t)nb * sizeof(float), hipMemcpyHostToDevice));
-        if (seq) OF2D_HIP(hipMemcpy(sq.p, seq, 2 * sizeof(float), hipMemcpyHostToDevice));
-        const float s[3] = {scal[0], scal[1], repf[6]};  // scal[2]: the caller's marker
-        OF2D_HIP(hipMemcpy(sc.p, s, sizeof s, hipMemcpyHostToDevice));
-        unsigned w[64] = {};
-        w[0] = words[0];
-        w[of2d::kStopWord] = words[1];
-        w[of2d::kFluidRegridWord] = words[2];
-        w[of2d::kFluidMcurWord] = words[3];
-        OF2D_HIP(hipMemcpy(st.w.p, w, sizeof w, hipMemcpyHostToDevice));
-        HostReport rep;
-        of2d::launch_fluid_report_decide(lp.p, nb, jp.p, sc.p, seq ? sq.p : nullptr, npx,
-                                         fixed != 0, rep.p, nullptr, of2d::FluidCtl{st.w.p, it});
-        fetch(w, st.w.p, 64);
-        words[0] = w[0];
-        words[1] = w[of2d::kStopWord];
-        words[2] = w[of2d::kFluidRegridWord];
-        words[3] = w[of2d::kFluidMcurWord];
-        const of2d::FluidReport &r = *rep.p;
-        sums[0] = r.sums[0];
-        sums[1] = r.sums[1];
-        const float f[6] = {r.maxabs, r.dt, r.jmin, r.seq[0], r.seq[1], r.err};
-        memcpy(repf, f, sizeof f);
-        fetch(repf + 6, sc.p + 2, 1);
-        repu[0] = r.status;
-        repu[1] = r.flags;
-    });
-}
-
-int of2d_prim_elastic_logger(const float *v, const float *prev, int dimx, int dimy, float *u,
-                             float *prev_out, double *sums) {
-    if (!v || !prev || !u || !prev_out || !sums)
-        return refuse(nullptr, "of2d_prim_elastic_logger: v, prev, u, prev_out or sums is NULL");
-    if (dimx < 1 || dimy < 1) return refuse(nullptr, "of2d_prim_elastic_logger: dimx, dimy < 1");
-    return prim(true, [&] {
-        SorLevel S(dimx, dimy, 2);
-        of2d::Level &L = S.L;
-        of2d::Field<float2> est, pv;
-        upload(est, nullptr, dimx, dimy);
-        upload(pv, prev, dimx, dimy);
-        const int nb = of2d::increment_nblocks(dimx, dimy);
-        of2d::DevArray<double> part, ds;
-        part.alloc(2 * (size_t)nb);
-        ds.alloc(2);
-        S.put(v, nullptr, 0u);
-        of2d::launch_logger(L.vb.p, est.p, pv.p, dimx, dimy, L.P, part.p, nullptr);
-        of2d::launch_reduce_partials(part.p, nb, 1, ds.p, nullptr);
-        download(u, est.p, est.P, dimx, dimy);
-        download(prev_out, pv.p, pv.P, dimx, dimy);
-        fetch(sums, ds.p, 2);
-    });
 }
 
 // ------------------------------------------------------------------ gateway
@@ -1517,10 +483,6 @@ const char *of2d_batch_last_error(const of2d_batch *b) {
 
 // ------------------------------------------------------------------ device-resident I/O
 namespace {
-// the axes of a call's array: pair, x, y, component (0: the axis is not used)
-struct Extents {
-    int n[4];
-};
 // "" or why the array is refused; no device work.  Unused axes' strides are
 // not looked at.
 std::string darray_refusal(const of2d_darray *a, const char *name, bool output, const Extents &e) {
@@ -1537,7 +499,9 @@ std::string darray_refusal(const of2d_darray *a, const char *name, bool output, 
     }
     return "";
 }
-of2d::DArrayView view_of(const of2d_darray *a, const Extents &e) {
+}  // namespace
+
+of2d::DArrayView of2d::capi::view_of(const of2d_darray *a, const Extents &e) {
     of2d::DArrayView v;
     v.ptr = a->ptr;
     v.f64 = a->dtype == OF2D_F64;
@@ -1547,20 +511,15 @@ of2d::DArrayView view_of(const of2d_darray *a, const Extents &e) {
     v.sc = e.n[3] > 0 ? a->stride[3] : 0;
     return v;
 }
-// an entry's arrays, checked in order; the first refusal is the message
-struct DArrayArg {
-    const of2d_darray *a;
-    const char *name;
-    bool output;
-    Extents e;
-};
-std::string first_refusal(const char *fn, std::initializer_list<DArrayArg> args) {
+std::string of2d::capi::first_refusal(const char *fn, std::initializer_list<DArrayArg> args) {
     for (const DArrayArg &g : args) {
         const std::string why = darray_refusal(g.a, g.name, g.output, g.e);
         if (!why.empty()) return std::string(fn) + ": " + why;
     }
     return "";
 }
+
+namespace {
 template <class F>
 int device_io(of2d_ctx *ctx, const char *fn, std::initializer_list<DArrayArg> args, F &&f) {
     if (!ctx) return refuse(nullptr, (std::string(fn) + ": ctx is NULL").c_str());
@@ -1577,17 +536,6 @@ int device_io(of2d_batch *b, const char *fn, std::initializer_list<DArrayArg> ar
         return OF2D_ERR_INVALID_ARGUMENT;
     }
     return guarded(b->err, f);
-}
-// dense host fields <-> npairs pitched fields (the primitives below)
-template <class T>
-void upload_pairs(of2d::batch::BField<T> &f, const float *host, int npairs, int dimx, int dimy) {
-    f.alloc(dimx, dimy, npairs);
-    const size_t row = (size_t)dimx * sizeof(T), P = (size_t)of2d::pitch_for(dimx);
-    const long stride = of2d::batch::pair_stride(dimx, dimy);
-    const size_t per = (size_t)dimx * dimy * (sizeof(T) / sizeof(float));
-    for (int k = 0; host && k < npairs; k++)
-        OF2D_HIP(hipMemcpy2D(f.p + k * stride, P * sizeof(T), host + k * per, row, row, dimy,
-                             hipMemcpyHostToDevice));
 }
 }  // namespace
 
@@ -1647,64 +595,6 @@ int of2d_batch_warp_device(of2d_batch *b, const of2d_darray *Imov, const of2d_da
                          b->b->warp_device(view_of(Imov, e), view_of(out, e),
                                            static_cast<hipStream_t>(stream));
                      });
-}
-
-// ---- one launch each of io_kernels.hip, on the null stream
-int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host) {
-    const Extents e = {{npairs, dimx, dimy, 0}};
-    const bool ok = out_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
-                    dimy > 0;
-    const std::string why =
-        ok ? first_refusal("of2d_prim_pack_image", {{in, "in", false, e}})
-           : std::string("of2d_prim_pack_image: out_host is NULL or a size is out of range");
-    if (!why.empty()) return refuse(nullptr, why.c_str());
-    return prim(true, [&] {
-        of2d::batch::BField<float> f;
-        upload_pairs(f, nullptr, npairs, dimx, dimy);
-        const long stride = of2d::batch::pair_stride(dimx, dimy);
-        const int P = of2d::pitch_for(dimx);
-        of2d::launch_pack_image(view_of(in, e), npairs, dimx, dimy, f.p, stride, P, nullptr);
-        for (int k = 0; k < npairs; k++)
-            download(out_host + (size_t)k * dimx * dimy, f.p + k * stride, P, dimx, dimy);
-    });
-}
-
-int of2d_prim_unpack_image(const float *in_host, int npairs, int dimx, int dimy,
-                           const of2d_darray *out) {
-    const Extents e = {{npairs, dimx, dimy, 0}};
-    const bool ok = in_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
-                    dimy > 0;
-    const std::string why =
-        ok ? first_refusal("of2d_prim_unpack_image", {{out, "out", true, e}})
-           : std::string("of2d_prim_unpack_image: in_host is NULL or a size is out of range");
-    if (!why.empty()) return refuse(nullptr, why.c_str());
-    return prim(true, [&] {
-        of2d::batch::BField<float> f;
-        upload_pairs(f, in_host, npairs, dimx, dimy);
-        of2d::launch_unpack_image(f.p, of2d::batch::pair_stride(dimx, dimy),
-                                  of2d::pitch_for(dimx), npairs, dimx, dimy, view_of(out, e),
-                                  nullptr);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-    });
-}
-
-int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
-                            const of2d_darray *out) {
-    const Extents e = {{npairs, dimx, dimy, 2}};
-    const bool ok = m_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
-                    dimy > 0;
-    const std::string why =
-        ok ? first_refusal("of2d_prim_unpack_motion", {{out, "out", true, e}})
-           : std::string("of2d_prim_unpack_motion: m_host is NULL or a size is out of range");
-    if (!why.empty()) return refuse(nullptr, why.c_str());
-    return prim(true, [&] {
-        of2d::batch::BField<float2> f;
-        upload_pairs(f, m_host, npairs, dimx, dimy);
-        of2d::launch_unpack_motion(f.p, of2d::batch::pair_stride(dimx, dimy),
-                                   of2d::pitch_for(dimx), npairs, dimx, dimy, view_of(out, e),
-                                   nullptr);
-        OF2D_HIP(hipStreamSynchronize(nullptr));
-    });
 }
 
 }  // extern "C"

@@ -12,8 +12,12 @@ import pytest
 from conftest import ROOT
 
 
-def header_functions():
-    src = open(os.path.join(ROOT, "include", "of2d.h")).read()
+PRODUCT_H = os.path.join("include", "of2d.h")
+PRIMS_H = os.path.join("opticalflow2d_amd", "csrc", "of2d_prims.h")
+
+
+def header_functions(path):
+    src = open(os.path.join(ROOT, path)).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     names = set(re.findall(r"\b(of2d_[a-z0-9_]+)\s*\(", src))
     names.discard("of2d_print_fn")
@@ -21,12 +25,18 @@ def header_functions():
 
 
 def test_library_exports_every_declared_symbol(of2d_lib):
+    """The product header and the test header each agree with their ctypes
+    table, share no name, and the library exports every name of both."""
     from opticalflow2d_amd import _lib
-    names = header_functions()
+    names, prims = header_functions(PRODUCT_H), header_functions(PRIMS_H)
     assert len(names) >= 25
-    for n in names:
+    assert not [n for n in names if n.startswith("of2d_prim_")], "test entries in include/of2d.h"
+    assert set(names) == set(_lib.PRODUCT_SIGNATURES), "ctypes table out of sync with include/of2d.h"
+    assert set(prims) == set(_lib.PRIM_SIGNATURES), "ctypes table out of sync with of2d_prims.h"
+    assert not set(names) & set(prims)
+    assert set(_lib.SIGNATURES) == set(names) | set(prims)
+    for n in names + prims:
         assert hasattr(of2d_lib, n), f"libof2d.so does not export {n}"
-    assert set(names) == set(_lib.SIGNATURES), "ctypes table out of sync with include/of2d.h"
 
 
 def test_library_is_gfx950_code_object():

@@ -3,7 +3,7 @@
 and the construct kernel with its Logger partials.
 
 Every entry of `opticalflow2d_amd.prim.curv_*` makes one call of the function
-Registration::loop_curvature calls (include/of2d.h).  What is held to what:
+Registration::loop_curvature calls (csrc/of2d_prims.h).  What is held to what:
 
 * rhs, construct (field), eigenvalues: on the bits.  The first two are plain
   float32 arithmetic restated in numpy in the kernel's order; the table is the

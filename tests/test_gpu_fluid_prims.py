@@ -3,7 +3,7 @@ at a time, against the oracle's CPU primitives.
 
 Every entry of `opticalflow2d_amd.prim` used here allocates a bare level with
 the solver's own helpers and makes the launch calls Registration::loop_fluid /
-loop_elastic make (include/of2d.h).  What is held to what:
+loop_elastic make (csrc/of2d_prims.h).  What is held to what:
 
 * every float32 output (v, R, maxabs, dt, the per-tile maxima, uo, the packed
   force, dI, It, the granules, the Jacobian minimum): on the bits (`same`),

@@ -2,7 +2,7 @@
 oracle's CPU primitives, on inputs chosen to break them.
 
 Every entry of `opticalflow2d_amd.prim` makes one call of the launch function
-the solvers call (include/of2d.h, "test and diagnostic entries").  Every
+the solvers call (csrc/of2d_prims.h, "test and diagnostic entries").  Every
 comparison is on the float32 bit patterns (uint32 views, so -0.0 != +0.0):
 that is the project's bar for these kernels and there is no tolerance in this
 file, with one exception: the fp64 Logger sums of smooth_norm, a tree sum of

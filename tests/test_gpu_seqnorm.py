@@ -12,7 +12,7 @@ terms where the float sum saturates far below the exact one, tiny magnitudes
 import numpy as np
 import pytest
 
-from opticalflow2d_amd.registration import motion_norms
+from opticalflow2d_amd.prims import motion_norms
 
 pytestmark = pytest.mark.gpu
 
@@ -222,7 +222,7 @@ def test_batched_chain(gpu, oracle, batch, dims, niter):
     updates, the check / fix / walk of the K updates in one launch each, two
     workspace sets predicting each other's successors): every update's sums
     bit for bit, ragged last batches included."""
-    from opticalflow2d_amd.registration import motion_norms_chain
+    from opticalflow2d_amd.prims import motion_norms_chain
     u = hs_like_chain(dims, niter, 40 + batch)
     got, res = motion_norms_chain(u, dims, batch)
     for k in range(niter):

@@ -14,7 +14,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from opticalflow2d_amd import ImageRegistration, set_print_sink  # noqa: E402
 from opticalflow2d_amd import synthetic as S  # noqa: E402
-from opticalflow2d_amd.registration import motion_norms  # noqa: E402
+from opticalflow2d_amd.prims import motion_norms  # noqa: E402
 
 set_print_sink(lambda s: None)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
