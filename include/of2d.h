@@ -204,28 +204,34 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done);
 /* owned rows of the motion, planar double [dimx*nrows*2] */
 int of2d_slab_get_motion(of2d_slab *s, double *out);
 /* average duration (microseconds) of one launch of the Jacobi kernel (the
- * fused kernel: THREE iterations per launch, over the whole slab in one
- * launch) over nlaunch launches, timed with HIP events on the stream it is
+ * fused kernel a fixed_iters run launches: THREE iterations per launch, or
+ * FOUR where info[11] says so, over the whole slab in one launch) over
+ * nlaunch launches, timed with HIP events on the stream it is
  * launched on.  The launches read the zeroed start buffer and write scratch:
  * the last run's motion (of2d_slab_get_motion) is left intact. */
 int of2d_slab_time_kernel(of2d_slab *s, int nlaunch, double *avg_us);
-/* slab facts for reports: info[0..10] = {nranks, ranks of the RCCL
+/* slab facts for reports: info[0..11] = {nranks, ranks of the RCCL
  * communicator (ncclCommCount; 0 without one), in-process group (0/1),
  * row_begin, row_end, dimx, pitch (elements), halo j-lines exchanged per fused
  * launch, interior/edge split (0/1), triple kernel derives dI from Iaux (0/1),
  * Logger of a convergence-on run (1: the reference's float running sums,
- * 0: fp64 sums — "logger_fp64" resolved)}; returns the number of entries
- * written */
+ * 0: fp64 sums — "logger_fp64" resolved), iterations per fused launch of a
+ * fixed_iters run (3, or 4: "hs_fixed_quads" resolved)}; returns the number of
+ * entries written */
 int of2d_slab_info(const of2d_slab *s, int *info, int n);
 /* the Logger errors of the last of2d_slab_run's iterations (the global ones:
  * the same on every rank), up to n into out; returns how many there are */
 int of2d_slab_last_errors(const of2d_slab *s, float *out, int n);
 /* wall time (ms, HIP events) of the last of2d_slab_run on this rank */
 int of2d_slab_last_run_ms(const of2d_slab *s, double *ms);
-/* the triple kernel's own average launch time (us) inside the last run,
- * from HIP events bracketing the back-to-back triple launches of each of its
+/* the fused kernel's own average launch time (us) inside the last run (the
+ * triple's, or the quad's in a run that launched quads: info[11]),
+ * from HIP events bracketing the back-to-back fused launches of each of its
  * first 64 chunks on the solver's stream (halo exchange included for N > 1),
- * and the number of launches that average covers */
+ * and the number of launches that average covers.  info[11] describes a
+ * fixed_iters run whatever the last run was: a convergence-on run launches
+ * triples even where info[11] is 4, and this average is then the triple's.
+ * of2d_slab_time_kernel always launches the kernel info[11] names. */
 int of2d_slab_last_run_kernel_us(const of2d_slab *s, double *avg_us, int *nlaunch);
 /* the halo's cost inside the last run, sampled with HIP events on the first 8
  * split triples (interior launch beside the exchange and two edge launches):
@@ -237,6 +243,10 @@ int of2d_slab_last_run_kernel_us(const of2d_slab *s, double *avg_us, int *nlaunc
  * *nsampled the launches sampled (0 when the run had no split triples) */
 int of2d_slab_last_run_halo_us(const of2d_slab *s, double *us3, int *nsampled);
 /* options (no reference counterpart):
+ *   "hs_fixed_quads" (1 = default, 0): a fixed_iters run of a one-rank slab
+ *   that is not split and reads dI advances four iterations per launch
+ *   (chunks of 25 launches) instead of three; 0 keeps the triples; the motion
+ *   is bit-identical either way, the Logger errors agree to rounding
  *   "hs_gradients_from_image" (-1 auto = default, 0, 1): the triple kernel
  *   derives dI from Iaux in the kernel (24 B/px per launch) instead of reading
  *   dI (28); auto does so when dI + It (12 B/px) exceed the 256 MB MALL;

@@ -1,8 +1,8 @@
 // hs_jacobi_impl.h — the fused Horn-Schunck Jacobi kernels the product
-// launches (hs_kernels.hip): one, two and three iterations per pass.  The
-// measured variants that are not launched (four iterations per pass, the
-// pre-OPT row step, diagnostic modes) live in tools/hs_variants_impl.h with
-// the tuning harness.
+// launches (hs_kernels.hip): one, two, three and four iterations per pass.
+// The measured variants that are not launched (four iterations per pass with
+// the whole window in registers, the pre-OPT row step, diagnostic modes) live
+// in tools/hs_variants_impl.h with the tuning harness.
 //
 // Restates, fused into one pass over HBM, the three full-grid passes of
 // OpticalFlowDiffusion::get_update (src/regularization/OpticalFlow/
@@ -959,6 +959,286 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi3_mid_kernel(
     jacobi3_body<ROWS, WAVES, XCD, MINB, UNR, PRIO, ALT, GI, true>(
         uo, un, dI, It, P, dimx, nrows, row0, dimy, alphasq, glo, ghi, partial, partial2, partial3,
         status, band0, gx, gy, rows, range_flag, jlo, jhi, Ia, m1, m2);
+}
+
+// ---------------------------------------------------------------------------
+// FOUR Jacobi iterations per pass, bit-identical to four single steps, for the
+// unsplit fixed-iteration run (slab.cpp).  The triple's strip geometry: 128-px
+// strips, lanes 2..61 own 2 px each, 120 output columns — the two halo lanes
+// on each side (4 px) are exactly what four steps consume (u1 is exact at lane
+// 0 px 1 / lane 63 px 0, u2 at lane 1 px 0 / lane 62 px 1, u3 at lane 1 px 1 /
+// lane 62 px 0) — and 8 / 6 halo j-lines of u / the gradients per band.  The
+// row step is the triple's (stepr_opt's arithmetic, div2_unscaled behind
+// range_flag, the same norms), so a quad equals a triple and a single step.
+// Per row step at march position sp: one u row (sp+4) and one gradient row
+// (sp+3) in, u1(sp+3), u2(sp+2), u3(sp+1), u4(sp), one u4 row out: 28 B per
+// pixel for FOUR iterations.  Each iteration's Logger magnitudes are taken
+// where its row is produced, in march order, so the fp32 lane sums are the
+// triple's for the same band and direction; partial .. partial4.
+// Register window: u0 at sp+2..sp+3 (+ one prefetched row), u1 at sp+1..sp+2,
+// u2 at sp..sp+1, u3 at sp-1..sp.  The gradient rows sp..sp+2, whose values
+// wait one, two and three row steps for their last use, are parked in LDS:
+// g (4 dwords) and den, rcp (4) of march position p in slot p & 3 as two
+// 16-B words per lane, [slot][word][thread], written when the row is completed
+// and read back before the step that uses it; It's 2 dwords per row stay in
+// registers.  A lane touches only its own words (no barrier, 16-B stride
+// across lanes).  4 slots x 2 words x 16 B x 256 threads = 32 KB per block:
+// four blocks per CU fit the 160 KB.
+template <int WAVES, bool XCD = true, int MINB = 4, int PRIO = 1, bool ALT = true>
+__global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
+    const float2 *__restrict__ uo, float2 *__restrict__ un, const float2 *__restrict__ dI,
+    const float *__restrict__ It, int P, int dimx, int nrows, int row0, int dimy, float alphasq,
+    int glo, int ghi, double *__restrict__ partial, double *__restrict__ partial2,
+    double *__restrict__ partial3, double *__restrict__ partial4, int band0, int gx, int gy,
+    int rows, const unsigned *__restrict__ range_flag, int jlo, int jhi) {
+    int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    if constexpr (XCD) {
+        if (!xcd_block(gx, gy, bx, by)) return;
+    }
+    __shared__ v4f park[4][2][64 * WAVES];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int x = bx * kHs3Out - 4 + 2 * lane;
+    const bool own = lane >= 2 && lane <= 61 && x < dimx;
+    const bool xin = x >= 0 && x + 2 <= P;
+    const int band = band0 + by;
+    if (jlo < 0) jlo = band0 * WAVES * rows;
+    if (jhi < 0) jhi = nrows;
+    const int jbeg = jlo + (by * WAVES + wave) * rows;
+    const int jend = min(jbeg + rows, jhi);
+    float s1d = 0.0f, s1p = 0.0f, s2d = 0.0f, s2p = 0.0f, s3d = 0.0f, s3p = 0.0f, s4d = 0.0f,
+          s4p = 0.0f;
+    auto cl = [&](int j) { return min(max(j, glo), ghi - 1); };
+    const int xl = xin ? x : (x < 0 ? 0 : P - 2);
+    auto ldu = [&](int j) { return load_row<2, true>(uo + (long)cl(j) * P, xl); };
+    // a gradient row in use, as the two 16-B words that are parked: a = the
+    // gradients of the lane's two px (gx0, gy0, gx1, gy1), b = (den0, den1, rcp0,
+    // rcp1); and It.  (Vector values, not arrays: an array member the optimiser
+    // fails to split keeps the row in scratch.)
+    struct G {
+        v4f a, b;
+        float2 t;
+    };
+    const bool grange = *range_flag == 0;
+    // a gradient row is loaded raw (dI, It) and completed with the shared
+    // denominator and its reciprocal when the march reaches it
+    struct GR {
+        v4f g;
+        float2 t;
+    };
+    auto ldgr = [&](int j) {
+        GR r;
+        const float4 g = ld4<false>(reinterpret_cast<const float4 *>(dI + (long)cl(j) * P + xl));
+        r.g = v4f{g.x, g.y, g.z, g.w};
+        r.t = ld2<false>(reinterpret_cast<const float2 *>(It + (long)cl(j) * P + xl));
+        return r;
+    };
+    auto fin = [&](const GR &r) {
+        const float den0 = (alphasq + r.g.x * r.g.x) + r.g.y * r.g.y;
+        const float den1 = (alphasq + r.g.z * r.g.z) + r.g.w * r.g.w;
+        return G{r.g, v4f{den0, den1, recip_refined(den0), recip_refined(den1)}, r.t};
+    };
+    // the lane's own words of slot `slot` (volatile: every put and get is a DS
+    // instruction in program order, none forwarded through registers)
+    typedef volatile __attribute__((address_space(3))) v4f lds_v4f;
+    lds_v4f *pk = (lds_v4f *)&park[0][0][threadIdx.x];
+    auto put = [&](int slot, const G &g) {
+        pk[(2 * slot) * 64 * WAVES] = g.a;
+        pk[(2 * slot + 1) * 64 * WAVES] = g.b;
+    };
+    auto get = [&](int slot, float2 t) {
+        const v4f a = pk[(2 * slot) * 64 * WAVES], b = pk[(2 * slot + 1) * 64 * WAVES];
+        return G{a, b, t};
+    };
+    const bool xedge_w = __builtin_amdgcn_ballot_w64(x == 0 || x == dimx - 1 || x + 1 == 0 ||
+                                                     x + 1 == dimx - 1) != 0;
+    // jacobi3_body's stepr_opt
+    auto stepr = [&](int j, const Row<2> &m, const Row<2> &c, const Row<2> &p, const G &g) {
+        float sx0 = dpp_from_left(c.v[1].x) + c.v[1].x;
+        float sy0 = dpp_from_left(c.v[1].y) + c.v[1].y;
+        float sx1 = dpp_from_right(c.v[0].x) + c.v[0].x;
+        float sy1 = dpp_from_right(c.v[0].y) + c.v[0].y;
+        asm("" : "+v"(sx0), "+v"(sy0), "+v"(sx1), "+v"(sy1));
+        const int jg = row0 + j;
+        const bool yb = (jg == 0) || (jg == dimy - 1);
+        v2f q[2];
+        q[0] = ((v2f{sx0, sy0} + v2f{m.v[0].x, m.v[0].y}) + v2f{p.v[0].x, p.v[0].y}) / 4.0f;
+        q[1] = ((v2f{sx1, sy1} + v2f{m.v[1].x, m.v[1].y}) + v2f{p.v[1].x, p.v[1].y}) / 4.0f;
+        if (yb || xedge_w) {
+            auto mask = [&](int k) __attribute__((always_inline)) {
+                const int xi = x + k;
+                const float2 z = zero_if(yb || xi == 0 || xi == dimx - 1, make_float2(q[k].x, q[k].y));
+                q[k] = v2f{z.x, z.y};
+            };
+            mask(0);
+            mask(1);
+        }
+        const v2f g0 = {g.a.x, g.a.y}, g1 = {g.a.z, g.a.w};
+        const v2f pr0 = q[0] * g0, pr1 = q[1] * g1;
+        const float sc0 = (g.t.x + pr0.x) + pr0.y, sc1 = (g.t.y + pr1.x) + pr1.y;
+        Row<2> o;
+        const float mn = fminf(fabsf(sc0), fabsf(sc1)), mx = fmaxf(fabsf(sc0), fabsf(sc1));
+        if (grange && __builtin_amdgcn_ballot_w64(!(mn >= 0x1p-50f && mx < 0x1p30f)) == 0) {
+            const float2 f0 = div2_unscaled(g0.x * sc0, g0.y * sc0, g.b.x, g.b.z);
+            const float2 f1 = div2_unscaled(g1.x * sc1, g1.y * sc1, g.b.y, g.b.w);
+            o.v[0] = make_float2(q[0].x - f0.x, q[0].y - f0.y);
+            o.v[1] = make_float2(q[1].x - f1.x, q[1].y - f1.y);
+        } else {
+            const float fx0 = g0.x * sc0, fy0 = g0.y * sc0, fx1 = g1.x * sc1, fy1 = g1.y * sc1;
+            o.v[0] = make_float2(q[0].x - fx0 / g.b.x, q[0].y - fy0 / g.b.x);
+            o.v[1] = make_float2(q[1].x - fx1 / g.b.y, q[1].y - fy1 / g.b.y);
+        }
+        return o;
+    };
+    const bool in1 = x + 1 < dimx;
+    auto mag = [](float a, float b) { return __builtin_amdgcn_sqrtf(a * a + b * b); };
+    auto norms = [&](const Row<2> &nw, const Row<2> &od, float &sd, float &sp) {
+        sd += mag(nw.v[0].x - od.v[0].x, nw.v[0].y - od.v[0].y);
+        sp += mag(od.v[0].x, od.v[0].y);
+        const float d1 = mag(nw.v[1].x - od.v[1].x, nw.v[1].y - od.v[1].y);
+        const float p1 = mag(od.v[1].x, od.v[1].y);
+        sd += in1 ? d1 : 0.0f;  // a select, not a product: padding may hold 0/0
+        sp += in1 ? p1 : 0.0f;
+    };
+    // one band, marched in direction D as jacobi3_body's
+    auto march = [&](auto dirc) __attribute__((always_inline)) {
+        constexpr int D = decltype(dirc)::value;
+        const int n = jend - jbeg;
+        auto J = [&](int sp) { return D > 0 ? jbeg + sp : jend - 1 - sp; };
+        auto S = [&](int sp, const Row<2> &bh, const Row<2> &c, const Row<2> &ah, const G &g) {
+            return D > 0 ? stepr(J(sp), bh, c, ah, g) : stepr(J(sp), ah, c, bh, g);
+        };
+        Row<2> uj2, uj3;      // u0 at positions sp+2, sp+3
+        Row<2> vj1, vj2;      // u1 at sp+1, sp+2
+        Row<2> wj, wj1;       // u2 at sp, sp+1
+        Row<2> xm1, xj;       // u3 at sp-1, sp
+        float2 tj, tj1, tj2;  // It at sp .. sp+2 (the rest of those rows: slots sp .. sp+2 & 3)
+        {
+            // halo rows first, so that their inputs die before the band's rows
+            // are loaded: u1 at -3..-1, u2 at -2..-1, then the rows the march keeps
+            const Row<2> a0 = ldu(J(-4)), a1 = ldu(J(-3)), a2 = ldu(J(-2)), a3 = ldu(J(-1));
+            const Row<2> uj = ldu(J(0));
+            const G gm3 = fin(ldgr(J(-3))), gm2 = fin(ldgr(J(-2))), gm1 = fin(ldgr(J(-1)));
+            const Row<2> pm3 = S(-3, a0, a1, a2, gm3);
+            const Row<2> pm2 = S(-2, a1, a2, a3, gm2);
+            const Row<2> pm1 = S(-1, a2, a3, uj, gm1);
+            const Row<2> qm2 = S(-2, pm3, pm2, pm1, gm2);
+            const Row<2> uj1 = ldu(J(1));
+            const G gj = fin(ldgr(J(0)));
+            put(0, gj);
+            tj = gj.t;
+            const Row<2> vj = S(0, a3, uj, uj1, gj);
+            const Row<2> qm1 = S(-1, pm2, pm1, vj, gm1);
+            uj2 = ldu(J(2));
+            const G gj1 = fin(ldgr(J(1)));
+            put(1, gj1);
+            tj1 = gj1.t;
+            vj1 = S(1, uj, uj1, uj2, gj1);
+            wj = S(0, pm1, vj, vj1, gj);
+            xm1 = S(-1, qm2, qm1, wj, gm1);
+            uj3 = ldu(J(3));
+            const G gj2 = fin(ldgr(J(2)));
+            put(2, gj2);
+            tj2 = gj2.t;
+            vj2 = S(2, uj1, uj2, uj3, gj2);
+            wj1 = S(1, vj, vj1, vj2, gj1);
+            xj = S(0, qm1, wj, wj1, gj);
+            if (own) {
+                norms(vj, uj, s1d, s1p);
+                norms(wj, vj, s2d, s2p);
+                norms(xj, wj, s3d, s3p);
+                if (1 < n) {
+                    norms(vj1, uj1, s1d, s1p);
+                    norms(wj1, vj1, s2d, s2p);
+                }
+                if (2 < n) norms(vj2, uj2, s1d, s1p);
+            }
+        }
+        Row<2> nu = ldu(J(4));
+        GR ng = ldgr(J(3));
+        // one output row; slot: sp & 3 (a constant in the unrolled loop, so the
+        // DS instructions carry the slot as their immediate offset)
+        auto body = [&](int sp, bool pref, int slot) __attribute__((always_inline)) {
+            const Row<2> a4 = nu;
+            const G gj3 = fin(ng);
+            put((slot + 3) & 3, gj3);
+            if (pref) {
+                nu = ldu(J(sp + 5));
+                ng = ldgr(J(sp + 4));
+            }
+            const G gj2 = get((slot + 2) & 3, tj2);
+            const Row<2> vj3 = S(sp + 3, uj2, uj3, a4, gj3);  // u1
+            const G gj1 = get((slot + 1) & 3, tj1);
+            const Row<2> wj2 = S(sp + 2, vj1, vj2, vj3, gj2);  // u2
+            const G gj = get(slot, tj);
+            const Row<2> xj1 = S(sp + 1, wj, wj1, wj2, gj1);  // u3
+            const Row<2> z = S(sp, xm1, xj, xj1, gj);         // u4
+            if (own) {
+                if (sp + 3 < n) norms(vj3, uj3, s1d, s1p);
+                if (sp + 2 < n) norms(wj2, vj2, s2d, s2p);
+                if (sp + 1 < n) norms(xj1, wj1, s3d, s3p);
+                norms(z, xj, s4d, s4p);
+                float2 *dst = un + (long)J(sp) * P + x;
+                if (x + 2 <= dimx)
+                    st4<true>(reinterpret_cast<float4 *>(dst),
+                              make_float4(z.v[0].x, z.v[0].y, z.v[1].x, z.v[1].y));
+                else
+                    dst[0] = z.v[0];
+            }
+            uj2 = uj3;
+            uj3 = a4;
+            vj1 = vj2;
+            vj2 = vj3;
+            wj = wj1;
+            wj1 = wj2;
+            xm1 = xj;
+            xj = xj1;
+            tj = tj1;
+            tj1 = tj2;
+            tj2 = gj3.t;
+        };
+        int sp = 0;
+        for (; sp + 4 < n; sp += 4) {
+            progress_prio<PRIO>(sp, n);
+#pragma unroll
+            for (int k = 0; k < 4; k++) body(sp + k, true, k);
+        }
+        for (; sp < n; ++sp) body(sp, sp + 1 < n, sp & 3);
+    };
+    if (jbeg < jend) {
+        if (ALT && (wave & 1))
+            march(std::integral_constant<int, -1>{});
+        else
+            march(std::integral_constant<int, 1>{});
+    }
+    // the triple's reduction: fp64 from the lane sums on, the same tree, waves
+    // added in order
+    double d[8] = {s1d, s1p, s2d, s2p, s3d, s3p, s4d, s4p};
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int q = 0; q < 8; q++) d[q] += __shfl_down(d[q], off);
+    __shared__ double red[8][WAVES];
+    if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < 8; q++) red[q][wave] = d[q];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w)
+#pragma unroll
+            for (int q = 0; q < 8; q++) r[q] += red[q][w];
+        const long blk = (long)band * gx + bx;
+        partial[2 * blk] = r[0];
+        partial[2 * blk + 1] = r[1];
+        partial2[2 * blk] = r[2];
+        partial2[2 * blk + 1] = r[3];
+        partial3[2 * blk] = r[4];
+        partial3[2 * blk + 1] = r[5];
+        partial4[2 * blk] = r[6];
+        partial4[2 * blk + 1] = r[7];
+    }
 }
 
 template <int ROWS, int WAVES>

@@ -102,6 +102,31 @@ void launch_hs_jacobi3(const float2 *u_old, float2 *u_new, const float2 *dI, con
     OF2D_HIP(hipGetLastError());
 }
 
+// Four iterations per launch for the unsplit fixed-iteration run: the triple's
+// grid (hs3_rows, the same blocks and partial slots), 4 resident blocks per CU
+// with part of the register window parked in LDS (hs_jacobi_impl.h)
+static const auto kHsJacobi4 = &hs::jacobi4_kernel<kHs3Waves, true, 4, 1, true>;
+
+void launch_hs_jacobi4(const float2 *u_old, float2 *u_new, const float2 *dI, const float *It,
+                       int P, int dimx, int dimy, float alphasq, int glo, int ghi,
+                       double *partial, double *partial2, double *partial3, double *partial4,
+                       const unsigned *range_flag, hipStream_t st, int slots) {
+    if (P % kHsStrip != 0 || dimy <= 0 || dimx > P || dimx < 2 || glo > -1 || ghi < dimy + 1)
+        throw std::invalid_argument("launch_hs_jacobi4: bad geometry");
+    if (!range_flag) throw std::invalid_argument("launch_hs_jacobi4: no range flag");
+    // the triple's rule and cost model (rounds x (rows + 2)), on purpose: the
+    // same rows give the triple's blocks and partial slots (hs3_nblocks), and
+    // the quad's slightly longer prologue is not modelled (of2d_device.h)
+    const int rows = hs3_rows(dimx, dimy, slots);
+    const int gx = (dimx + kHs3Out - 1) / kHs3Out;
+    const int gy = (dimy + kHs3Waves * rows - 1) / (kHs3Waves * rows);
+    const dim3 gl(8 * ((gx * gy + 7) / 8));
+    hipLaunchKernelGGL(kHsJacobi4, gl, dim3(64 * kHs3Waves), 0, st, u_old, u_new, dI, It, P, dimx,
+                       dimy, 0, dimy, alphasq, glo, ghi, partial, partial2, partial3, partial4, 0,
+                       gx, gy, rows, range_flag, -1, -1);
+    OF2D_HIP(hipGetLastError());
+}
+
 int launch_hs_jacobi3_window(const float2 *u_old, float2 *u_new, const float2 *dI,
                              const float *It, int P, int dimx, int nrows, int row0, int dimy,
                              float alphasq, int glo, int ghi, int jlo, int jhi,

@@ -48,13 +48,18 @@ struct FusedPlan {
 // The launches of a chunk of C iterations from buffer a.  With pairs: triples
 // while three iterations remain (if triples), then a pair or a single for the
 // tail, alternating between the two buffers other than a.  Without: the single
-// steps of the rotation above.
-inline FusedPlan plan_fused(int a, int C, bool triples, bool pairs) {
+// steps of the rotation above.  With quads (the unsplit fixed-iteration run,
+// which takes no break and replays nothing): four iterations per launch while
+// four remain, then the same triple, pair or single for the tail.
+inline FusedPlan plan_fused(int a, int C, bool triples, bool pairs, bool quads = false) {
     FusedPlan p;
     p.end = a;
     p.launches.reserve((size_t)std::max(C, 0));  // one allocation: the loops plan every chunk
     for (int t = 0; t < C;) {
-        const int K = !pairs ? 1 : (triples && C - t >= 3 ? 3 : std::min(2, C - t));
+        const int K = !pairs ? 1
+                      : quads && C - t >= 4 ? 4
+                      : triples && C - t >= 3 ? 3
+                                              : std::min(2, C - t);
         const int out = pairs ? other(a, p.end) : single_dst(a, t);
         p.launches.push_back({K, t, p.end, out});
         p.end = out;
@@ -62,6 +67,10 @@ inline FusedPlan plan_fused(int a, int C, bool triples, bool pairs) {
     }
     return p;
 }
+// Iterations per chunk of a fixed-iteration run.  It has no break to replay, so
+// a chunk only sets how often the partial rows are reduced: 33 triples, or 25
+// quads (1000 iterations: ten whole chunks, no tail).
+constexpr int fixed_chunk(bool quads) { return quads ? 100 : 99; }
 // A break at chunk-local iteration t of C: is iterate t + 1 gone from
 // single_dst(a, t)?  Fused launches never wrote it there; single steps
 // overwrote it with iterate t + 3.  The replay runs single steps 0..t from a.

@@ -210,6 +210,21 @@ int launch_hs_jacobi3_window(const float2 *u_old, float2 *u_new, const float2 *d
                              const float *Ia = nullptr);
 void launch_hs_precheck(const float2 *base, size_t count, int P, int ghost, int dimx, int dimy,
                         float alphasq, unsigned *range_flag, unsigned *status, hipStream_t st);
+// Four Jacobi iterations per launch (hs::jacobi4_kernel) over a whole image
+// (rows 0 .. dimy-1 of the level: no neighbour above or below, so the j-lines
+// outside [0, dimy) only feed pixels the border rule zeroes), bit-identical to
+// four launch_hs_jacobi calls.  The triple's grid and partial slots
+// (hs3_rows(dimx, dimy, slots)); rows [glo, ghi) of u, dI and It readable
+// (rows beyond are clamped into it); the gradients are read from dI;
+// range_flag as for the triple (launch_hs_precheck's word, required).  The
+// j-lines per wave are hs3_rows', whose cost model (rounds x (rows + 2)) is the
+// triple's, reused on purpose: the quad's prologue is a row step or two longer,
+// which moves the optimum only where two candidates are that close, and equal
+// rows keep the quad's blocks and Logger partials those of the triple.
+void launch_hs_jacobi4(const float2 *u_old, float2 *u_new, const float2 *dI, const float *It,
+                       int P, int dimx, int dimy, float alphasq, int glo, int ghi,
+                       double *partial, double *partial2, double *partial3, double *partial4,
+                       const unsigned *range_flag, hipStream_t st, int slots = 1024);
 constexpr int kRangeFlagWord = 32;  // word of the 64-word status buffers holding range_flag
 constexpr int kStopWord = 33;  // the exact-Logger loop's break (seqnorm_decide)
 // the Fluid loop's device-side decisions (Registration::loop_fluid, FluidCtl):

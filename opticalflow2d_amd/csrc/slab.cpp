@@ -101,10 +101,18 @@ struct of2d_slab {
     unsigned *d_status = nullptr;
     of2d::HostScratch hs;
     int chunk = 33;  // eleven fused triples per chunk
-    // a fixed-iteration run has no break to replay, so its chunks only set how
-    // often the partial rows are reduced: 33 triples per reduction launch
-    int chunk_fixed = 99;
-    int chunk_cap() const { return chunk > chunk_fixed ? chunk : chunk_fixed; }
+    // (a fixed-iteration run has no break to replay, so its chunks only set how
+    // often the partial rows are reduced: sched::fixed_chunk, 33 triples or 25
+    // quads per reduction launch)
+    // the unsplit fixed-iteration run of a one-rank slab takes four iterations
+    // per launch (hs::jacobi4_kernel, 25 per chunk) unless this is 0 (option
+    // "hs_fixed_quads"; the motion is bit-identical either way)
+    int quads = 1;
+    // rows of the partial buffer: the longest chunk of any run
+    int chunk_cap() const {
+        namespace sched = of2d::sched;
+        return std::max(chunk, std::max(sched::fixed_chunk(false), sched::fixed_chunk(true)));
+    }
     int fin = 0;    // buffer holding the final motion
     int start = 0;  // zeroed buffer the next run starts from (motion_est->reset())
     // a run began and has not re-zeroed `start` (it threw midway): the next
@@ -356,6 +364,12 @@ struct SlabGeometry {
 };
 bool use_gi(const of2d_slab *s) {
     return s->gi < 0 ? of2d::hs3_gradients_from_image(s->dimx, s->nrows) : s->gi != 0;
+}
+// a fixed-iteration run of this slab launches quads: the whole image in one
+// slab (no halo above or below, no split, no rehearsed exchange) with the
+// gradients read from dI (slabs that derive them from the image keep the triple)
+bool use_quads(const of2d_slab *s, bool split) {
+    return s->quads && s->nranks == 1 && !split && !s->self_halo && !use_gi(s) && s->dimx >= 2;
 }
 // the exact-Logger loop's triples (run_exact): its passes stream the iterates
 // beside them (of2d::hs3_exact_gradients_from_image)
@@ -934,8 +948,11 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
         // partial rows long enough for every kernel; each row is reduced over
         // the blocks of the kernel that wrote it
         const int nb = G.nb;
-        const int nblk[3] = {of2d::hs_nblocks(s->P, s->nrows),  // single, pair, triple
-                             of2d::hs2_nblocks(s->dimx, s->nrows), G.n3};
+        const int nblk[4] = {of2d::hs_nblocks(s->P, s->nrows),  // single, pair, triple, quad
+                             of2d::hs2_nblocks(s->dimx, s->nrows), G.n3, G.n3};
+        // four iterations per launch, and the launches a chunk's timing covers
+        const bool quads = fixed_iters && use_quads(s, G.split);
+        const int Km = quads ? 4 : 3;
         const double npx = (double)s->dimx * s->dimy;
         unsigned *range_flag = s->d_status + of2d::kRangeFlagWord;
         // Iaux == Imov (zero initial motion); its three ghost j-lines hold the
@@ -970,8 +987,17 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
         // E..E+2, written by the interior of launch k-1 (comm_st waits ev_int,
         // recorded before this launch's interior).  Pairs and single steps
         // (chunk tails, replays) exchange and launch on st.
-        auto fused = [&](int K, int in, int out, double *p1, double *p2, double *p3) {
+        auto fused = [&](int K, int in, int out, double *p1, double *p2, double *p3,
+                         double *p4 = nullptr) {
             float2 *uin = s->u[in].p;
+            if (K == 4) {
+                // one rank, the whole image: no exchange; dI and It have two
+                // ghost j-lines (u three), and none of them feeds an image pixel
+                of2d::launch_hs_jacobi4(uin, s->u[out].p, s->dI.p, s->It.p, s->P, s->dimx,
+                                        s->nrows, alphasq, -2, s->nrows + 2, p1, p2, p3, p4,
+                                        range_flag, s->st, G.slots);
+                return;
+            }
             if (K == 3 && G.split) {
                 hipEvent_t *eh = s->halo_n < of2d_slab::kHaloTimed
                                      ? s->ev_halo + 5 * s->halo_n++ : nullptr;
@@ -1045,15 +1071,15 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
             k0 = niter;  // skips the fused-partials loop
         }
         while (k0 < niter && done < 0) {
-            const int C = std::min(fixed_iters ? s->chunk_fixed : s->chunk, niter - k0);
+            const int C = std::min(fixed_iters ? sched::fixed_chunk(quads) : s->chunk, niter - k0);
             auto part = [&](int t) { return s->d_partial + (size_t)t * nb * 2; };
             // the slab always fuses: triples, then a pair / single tail
             // (sched::plan_fused); the chunk's start buffer a stays intact for
             // a replay
-            const sched::FusedPlan plan = sched::plan_fused(a, C, true, true);
+            const sched::FusedPlan plan = sched::plan_fused(a, C, true, true, quads);
             of2d::PartialRuns runs;
-            // time this chunk's triples (the first kTriTimed chunks of the run)
-            const bool timed = C >= 3 && s->tri_pairs < of2d_slab::kTriTimed;
+            // time this chunk's triples or quads (the first kTriTimed chunks of the run)
+            const bool timed = C >= Km && s->tri_pairs < of2d_slab::kTriTimed;
             if (timed) {
                 join_st();
                 OF2D_HIP(hipEventRecord(s->ev_tri[2 * s->tri_pairs], s->st));
@@ -1063,13 +1089,13 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
                     single(l.in, l.out, part(l.t));
                 else
                     fused(l.K, l.in, l.out, part(l.t), part(l.t + 1),
-                          l.K == 3 ? part(l.t + 2) : nullptr);
+                          l.K >= 3 ? part(l.t + 2) : nullptr, l.K == 4 ? part(l.t + 3) : nullptr);
                 runs.add(l.t, l.K, nblk[l.K - 1]);
-                if (timed && l.K == 3 && C - (l.t + 3) < 3) {  // the chunk's last triple
+                if (timed && l.K == Km && C - (l.t + Km) < Km) {  // the chunk's last triple / quad
                     join_st();
                     OF2D_HIP(hipEventRecord(s->ev_tri[2 * s->tri_pairs + 1], s->st));
                     s->tri_pairs++;
-                    s->tri_launches += C / 3;
+                    s->tri_launches += C / Km;
                 }
             }
             if (fixed_iters) {
@@ -1176,10 +1202,19 @@ int of2d_slab_time_kernel(of2d_slab *s, int nlaunch, double *avg_us) {
         // scratch buffer, so the last run's result (fin) and the next run's start
         // survive; the partials go to the run's partial buffer, re-written by
         // every run before it is read
-        const int nb = slab_geometry(s).nb;
+        // (the quad kernel where a fixed-iteration run launches it)
+        const SlabGeometry G = slab_geometry(s);
+        const int nb = G.nb;
         double *p1 = s->d_partial, *p2 = p1 + (size_t)nb * 2, *p3 = p1 + (size_t)nb * 4;
         const int in = s->start, out = scratch_buffer(s);
         auto go = [&] {
+            if (use_quads(s, G.split)) {
+                of2d::launch_hs_jacobi4(s->u[in].p, s->u[out].p, s->dI.p, s->It.p, s->P, s->dimx,
+                                        s->nrows, alphasq, -2, s->nrows + 2, p1, p2, p3,
+                                        p1 + (size_t)nb * 6, s->d_status + of2d::kRangeFlagWord,
+                                        s->st, G.slots);
+                return;
+            }
             of2d::launch_hs_jacobi3(s->u[in].p, s->u[out].p, s->dI.p, s->It.p, s->P, s->dimx,
                                     s->nrows, s->rb, s->dimy, alphasq, -3, s->nrows + 3, p1, p2,
                                     p3, s->d_status, s->d_status + of2d::kRangeFlagWord, s->st,
@@ -1204,7 +1239,7 @@ int of2d_slab_info(const of2d_slab *s, int *info, int n) {
     const int halo_lines = s->nranks > 1 ? 3 : 0;
     const int v[] = {s->nranks, rccl, s->grp ? 1 : 0, s->rb, s->re, s->dimx, s->P,
                      halo_lines, slab_geometry(s).split ? 1 : 0, use_gi(s) ? 1 : 0,
-                     exact_logger(s) ? 1 : 0};
+                     exact_logger(s) ? 1 : 0, use_quads(s, slab_geometry(s).split) ? 4 : 3};
     const int k = std::min(n, (int)(sizeof v / sizeof v[0]));
     for (int i = 0; i < k; i++) info[i] = v[i];
     return k;
@@ -1230,6 +1265,10 @@ int of2d_slab_set_option(of2d_slab *s, const char *key, double value) {
     }
     if (std::strcmp(key, "hs_gradients_from_image") == 0) {
         s->gi = value < 0.0 ? -1 : (value != 0.0 ? 1 : 0);
+        return OF2D_OK;
+    }
+    if (std::strcmp(key, "hs_fixed_quads") == 0) {
+        s->quads = value != 0.0;
         return OF2D_OK;
     }
     s->err = std::string("slab: unknown option ") + key;

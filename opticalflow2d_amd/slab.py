@@ -117,18 +117,21 @@ class SlabSolver:
         one), rows, pitch, halo lines per fused launch, interior/edge split,
         whether the triple kernel derives dI from Iaux, and the Logger a
         convergence-on run takes (1: the reference's float running sums, 0:
-        fp64 sums)."""
-        buf = (C.c_int * 11)()
-        n = _lib.lib().of2d_slab_info(self._h, buf, 11)
+        fp64 sums), and the iterations a fixed_iters run advances per fused
+        launch (3, or 4 where it launches the quad kernel)."""
+        buf = (C.c_int * 12)()
+        n = _lib.lib().of2d_slab_info(self._h, buf, 12)
         if n < 0:
             self._chk(-n)
         keys = ["nranks", "rccl_ranks", "in_process_group", "row_begin", "row_end", "dimx",
-                "pitch", "halo_lines", "split", "gradients_from_image", "logger_reference"]
+                "pitch", "halo_lines", "split", "gradients_from_image", "logger_reference",
+                "iterations_per_launch"]
         return {k: int(buf[i]) for i, k in enumerate(keys[:n])}
 
     def set_option(self, key: str, value: float) -> None:
         """Tuning switch (include/of2d.h of2d_slab_set_option), e.g.
-        "hs_gradients_from_image" 0/1; results are bit-identical either way."""
+        "hs_gradients_from_image" 0/1, "hs_fixed_quads" 0/1; the motion is
+        bit-identical either way."""
         self._chk(_lib.lib().of2d_slab_set_option(self._h, key.encode(), float(value)))
 
     def run(self, niter: int, fixed_iters: bool = False) -> int:
@@ -149,7 +152,9 @@ class SlabSolver:
         return us.value
 
     def last_run_kernel_us(self) -> tuple:
-        """(average us per triple launch, launches averaged) inside the last run."""
+        """(average us per fused launch — triples, or quads where
+        info()["iterations_per_launch"] is 4 —, launches averaged) inside the
+        last run."""
         us = C.c_double(0.0)
         n = C.c_int(0)
         self._chk(_lib.lib().of2d_slab_last_run_kernel_us(self._h, C.byref(us), C.byref(n)))
