@@ -185,9 +185,11 @@ int of2d_rccl_get_unique_id(void *out, int len);
 typedef struct of2d_slab of2d_slab;
 int of2d_slab_create(of2d_slab **out, int dimx, int dimy, float alpha, int rank, int nranks,
                      int device, const void *rccl_unique_id, int id_len);
-/* images: rows [row_begin-3, row_end+3) clipped to [0, dimy), double, x fast
+/* images: rows [row_begin-3, row_end+4) clipped to [0, dimy), double, x fast
  * (three halo rows: iterations run fused in threes, whose first step also
- * covers two halo j-lines on each side) */
+ * covers two halo j-lines on each side; the fourth row below: the moving image
+ * is warped by the zero motion as the reference does, which reads the row
+ * below every row it produces and spreads a NaN or inf pixel) */
 int of2d_slab_set_images(of2d_slab *s, const double *Iref_rows, const double *Imov_rows);
 /* The slab's per-run setup lives outside of2d_slab_run: set_images computes the
  * gradients and the divide-by-zero / division-range test (dI is fixed per image

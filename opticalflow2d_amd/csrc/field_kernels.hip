@@ -249,9 +249,9 @@ __global__ void compose_zero_kernel(const float2 *__restrict__ v, float2 *__rest
     const long idx = (long)j * P + i;
     const float2 c = v[idx];
     const float px = (float)i + c.x;
-    const int dx = (int)floorf(px);
+    const int dx = floor_int(px);
     const float py = (float)(row0 + j) + c.y;
-    const int dy = (int)floorf(py);
+    const int dy = floor_int(py);
     float2 o = make_float2(0.0f, 0.0f);
     if (!(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy)) o = make_float2(c.x + 0.0f, c.y + 0.0f);
     out[idx] = o;
@@ -260,6 +260,32 @@ void launch_compose_zero(const float2 *v, float2 *out, int dimx, int nrows, int 
                          int dimy, hipStream_t st) {
     hipLaunchKernelGGL(compose_zero_kernel, grid2d(dimx, nrows), dim3(kBx, kBy), 0, st, v, out,
                        dimx, nrows, P, row0, dimy);
+    OF2D_HIP(hipGetLastError());
+}
+
+// Image::warp2d (src/Image.cpp:119-182) by a ZERO motion, as the reference
+// applies it to the moving image before the first gradients: fx = fy = 0, so
+// the weight is 1 and the value is the pixel itself plus its right, lower and
+// diagonal taps times 0.  That is the identity on finite pixels only: a NaN
+// or inf tap times 0 is NaN, so a non-finite pixel spreads to its left and
+// upper neighbours (and -0 becomes +0 beside a positive tap).  Slab variant:
+// rows [0, nrows) are global j-lines row0.. of a dimy-line grid; row nrows of
+// `raw` is read unless it lies past the grid.
+__global__ void warp_zero_rows_kernel(const float *__restrict__ raw, float *__restrict__ out,
+                                      int dimx, int nrows, int P, int row0, int dimy) {
+    OF2D_PX_PROLOGUE(dimx, nrows)
+    const long idx = (long)j * P + i;
+    const bool ax = i < dimx - 1, ay = row0 + j < dimy - 1;
+    float val = (raw[idx] * 1.0f) * 1.0f;
+    if (ax) val = val + (raw[idx + 1] * 0.0f) * 1.0f;
+    if (ay) val = val + (raw[idx + P] * 1.0f) * 0.0f;
+    if (ax && ay) val = val + (raw[idx + P + 1] * 0.0f) * 0.0f;
+    out[idx] = val;  // val / 1.0f
+}
+void launch_warp_zero_rows(const float *raw, float *out, int dimx, int nrows, int P, int row0,
+                           int dimy, hipStream_t st) {
+    hipLaunchKernelGGL(warp_zero_rows_kernel, grid2d(dimx, nrows), dim3(kBx, kBy), 0, st, raw,
+                       out, dimx, nrows, P, row0, dimy);
     OF2D_HIP(hipGetLastError());
 }
 

@@ -145,7 +145,10 @@ __device__ __forceinline__ void gradients_px(const float *__restrict__ Iref,
                                              long idx, int i, int jg, int dimx, int dimy, int P) {
     float gx, gy;
     if (i == 0)
-        gx = Ia[idx + 1] - Ia[idx];
+        // f[idx + 1] in the reference's unpitched array: with one column that
+        // is the pixel of the next j-line (one past the array on the last
+        // j-line, read as 0 here), not the pitch padding
+        gx = (dimx > 1 ? Ia[idx + 1] : (jg < dimy - 1 ? Ia[idx + P] : 0.0f)) - Ia[idx];
     else if (i == dimx - 1)
         gx = Ia[idx] - Ia[idx - 1];
     else

@@ -119,6 +119,25 @@ __device__ __forceinline__ float2 update_px(float2 q, float gx, float gy, float 
 // In that range the sequence below is therefore the compiler's sequence on
 // the same values: bit-identical quotients, with the reciprocal refinement
 // (which depends on b only) shared by every division by the same b.
+// a = g * sc is 0 only through g == 0: a wave step with sc == 0 on any lane
+// takes the IEEE sequence (the ballot's mn >= 2^-50 is false for 0).
+// Where each bound is held to the oracle's bits:
+//   low end (sc below 2^-50, gradients below 2^-30): tests/test_gpu_hs.py
+//     test_division_paths_bitwise, tests/test_gpu_hs_quad.py
+//     test_quad_division_paths_bitwise;
+//   gradients at 2^-30, 2^-30 - ulp, 2^20 - ulp, 2^20 and beyond; alpha^2 at
+//     2^-40, below it, 2^40 - 2^17 and 2^40; sc at 2^-50, 2^-50 - ulp,
+//     2^30 - ulp, 2^30 and beyond; a at 2^-80; single lanes out of range;
+//     inf / NaN operands: tests/test_gpu_hs_division_range.py (cases 4, 5, 6,
+//     1-3, 7-8 of its docstring).
+// Two of the bounds are narrower than those tests can tell.  With the ballot's
+// upper bound loosened to 2^60, and with the precheck's gradient bound
+// loosened to 2^60, every test of that file gives the same result as with the
+// bounds above: |sc| up to 2^32 beside gradients below 2^20 keeps a below 2^52,
+// still more than 2^96 under the overflow threshold, and a gradient of 2^20 or
+// more puts the denominator at 2^40 or more, so hs_precheck_kernel's
+// denominator test already implies its upper gradient test.  The bounds stay
+// as they are: the argument above is made for them.
 __device__ __forceinline__ float recip_refined(float b) {
     const float r0 = __builtin_amdgcn_rcpf(b);
     return __builtin_fmaf(__builtin_fmaf(-b, r0, 1.0f), r0, r0);

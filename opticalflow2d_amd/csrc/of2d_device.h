@@ -535,8 +535,21 @@ void launch_regrid(const float2 *m_old, const float2 *est, float2 *est0, float2 
                    const float *Imov, float *Iaux, int dimx, int dimy, int P, hipStream_t st);
 void launch_compose_zero(const float2 *v, float2 *out, int dimx, int nrows, int P, int row0,
                          int dimy, hipStream_t st);
+// out rows [0, nrows) = warp2d of `raw` by a zero motion (field_kernels.hip):
+// the identity except beside non-finite pixels; reads raw row nrows where
+// row0 + nrows < dimy
+void launch_warp_zero_rows(const float *raw, float *out, int dimx, int nrows, int P, int row0,
+                           int dimy, hipStream_t st);
 void launch_add_motion(const float2 *a, const float2 *b, float2 *out, int dimx, int dimy, int P,
                        hipStream_t st);
+// (int)floorf(v) as the reference's x86-64 build converts it: a NaN gives
+// INT_MIN (cvttss2si), which the callers' range tests reject, where the
+// device's conversion gives 0, a pixel inside the grid.  (Values beyond int
+// give INT_MIN there and INT_MAX here: outside the grid either way.)
+__device__ __forceinline__ int floor_int(float v) {
+    return v == v ? (int)floorf(v) : (int)0x80000000;
+}
+
 // One pixel of Motion::accumulate (src/Motion.cpp:113-178): c + mo(x + c),
 // bilinear and renormalised by the valid weight; `own` where floor(x + c) falls
 // outside the grid.  Branch-free (field_kernels.hip, warp_px): the taps are
@@ -548,10 +561,10 @@ __device__ __forceinline__ float2 accumulate_px(const float2 *__restrict__ mo, f
                                                 float2 own, int i, int j, int dimx, int dimy,
                                                 int P) {
     const float px = (float)i + c.x;
-    const int dx = (int)floorf(px);
+    const int dx = floor_int(px);
     const float fx = px - (float)dx;
     const float py = (float)j + c.y;
-    const int dy = (int)floorf(py);
+    const int dy = floor_int(py);
     const float fy = py - (float)dy;
     const bool ok = !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
     const bool ax = dx < dimx - 1, ay = dy < dimy - 1, axy = ax && ay;

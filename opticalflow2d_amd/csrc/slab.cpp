@@ -11,7 +11,8 @@
 // bytes per iteration as a one-line exchange per step, a third of the
 // messages.  The exchange runs on its own stream while the interior row bands
 // compute; only the outer bands wait for it.  The gradients of the halo rows
-// are computed locally from three image halo rows (set_images).  The Logger's
+// are computed locally from three image halo rows (set_images; the moving
+// image's come from four raw rows below, see there).  The Logger's
 // norms (Logger.cpp:32-51) are fused into the stencil kernels per block,
 // reduced per rank, and all-reduced once per chunk of iterations (two doubles
 // per iteration) — the host then applies the reference's break test
@@ -20,8 +21,9 @@
 // equals the single-grid result bit for bit.
 //
 // The slab path registers with zero initial motion, one level, one refine:
-// warp2d by a zero field is the identity (src/Image.cpp:144-173 with fx=fy=0),
-// so Iaux == Imov and the gradients are taken of Imov directly.
+// warp2d by a zero field (src/Image.cpp:144-173 with fx=fy=0) is the identity
+// on finite pixels, and set_images applies it once (launch_warp_zero_rows), so
+// the field Imov holds Iaux and the gradients are taken of it.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -771,7 +773,7 @@ static int slab_create(of2d_slab **out, int dimx, int dimy, float alpha, int ran
         OF2D_HIP(hipMalloc(&s->d_status, 64 * sizeof(unsigned)));
         OF2D_HIP(hipMemset(s->d_status, 0, 64 * sizeof(unsigned)));
         OF2D_HIP(hipDeviceSynchronize());  // null-stream memset vs the non-blocking stream
-        OF2D_HIP(hipMalloc(&s->d_stage, sizeof(double) * 2 * (size_t)dimx * (s->nrows + 6)));
+        OF2D_HIP(hipMalloc(&s->d_stage, sizeof(double) * 2 * (size_t)dimx * (s->nrows + 7)));
         s->hs.ensure(s->chunk);
         reserve_sums(s, 3000);  // 48 KB: a fixed_iters run of 3000 iterations needs no allocation
         if (grp) {
@@ -850,17 +852,27 @@ int of2d_slab_create_local(of2d_slab **out, int dimx, int dimy, float alpha, int
 int of2d_slab_set_images(of2d_slab *s, const double *Iref_rows, const double *Imov_rows) {
     if (!s || !Iref_rows || !Imov_rows) return OF2D_ERR_INVALID_ARGUMENT;
     return sguard(s, [&] {
-        // rows [rb-3, re+3) clipped to [0, dimy) -> local rows [-up3, nrows+dn3)
+        // rows [rb-3, re+4) clipped to [0, dimy) -> local rows [-up3, nrows+dn4).
+        // Iaux is the moving image warped by the zero motion (Image::warp2d),
+        // which is the identity on finite pixels but spreads a NaN or inf
+        // pixel to its left and upper neighbours: the rows [-up3, nrows+dn3)
+        // the kernels read are warped from the raw rows, the last of which
+        // needs the raw row below it (the fourth halo row)
         const int up3 = std::min(3, s->rb), dn3 = std::min(3, s->dimy - s->re);
-        const int rows = s->nrows + up3 + dn3;
-        for (int which = 0; which < 2; which++) {
-            const double *src = which ? Imov_rows : Iref_rows;
-            of2d::Field<float> &dst = which ? s->Imov : s->Iref;
-            OF2D_HIP(hipMemcpyAsync(s->d_stage, src, sizeof(double) * s->dimx * rows,
-                                    hipMemcpyHostToDevice, s->st));
-            of2d::launch_d2f(s->d_stage, s->dimx, rows, dst.p - (long)up3 * s->P, s->P, 0,
-                             s->st);
-        }
+        const int dn4 = std::min(4, s->dimy - s->re);
+        const int rows3 = s->nrows + up3 + dn3, rows4 = s->nrows + up3 + dn4;
+        OF2D_HIP(hipMemcpyAsync(s->d_stage, Iref_rows, sizeof(double) * s->dimx * rows3,
+                                hipMemcpyHostToDevice, s->st));
+        of2d::launch_d2f(s->d_stage, s->dimx, rows3, s->Iref.p - (long)up3 * s->P, s->P, 0,
+                         s->st);
+        of2d::Field<float> raw;
+        raw.alloc(s->dimx, s->nrows, 4);
+        OF2D_HIP(hipMemcpyAsync(s->d_stage, Imov_rows, sizeof(double) * s->dimx * rows4,
+                                hipMemcpyHostToDevice, s->st));
+        of2d::launch_d2f(s->d_stage, s->dimx, rows4, raw.p - (long)up3 * s->P, s->P, 0, s->st);
+        of2d::launch_warp_zero_rows(raw.p - (long)up3 * s->P, s->Imov.p - (long)up3 * s->P,
+                                    s->dimx, rows3, s->P, s->rb - up3, s->dimy, s->st);
+        OF2D_HIP(hipStreamSynchronize(s->st));  // raw is freed on return
         slab_prepare(s);
     });
 }
@@ -955,7 +967,7 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
         const int Km = quads ? 4 : 3;
         const double npx = (double)s->dimx * s->dimy;
         unsigned *range_flag = s->d_status + of2d::kRangeFlagWord;
-        // Iaux == Imov (zero initial motion); its three ghost j-lines hold the
+        // the field Imov holds Iaux (set_images); its three ghost j-lines hold the
         // neighbours' image rows, as the gradients of the halo rows need
         const float *ia = use_gi(s) ? s->Imov.p : nullptr;
         namespace sched = of2d::sched;

@@ -111,9 +111,11 @@ def _bits(a):
 def test_division_paths_bitwise(gpu, oracle, case, gi):
     """The triple Jacobi kernel divides without div_scale where that is exact
     (hs_jacobi_impl.h div2_unscaled: gradients in 0 or [2^-30, 2^20), the
-    denominator in [2^-40, 2^40), sc in 0 or [2^-50, 2^30)) and takes the
-    compiler's IEEE sequence in every other wave-step.  Both give the oracle's
-    bits, signs of zero included.
+    denominator in [2^-40, 2^40), |sc| in [2^-50, 2^30) on every lane) and
+    takes the compiler's IEEE sequence in every other wave-step, those with
+    sc == 0 on some lane included.  Both give the oracle's bits, signs of zero
+    included.  (The high end and the exact bounds:
+    test_gpu_hs_division_range.py.)
       blob   It = 0 outside a 20 x 20 blob: the motion at the diffusion front is
              far below 2^-50 (scaled path there, fast path elsewhere);
       tiny   intensities ~1e-12: gradients below 2^-30 (scaled path everywhere);
