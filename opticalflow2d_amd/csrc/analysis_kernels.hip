@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256) void invert_step_kernel(const float2 *__restri
         if (i >= dimx || j >= dimy) continue;
         const long idx = (long)j * P + i;
         const float2 v = vin[idx];
-        const int dx = (int)floorf((float)i + v.x), dy = (int)floorf((float)j + v.y);
+        const int dx = floor_int((float)i + v.x), dy = floor_int((float)j + v.y);
         const bool ok = !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
         const float2 r = accumulate_px(u, v, make_float2(0.0f, 0.0f), i, j, dimx, dimy, P);
         vout[idx] = make_float2(v.x - r.x, v.y - r.y);

@@ -100,10 +100,10 @@ __device__ __forceinline__ void warp_batch(const float *__restrict__ Imov,
 #pragma unroll
     for (int q = 0; q < B; q++) {
         const float px = (float)a[q] + m[q].x;
-        const int dx = (int)floorf(px);
+        const int dx = floor_int(px);
         fx[q] = px - (float)dx;
         const float py = (float)b[q] + m[q].y;
-        const int dy = (int)floorf(py);
+        const int dy = floor_int(py);
         fy[q] = py - (float)dy;
         ok[q] = in[q] && !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
         ax[q] = dx < dimx - 1;
@@ -507,10 +507,10 @@ __device__ __forceinline__ void compose_px(const float2 *__restrict__ u, int i, 
         const bool in = j < dimy;
         own[k] = u[in ? ((unsigned)j * (unsigned)P + (unsigned)i) : 0u];
         const float px = (float)i + cv[k].x;
-        const int dx = (int)floorf(px);
+        const int dx = floor_int(px);
         fx[k] = px - (float)dx;
         const float py = (float)j + cv[k].y;
-        const int dy = (int)floorf(py);
+        const int dy = floor_int(py);
         fy[k] = py - (float)dy;
         ok[k] = in && !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
         ax[k] = dx < dimx - 1;
@@ -1040,10 +1040,10 @@ __global__ void exp_square_kernel(const float2 *__restrict__ mo, float2 *__restr
     }
     float2 out = c;
     const float px = (float)i + c.x;
-    const int dx = (int)floorf(px);
+    const int dx = floor_int(px);
     const float fx = px - (float)dx;
     const float py = (float)j + c.y;
-    const int dy = (int)floorf(py);
+    const int dy = floor_int(py);
     const float fy = py - (float)dy;
     if (!(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy)) {
         const float2 *b = mo + (long)dy * P + dx;

@@ -108,10 +108,10 @@ __device__ __forceinline__ void upsample_motion_px(const float2 *__restrict__ in
 __device__ __forceinline__ float warp_px(const float *__restrict__ src, float2 m, float own, int i,
                                          int j, int dimx, int dimy, int P) {
     const float px = (float)i + m.x;
-    const int dx = (int)floorf(px);
+    const int dx = floor_int(px);
     const float fx = px - (float)dx;
     const float py = (float)j + m.y;
-    const int dy = (int)floorf(py);
+    const int dy = floor_int(py);
     const float fy = py - (float)dy;
     const bool ok = !(dx < 0 || dx >= dimx || dy < 0 || dy >= dimy);
     const bool ax = dx < dimx - 1, ay = dy < dimy - 1;

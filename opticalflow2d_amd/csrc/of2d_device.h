@@ -545,7 +545,13 @@ void launch_add_motion(const float2 *a, const float2 *b, float2 *out, int dimx, 
 // (int)floorf(v) as the reference's x86-64 build converts it: a NaN gives
 // INT_MIN (cvttss2si), which the callers' range tests reject, where the
 // device's conversion gives 0, a pixel inside the grid.  (Values beyond int
-// give INT_MIN there and INT_MAX here: outside the grid either way.)
+// give INT_MIN there and INT_MAX here: outside the grid either way.)  Every
+// conversion of a sampling coordinate goes through it: accumulate_px below,
+// warp_px (field_px.h), compose_zero_kernel (field_kernels.hip), warp_batch,
+// compose_px and exp_square_kernel (demons_kernels.hip) and the out-of-bounds
+// count of invert_step_kernel (analysis_kernels.hip).  upsample_motion_px
+// converts finite grid coordinates only and keeps the bare conversion.
+// Held by tests/test_gpu_nonfinite_sampling.py.
 __device__ __forceinline__ int floor_int(float v) {
     return v == v ? (int)floorf(v) : (int)0x80000000;
 }

@@ -121,11 +121,22 @@ def test_jacobian_of_zero_motion(gpu):
 
 
 # ------------------------------------------------------------------ inverse
+def planted_field(dimx, dimy, amp, planted=()):
+    """sinusoids with NaN on the (j, i, component) words of `planted`."""
+    u = sinusoids(dimx, dimy, amp).copy()
+    for j, i, c in planted:
+        u[j, i, c] = np.nan
+    return frozen(u)
+
+
 @functools.lru_cache(maxsize=None)
-def invert_ref(dimx, dimy, amp, max_iter, tol):
-    """The loop of of2d_field_invert restated around oracle_accumulate."""
+def invert_ref(dimx, dimy, amp, max_iter, tol, planted=()):
+    """The loop of of2d_field_invert restated around oracle_accumulate.  The
+    range test is the reference's, with its x86 conversion: a NaN coordinate
+    converts to INT_MIN, which is outside the grid (as accumulate_px and
+    oracle_accumulate take it)."""
     from oracle import oracle as O
-    u = sinusoids(dimx, dimy, amp)
+    u = planted_field(dimx, dimy, amp, planted)
     i = np.arange(dimx, dtype=F)[None, :]
     j = np.arange(dimy, dtype=F)[:, None]
     v = np.zeros_like(u)
@@ -133,12 +144,14 @@ def invert_ref(dimx, dimy, amp, max_iter, tol):
     for _ in range(max_iter):
         r = u.copy()
         O.lib().oracle_accumulate(r.reshape(-1), v.reshape(-1), dimx, dimy)
-        fx, fy = np.floor(i + v[..., 0]), np.floor(j + v[..., 1])
-        oob = (fx < 0) | (fx >= dimx) | (fy < 0) | (fy >= dimy)
+        with np.errstate(invalid="ignore"):
+            fx, fy = np.floor(i + v[..., 0]), np.floor(j + v[..., 1])
+            oob = (fx < 0) | (fx >= dimx) | (fy < 0) | (fy >= dimy) | np.isnan(fx) | np.isnan(fy)
         r[oob] = 0
         v = v - r
         assert v.dtype == F
-        res.append(np.abs(r).max())
+        with np.errstate(invalid="ignore"):
+            res.append(np.abs(r).max())  # NaN if any r is
         n_oob = int(oob.sum())
         if res[-1] < F(tol):
             conv = True
@@ -205,6 +218,34 @@ def test_invert_chunk_boundary(gpu, oracle):
         same(res, longest[:max_iter], f"prefix of {max_iter} updates")
     _, info, _ = check_invert(64, 64, 2.0, 50, tol=1e-5)
     assert info["converged"] and INVERT_CHUNK < info["iterations"] < 2 * INVERT_CHUNK
+
+
+NAN_PLANTS = ((0, 0, 0), (16, 40, 1), (32, 64, 0))  # first pixel, interior, last pixel
+
+
+@pytest.mark.parametrize("max_iter", [1, 2, 3])
+def test_invert_nan_pixels(gpu, oracle, max_iter):
+    """65 x 33 with three NaN words.  The first update starts from v = 0, so
+    its coordinates are finite and the NaN arrives through the sampled values
+    (at the planted pixels and their left and upper neighbours, weight 0); from
+    the second update on those pixels carry a NaN coordinate with an in-range
+    partner, which the reference's conversion puts outside the grid: they are
+    counted, keep their v, and the count agrees with the composition two lines
+    below it.  A NaN residual is never below the tolerance."""
+    dimx, dimy, amp, tol = 65, 33, 1.0, 1e-3
+    want_v, want_res, want_oob, want_conv = invert_ref(dimx, dimy, amp, max_iter, tol, NAN_PLANTS)
+    assert not want_conv and len(want_res) == max_iter and np.isnan(want_res).all()
+    assert np.isnan(want_v).sum() <= 0.25 * want_v.size
+    assert (want_oob > 0) == (max_iter > 1)
+    v, info, res = field.invert(planted_field(dimx, dimy, amp, NAN_PLANTS), max_iter=max_iter,
+                                tol=tol)
+    print(f"{max_iter} updates: {info}, oracle out_of_bounds {want_oob}")
+    assert info["iterations"] == max_iter and not info["converged"]
+    assert np.isnan(res).all() and np.isnan(info["residual"])
+    assert info["out_of_bounds"] == want_oob
+    nan = np.isnan(want_v)
+    assert np.array_equal(np.isnan(v), nan)
+    same(np.where(nan, F(0), v), np.where(nan, F(0), want_v), "inverse field beside the NaN")
 
 
 def test_invert_repeatable(gpu):

@@ -18,11 +18,14 @@ both paths), displacements of -0.0 and +-1e-40; values of mixed sign, up to
 test_inputs_reach_what_they_claim (CPU) classifies every pixel the way the
 kernels do and asserts each class is there.
 
-Every input is finite and every |coordinate| < 2^30: beyond that, and for NaN,
-the reference's (int)floor(...) is undefined, the oracle only shows what x86
-happens to do, and NaN sign bits differ between x86 and the GPU.  Gradients and
-the Demons force need dimx, dimy >= 2: the reference's one-sided differences
-read past a one-pixel axis.
+Every input here is finite and every |coordinate| < 2^30.  NaN, inf and
+beyond-int coordinates and non-finite sources live in
+test_gpu_nonfinite_sampling.py, which holds the kernels to what the
+reference's x86-64 build does with (int)floor(...) there (cvttss2si: INT_MIN,
+so the pixel is outside and keeps its own value) and compares NaN positions
+instead of NaN sign and payload, which differ between x86 and the GPU.
+Gradients and the Demons force need dimx, dimy >= 2: the reference's one-sided
+differences read past a one-pixel axis.
 
 Arrays are in the C-ABI's layout: image [dimy, dimx], motion [dimy, dimx, 2].
 
