@@ -4,8 +4,10 @@
 Every frame is the first one translated a little further; BatchRegistration
 runs the 64 Horn-Schunck registrations together (one workgroup per frame, each
 stopping on its own iteration) and the per-frame iteration counts are printed.
+With --reg 3 the registrations are Thirion's Demons (parameters 1, 0.25, 1.5,
+2.5, kernel width 5, Composition).
 
-    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300]
+    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
 """
 import argparse
 import os
@@ -25,6 +27,8 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--niter", type=int, default=300)
     ap.add_argument("--alpha", type=float, default=0.3)
+    ap.add_argument("--reg", type=int, default=0, choices=[0, 3],
+                    help="0 Horn-Schunck (alpha), 3 Thirion's Demons")
     a = ap.parse_args()
     n, B = a.size, a.frames
     ref, _ = S.texture_pair(n, seed=3, sigma=3.0)
@@ -34,7 +38,8 @@ def main():
     # texture_pair's second image is its first (one seed: ref) shifted bilinearly
     frames = np.stack([S.texture_pair(n, seed=3, sigma=3.0, shift=(sx, sy))[1]
                        for sx, sy in shifts])
-    with BatchRegistration(B, (n, n), [a.niter, a.niter], 1, a.alpha) as b:
+    params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
+    with BatchRegistration(B, (n, n), [a.niter, a.niter], 1, params, reg=a.reg) as b:
         b.register(ref, frames)  # one reference shared by every frame
         motion = b.motion()
         iters = b.iterations()

@@ -344,12 +344,19 @@ int of2d_image_similarity(const float *a, const float *b, int dimx, int dimy, do
  * of2d_warp takes, on the device */
 int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *out);
 
-/* ---- batched Horn-Schunck: many small pairs of one size in one call ----
- * nbatch independent Diffusion registrations with the same parameters.  Each
+/* ---- batched Horn-Schunck and Thirion's Demons: many small pairs of one
+ * size in one call ----
+ * nbatch independent registrations with the same parameters, reg =
+ * OF2D_REG_DIFFUSION (regparams = {alpha}) or OF2D_REG_THIRIONS_DEMONS
+ * (regparams = {sigma_i, sigma_x, sigma_diffusion, sigma_fluid, kernel_width,
+ * accumulation}, of2d_create's six: Composition 0 or Addition 1, any other
+ * value leaves the motion without the correction as of2d_create does; any
+ * kernel_width >= 1, even and wider than the image included).  Each
  * pair is run by one workgroup with the whole iteration loop inside the
  * kernel; the passes around the loop (pyramid, warp, gradients, composition)
  * take the pair as a grid dimension, so the kernel launches of one estimate do
- * not depend on nbatch.  The pyramid and refine sequence, the per-pixel
+ * not depend on nbatch.  (Demons has no gradients pass: its loop warps the
+ * moving image by the iterate and differentiates it in every iteration.)  The pyramid and refine sequence, the per-pixel
  * arithmetic and therefore the motion of every pair are those of of2d_create /
  * of2d_estimate on that pair alone (a new context's first estimate: every
  * of2d_batch_estimate starts from a zero motion field), bit for bit when the
@@ -369,10 +376,13 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  *
  * of2d_batch_create refuses with OF2D_ERR_INVALID_ARGUMENT and a message
  * (of2d_batch_last_error(NULL)), before any device work: nbatch < 1 or > 65535,
- * a reg other than OF2D_REG_DIFFUSION, nparams != 1 (the reference's message),
+ * a reg other than OF2D_REG_DIFFUSION and OF2D_REG_THIRIONS_DEMONS, nparams !=
+ * 1 (Diffusion) or != 6 (Demons; the reference's message), a Demons
+ * kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
  * Options: "fixed_iters", "device" (before first use); an unknown key is
- * refused.  Splitting one pair over several workgroups is not offered: with
+ * refused ("demons_separable" among them: the batch smooths with the direct
+ * convolution only).  Splitting one pair over several workgroups is not offered: with
  * fewer pairs than compute units most of the device idles. */
 typedef struct of2d_batch of2d_batch;
 #define OF2D_BATCH_MAXPX (512 * 512)

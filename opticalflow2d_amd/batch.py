@@ -1,9 +1,10 @@
-"""Batched Horn-Schunck: many small image pairs of one size in one call.
+"""Batched Horn-Schunck and Thirion's Demons: many small image pairs of one
+size in one call.
 
 :class:`BatchRegistration` is the object-style handle on ``of2d_batch_*``
-(include/of2d.h): ``nbatch`` independent Diffusion registrations with the same
-parameters, each run by one workgroup with the whole iteration loop inside the
-kernel.  Arrays follow :class:`ImageRegistration`'s convention with a leading
+(include/of2d.h): ``nbatch`` independent Diffusion or Thirion's Demons
+registrations with the same parameters, each run by one workgroup with the
+whole iteration loop inside the kernel.  Arrays follow :class:`ImageRegistration`'s convention with a leading
 pair axis: an image is ``[dimx, dimy]`` (x first), a stack of them
 ``[nbatch, dimx, dimy]`` and the motion ``[nbatch, dimx, dimy, 2]``.
 """
@@ -16,27 +17,34 @@ import numpy as np
 
 from . import _device, _lib
 from ._lib import check
+from .registration import Regularisation
 
 #: most pixels a batch image may have (include/of2d.h OF2D_BATCH_MAXPX)
 BATCH_MAXPX = 512 * 512
 
 
 class BatchRegistration:
-    """``nbatch`` Horn-Schunck registrations of ``dims = (dimx, dimy)`` images.
+    """``nbatch`` registrations of ``dims = (dimx, dimy)`` images.
 
     ``niter`` (nscales+1 values, finest level first), ``nscales``, ``alpha``
-    and ``nrefine`` are :class:`ImageRegistration`'s for Diffusion.  Keyword
-    options map to ``of2d_batch_set_option``: ``fixed_iters``, ``device``.
+    and ``nrefine`` are :class:`ImageRegistration`'s.  ``reg`` is
+    ``Regularisation.Diffusion`` (the default; ``alpha`` is Horn-Schunck's one
+    parameter) or ``Regularisation.ThirionsDemons`` (3), for which ``alpha``
+    carries the one-pair path's six parameters ``[sigma_i, sigma_x,
+    sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
+    method is refused.  The other keyword options map to
+    ``of2d_batch_set_option``: ``fixed_iters``, ``device``.
     With convergence on, every pair stops on its own iteration; the errors are
     those of ``logger_fp64=1`` (fp64 sums in a fixed order).
     """
 
     def __init__(self, nbatch: int, dims: Sequence[int], niter: Sequence[int], nscales: int,
-                 alpha: float, nrefine: int = 1, **options):
+                 alpha, nrefine: int = 1, *, reg: int = Regularisation.Diffusion, **options):
         L = _lib.lib()
         self.nbatch = int(nbatch)
         self.dimx, self.dimy = int(dims[0]), int(dims[1])
         self.nscales, self.nrefine = int(nscales), int(nrefine)
+        self.reg = int(reg)
         nit = np.ascontiguousarray(np.asarray(niter, dtype=np.int32).reshape(-1)[: max(nscales, 0) + 1])
         if nit.size < nscales + 1:
             raise ValueError("niter needs nscales+1 entries")
@@ -44,7 +52,8 @@ class BatchRegistration:
         self._h = None
         h = C.c_void_p()
         st = L.of2d_batch_create(C.byref(h), self.nbatch, self.dimx, self.dimy, nit,
-                                 self.nscales, 0, p if p.size else np.zeros(1, np.float32),
+                                 self.nscales, self.reg,
+                                 p if p.size else np.zeros(1, np.float32),
                                  int(p.size), self.nrefine)
         check(st, L.of2d_batch_last_error(None).decode())
         self._h = h

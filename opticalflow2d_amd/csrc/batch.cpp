@@ -1,6 +1,8 @@
-// batch.cpp — host driver of the batched Horn-Schunck registration
-// (of2d_batch.h).  The pyramid and refine sequence is that of
-// Registration::estimate / estimate_level for Diffusion (registration.cpp),
+// batch.cpp — host driver of the batched Horn-Schunck and Thirion's Demons
+// registrations (of2d_batch.h).  The pyramid and refine sequence is that of
+// Registration::estimate / estimate_level for Diffusion and Thirion's Demons
+// (registration.cpp; Demons takes no gradients pass: its loop warps and
+// differentiates the moving image itself),
 // applied to all pairs at once: the host enqueues every level's launches and
 // reads nothing back until the estimate ends; every decision (a pair's break,
 // its divide-by-zero) is taken in the kernels.  The number of launches does
@@ -17,13 +19,14 @@ namespace batch {
 
 Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int reg,
              const float *params, unsigned nparams, int nrefine)
-    : B_(nbatch), dimx_(dimx), dimy_(dimy), nscales_(nscales), nrefine_(nrefine) {
+    : B_(nbatch), dimx_(dimx), dimy_(dimy), nscales_(nscales), nrefine_(nrefine), reg_(reg) {
     if (nbatch < 1) throw std::invalid_argument("Error: batch needs nbatch >= 1\n");
     if (nbatch > kMaxPairs)
         throw std::invalid_argument("Error: batch takes at most 65535 pairs per call\n");
-    if (reg != 0)
+    if (reg != 0 && reg != 3)
         throw std::invalid_argument(
-            "Error: the batched registration supports Diffusion regularisation only\n");
+            "Error: the batched registration supports Diffusion regularisation only, or "
+            "Thirion's Demons\n");
     if (!valid_regularisation_parameters(reg, nparams))
         throw std::invalid_argument(
             "Invalid number of regularisation parameters for given regularisation method.\n");
@@ -36,7 +39,15 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
         throw std::invalid_argument(
             "Error: batch images may have at most 512 * 512 pixels (OF2D_BATCH_MAXPX)\n");
     niter_.assign(niter, niter + nscales + 1);
-    alpha_ = params[0];
+    params_.assign(params, params + nparams);
+    if (reg == 3) {  // Demons.cpp:19-23, as Registration::Registration
+        const int kw = (int)(unsigned)params[4];
+        if (kw < 1) throw std::invalid_argument("Error: Demons kernel width must be >= 1\n");
+        kdiff_ = gaussian_kernel(kw, params[2]);
+        kfluid_ = gaussian_kernel(kw, params[3]);
+    } else {
+        alpha_ = params[0];
+    }
     // ImageRegistration.cpp:56-61: dim(dimin.x/scale, dimin.y/scale) with float scale
     ldx_.resize(nscales + 1);
     ldy_.resize(nscales + 1);
@@ -61,6 +72,10 @@ void Batch::release_device() {
     if (d_status_) (void)hipFree(d_status_);
     if (d_iters_) (void)hipFree(d_iters_);
     if (d_errs_) (void)hipFree(d_errs_);
+    if (d_kf_) (void)hipFree(d_kf_);
+    if (d_kd_) (void)hipFree(d_kd_);
+    d_kf_ = nullptr;
+    d_kd_ = nullptr;
     d_stage_ = nullptr;
     d_status_ = nullptr;
     d_iters_ = nullptr;
@@ -129,6 +144,23 @@ void Batch::allocate_device() {
         L.dI.alloc(L.dx, L.dy, B_);
         L.est[0].alloc(L.dx, L.dy, B_);
         L.est[1].alloc(L.dx, L.dy, B_);
+        if (reg_ == 3) L.mid.alloc(L.dx, L.dy, B_);
+    }
+    if (reg_ == 3) {
+        // both tables once per Batch, sigma_fluid's first (Registration::loop_demons)
+        const size_t n = kfluid_.size();
+        std::vector<float> kf(2 * n);
+        std::vector<double> kd(2 * n);
+        for (size_t t = 0; t < n; t++) {
+            kf[t] = (float)kfluid_[t];
+            kd[t] = kfluid_[t];
+            kf[n + t] = (float)kdiff_[t];
+            kd[n + t] = kdiff_[t];
+        }
+        OF2D_HIP(hipMalloc(&d_kf_, sizeof(float) * 2 * n));
+        OF2D_HIP(hipMalloc(&d_kd_, sizeof(double) * 2 * n));
+        OF2D_HIP(hipMemcpy(d_kf_, kf.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+        OF2D_HIP(hipMemcpy(d_kd_, kd.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
     }
     stage_pairs_ = chunk_pairs();
     OF2D_HIP(hipMalloc(&d_stage_, stage_pairs_ * 2 * (size_t)dimx_ * dimy_ * sizeof(double)));
@@ -247,8 +279,9 @@ void Batch::estimate() {
             // *Iaux = *Imov; Iaux->warp2d(*motion)
             launch_warp(L.Imov.p, L.motion[L.mcur].p, L.Iaux.p, L.stride, L.dx, L.dy, L.P, B_,
                         d_status_, st_);
-            launch_gradients(L.Iref.p, shared_ ? 0 : L.stride, L.Iaux.p, L.dI.p, L.It.p, L.stride,
-                             L.dx, L.dy, L.P, B_, d_status_, st_);
+            if (reg_ == 0)
+                launch_gradients(L.Iref.p, shared_ ? 0 : L.stride, L.Iaux.p, L.dI.p, L.It.p,
+                                 L.stride, L.dx, L.dy, L.P, B_, d_status_, st_);
             // motion_est starts at zero
             OF2D_HIP(hipMemsetAsync(L.est[0].base, 0, L.est[0].bytes(), st_));
             LoopArgs a;
@@ -269,14 +302,17 @@ void Batch::estimate() {
             a.errs = d_errs_;
             a.maxn = maxn_;
             OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
-            launch_hs_loop(a, B_, conv, st_);
+            if (reg_ == 3)
+                launch_demons_loop(demons_args(L, s, loop), B_, conv, st_);
+            else
+                launch_hs_loop(a, B_, conv, st_);
             OF2D_HIP(hipEventRecord(ev_[2 * loop + 1], st_));
             // motion->accumulate(*motion_est)
             launch_accumulate(L.motion[L.mcur].p, L.est[0].p, L.est[1].p, L.motion[1 - L.mcur].p,
                               L.stride, L.dx, L.dy, L.P, B_, d_iters_, nloops_, loop, d_status_,
                               st_);
             L.mcur ^= 1;
-            launches_ += 4;
+            launches_ += reg_ == 0 ? 4 : 3;  // Demons: no gradients launch
         }
         if (s > 0) {
             launch_upsample_motion(L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P,
@@ -311,6 +347,43 @@ void Batch::estimate() {
             pair_err_ = "Divide by zero exception (pair " + std::to_string(k) + ")";
             break;
         }
+}
+
+// the loop launch of level s (L) for Thirion's Demons: the iterate in est[],
+// It as the warped image, dI as the correction
+DemonsLoopArgs Batch::demons_args(BLevel &L, int s, int loop) const {
+    const size_t n = kfluid_.size();
+    const int kw = (int)(unsigned)params_[4];
+    DemonsLoopArgs a;
+    a.u0 = L.est[0].p;
+    a.u1 = L.est[1].p;
+    a.Iref = L.Iref.p;
+    a.sref = shared_ ? 0 : L.stride;
+    a.Iaux = L.Iaux.p;
+    a.W = L.It.p;
+    a.corr = L.dI.p;
+    a.mid = L.mid.p;
+    a.stride = L.stride;
+    a.dx = L.dx;
+    a.dy = L.dy;
+    a.P = L.P;
+    a.niter = niter_[s];
+    // Demons.cpp:48-49
+    a.sigma_isq = params_[0] * params_[0];
+    a.sigma_xsq = params_[1] * params_[1];
+    a.fluid = DemonsTable{d_kf_, d_kd_, full_weight(kfluid_, kw)};
+    a.diff = DemonsTable{d_kf_ + n, d_kd_ + n, full_weight(kdiff_, kw)};
+    a.kw = kw;
+    // static_cast<MotionAccumulation>((int) regparams[5]), as loop_demons
+    const int accum = (int)params_[5];
+    a.mode = accum == 0 ? 0 : (accum == 1 ? 1 : 2);
+    a.status = d_status_;
+    a.iters = d_iters_;
+    a.nloops = nloops_;
+    a.loop = loop;
+    a.errs = d_errs_;
+    a.maxn = maxn_;
+    return a;
 }
 
 void Batch::get_motion(double *out) {

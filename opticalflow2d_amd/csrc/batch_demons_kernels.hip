@@ -1,0 +1,240 @@
+// batch_demons_kernels.hip — B independent Thirion's Demons registrations of
+// one size (of2d_batch.h).
+//
+// The loop kernel: one workgroup per pair runs the niter iterations of
+// DemonsThirions::get_update (src/regularization/Demons/DemonsThirions.cpp:
+// 18-42) for its pair, with __syncthreads() as the only synchronisation.  An
+// iteration is five stages through the pair's slices in global memory, a
+// barrier after each (a stage reads its predecessor's values at other pixels):
+//   1  W    = warp2d(Iaux, u)                        Image.cpp:119-182 (warp_px)
+//   2  c    = -dI It / (|dI|^2 + It^2 si^2 / sx^2)   IterativeSolver.cpp:22-56,
+//             with dI = grad(W), It = W - Iref       Demons.cpp:34-63
+//   3  c   <- c (*) G(sigma_fluid)                   Field.tpp:209-269
+//   4  mid  = accumulate(u, c) | u + c | u           DemonsThirions.cpp:33-38,
+//                                                    Motion.cpp:113-178
+//   5  u'   = mid (*) G(sigma_diffusion), plus the Logger sums against u
+// Stages 3 and 4 are one pass: the update gathers u, not c.  Thread t takes
+// pixels t, t + T, ... in ascending linear index in every stage.
+//
+// The per-pixel arithmetic restates the one-pair kernels' (demons_kernels.hip:
+// demons_corr without the power-of-two multiply, whose bits are the
+// division's; conv_px without the LDS tile; the borders of
+// demons_force_kernel) and shares warp_px and accumulate_px with them,
+// compiled with -ffp-contract=off and IEEE division: the iterates are
+// bit-identical to the one-pair path's and the oracle's.
+//
+// Convergence is the HS loop's (batch_kernels.hip): fp64 sums of logger_mag in
+// a fixed order, logger_error's float arithmetic and the reference's break by
+// the workgroup's first thread: the "logger_fp64" semantics.
+//
+// A zero denominator (coord2d.h:95-100) sets the pair's kStatusDivZero; the
+// workgroup learns it at the barrier after stage 2 and leaves the loop.
+#include "of2d_batch.h"
+
+#include "field_px.h"
+
+namespace of2d {
+namespace batch {
+
+namespace {
+
+// Field<vector2d>::convolute (Field.tpp:209-269) at pixel (i, j) of the
+// pitched field f: the direct kw x kw sum over the taps whose LINEAR index
+// lin + ii + jj * dimx lies in [0, N) (a tap past an x edge is the
+// neighbouring j-line's pixel), ii outer / jj inner, fp32 products and sums
+// with (float) weights; divided by (float) of the fp64 sum of the valid
+// weights (wfull where every tap is valid: the same additions in the same
+// order).  false: the weight sum is 0 and the reference leaves the pixel.
+// KW > 0: the width at compile time (the taps unrolled, the weights in scalar
+// registers); KW == 0: the runtime width kw_rt.  The same operations in the
+// same order either way.
+template <int KW>
+__device__ __forceinline__ bool conv_direct(const float2 *__restrict__ f, const DemonsTable &k,
+                                            int kw_rt, int i, int j, int dx, int dy, int P,
+                                            float2 &out) {
+    const int kw = KW > 0 ? KW : kw_rt;
+    const int c = (kw - 1) / 2;
+    const long N = (long)dx * dy, lin = (long)j * dx + i;
+    const bool interior = (lin - c - (long)c * dx >= 0) && (lin + c + (long)c * dx < N);
+    float vx = 0.0f, vy = 0.0f;
+    double weight = 0.0;
+#pragma unroll
+    for (int ii = -c; ii <= c; ii++) {
+        // column i + ii of j-line j + jj is pixel (col, j + jj + r)
+        int col = i + ii, r = 0;
+        while (col < 0) {  // once unless c > dx
+            col += dx;
+            r -= 1;
+        }
+        while (col >= dx) {
+            col -= dx;
+            r += 1;
+        }
+        const float *kf = k.kf + (ii + c);
+        if (interior) {
+            const float2 *p = f + (long)(j + r - c) * P + col;
+#pragma unroll
+            for (int q = 0; q <= 2 * c; q++) {  // q = jj + c
+                const float2 t = p[(long)q * P];
+                const float w = kf[q * kw];
+                vx = vx + t.x * w;
+                vy = vy + t.y * w;
+            }
+        } else {
+            const double *kd = k.kd + (ii + c);
+#pragma unroll
+            for (int q = 0; q <= 2 * c; q++) {
+                const int row = j + r + q - c;
+                // 0 <= col < dx: row * dx + col is in [0, N) iff the row is
+                if ((unsigned)row >= (unsigned)dy) continue;  // Field.tpp:245-247
+                const float2 t = f[(long)row * P + col];
+                const float w = kf[q * kw];
+                vx = vx + t.x * w;
+                vy = vy + t.y * w;
+                weight += kd[q * kw];
+            }
+        }
+    }
+    if (interior) weight = k.wfull;
+    if (weight == 0) return false;
+    const float wf = (float)weight;  // coord2d::operator/(const T&) with T = float
+    out = make_float2(vx / wf, vy / wf);
+    return true;
+}
+
+template <int WAVES, bool CONV, int KW>
+__global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs a) {
+    constexpr int T = 64 * WAVES;
+    const long pair = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int *iters = a.iters + pair * a.nloops + a.loop;
+    if (a.status[pair] & kStatusDivZero) {  // an earlier loop's: nothing runs
+        if (tid == 0) *iters = 0;
+        return;
+    }
+    float2 *u0 = a.u0 + pair * a.stride, *u1 = a.u1 + pair * a.stride;
+    const float *__restrict__ Iref = a.Iref + pair * a.sref;
+    const float *__restrict__ Iaux = a.Iaux + pair * a.stride;
+    float *W = a.W + pair * a.stride;
+    float2 *C = a.corr + pair * a.stride, *M = a.mid + pair * a.stride;
+    float *errs = CONV ? a.errs + (pair * a.nloops + a.loop) * (long)a.maxn : nullptr;
+    const int dx = a.dx, dy = a.dy, P = a.P, npx = dx * dy, kw = a.kw;
+    const float nf = (float)(double)npx;  // logger_error: (float)npx
+    __shared__ int s_stop, s_bad;
+    if (tid == 0) s_stop = s_bad = 0;  // published by the barrier after stage 1
+    int n = 0;
+    bool bad = false;
+    for (int it = 0; it < a.niter; ++it) {
+        const float2 *src = (it & 1) ? u1 : u0;
+        float2 *dst = (it & 1) ? u0 : u1;
+        // 1. the moving image by the iterate
+        for (int idx = tid; idx < npx; idx += T) {
+            const int j = idx / dx, i = idx - j * dx;
+            const long o = (long)j * P + i;
+            W[o] = warp_px(Iaux, src[o], Iaux[o], i, j, dx, dy, P);
+        }
+        __syncthreads();
+        // 2. the correction: gradients.h:9-32 (central / 2.0f, one-sided on the
+        // borders; with one column f[idx + 1] is the next j-line's pixel, as
+        // gradients_px has it), It = W - Iref, Demons.cpp:57
+        for (int idx = tid; idx < npx; idx += T) {
+            const int j = idx / dx, i = idx - j * dx;
+            const long o = (long)j * P + i;
+            const float w0 = W[o];
+            float gx, gy;
+            if (i == 0)
+                gx = (dx > 1 ? W[o + 1] : (j < dy - 1 ? W[o + P] : 0.0f)) - w0;
+            else if (i == dx - 1)
+                gx = w0 - W[o - 1];
+            else
+                gx = (W[o + 1] - W[o - 1]) / 2.0f;
+            if (j == 0)
+                gy = W[o + P] - w0;
+            else if (j == dy - 1)
+                gy = w0 - W[o - P];
+            else
+                gy = (W[o + P] - W[o - P]) / 2.0f;
+            const float It = w0 - Iref[o];
+            // dI * It / (dI.x^2 + dI.y^2 + It*It*sigma_isq/sigma_xsq) * -1
+            const float t = (It * It) * a.sigma_isq;
+            const float den = (gx * gx + gy * gy) + t / a.sigma_xsq;
+            bad |= den == 0.0f;
+            C[o] = make_float2(((gx * It) / den) * -1.0f, ((gy * It) / den) * -1.0f);
+        }
+        if (bad) s_bad = 1;
+        __syncthreads();
+        if (s_bad) break;  // block-uniform: the reference throws here
+        // 3 + 4. the smoothed correction and the motion update
+        for (int idx = tid; idx < npx; idx += T) {
+            const int j = idx / dx, i = idx - j * dx;
+            const long o = (long)j * P + i;
+            float2 c;
+            if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
+            const float2 own = src[o];
+            float2 m = own;  // another enum value: no update
+            if (a.mode == 0)
+                m = accumulate_px(src, c, own, i, j, dx, dy, P);
+            else if (a.mode == 1)
+                m = make_float2(own.x + c.x, own.y + c.y);  // Field::operator+=
+            M[o] = m;
+        }
+        __syncthreads();
+        // 5. the smoothed motion into the other buffer, and the Logger's terms
+        double v[2] = {0.0, 0.0};
+        for (int idx = tid; idx < npx; idx += T) {
+            const int j = idx / dx, i = idx - j * dx;
+            const long o = (long)j * P + i;
+            float2 nw;
+            if (!conv_direct<KW>(M, a.diff, kw, i, j, dx, dy, P, nw)) nw = M[o];
+            if constexpr (CONV) logger_add(nw, src[o], v[0], v[1]);
+            dst[o] = nw;
+        }
+        n = it + 1;
+        if constexpr (CONV) {
+            block_sums<2, WAVES>(v, wave, lane);
+            if (tid == 0) {
+                // logger_error (registration.cpp) on the device
+                const float prevnorm = (float)v[1] / nf;
+                const float diffnorm = (float)v[0] / nf;
+                const float err = prevnorm == 0 ? 0.0f : diffnorm / prevnorm;
+                errs[it] = err;
+                s_stop = (err < 0.001f && it > 1) ? 1 : 0;
+            }
+        }
+        // the iterate is complete (and the decision published) for every thread
+        __syncthreads();
+        if constexpr (CONV) {
+            if (s_stop) break;
+        }
+    }
+    if (tid == 0) *iters = n;
+    if (__any(bad) && lane == 0) atomicOr(a.status + pair, kStatusDivZero);
+}
+
+}  // namespace
+
+namespace {
+template <int KW>
+void launch_width(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st) {
+    if (conv)
+        hipLaunchKernelGGL((demons_loop_kernel<kLoopWaves, true, KW>), dim3(B),
+                           dim3(kLoopThreads), 0, st, a);
+    else
+        hipLaunchKernelGGL((demons_loop_kernel<kLoopWaves, false, KW>), dim3(B),
+                           dim3(kLoopThreads), 0, st, a);
+}
+}  // namespace
+
+// the usual widths are compiled in; every other one takes the runtime loops
+void launch_demons_loop(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st) {
+    switch (a.kw) {
+        case 3: launch_width<3>(a, B, conv, st); break;
+        case 5: launch_width<5>(a, B, conv, st); break;
+        case 7: launch_width<7>(a, B, conv, st); break;
+        default: launch_width<0>(a, B, conv, st); break;
+    }
+    OF2D_HIP(hipGetLastError());
+}
+
+}  // namespace batch
+}  // namespace of2d

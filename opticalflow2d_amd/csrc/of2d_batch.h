@@ -1,5 +1,6 @@
-// of2d_batch.h — B independent Horn-Schunck registrations of one size in one
-// call (batch.cpp, batch_kernels.hip).
+// of2d_batch.h — B independent Horn-Schunck or Thirion's Demons registrations
+// of one size in one call (batch.cpp, batch_kernels.hip,
+// batch_demons_kernels.hip).
 //
 // Layout: the B fields of a pyramid level live in one allocation, pair k at
 // k * stride elements, each laid out exactly as a Field<T> (of2d_host.h): the
@@ -50,6 +51,40 @@ struct LoopArgs {
 // conv: Logger sums, errors and the reference's break (fp64 sums in a fixed
 // order: the logger_fp64 semantics); otherwise exactly niter iterations
 void launch_hs_loop(const LoopArgs &a, int B, bool conv, hipStream_t st);
+
+// One Gaussian table of the Demons loop on the device (Batch::allocate_device):
+// (float) weights for the sums, double weights for the boundary weight sums,
+// idx = (ii + c) + (jj + c) * kw, and the interior weight sum in the
+// reference's order (full_weight, solvers.cpp)
+struct DemonsTable {
+    const float *kf = nullptr;
+    const double *kd = nullptr;
+    double wfull = 0.0;
+};
+// Thirion's Demons (batch_demons_kernels.hip): the pair's whole loop of
+// DemonsThirions::get_update, staged through the pair's slices of W, corr and
+// mid with a barrier after each stage
+struct DemonsLoopArgs {
+    float2 *u0, *u1;      // the iterate's two buffers; iteration t reads u[t & 1]
+    const float *Iref;
+    long sref;            // Iref's pair stride, 0 for a shared reference
+    const float *Iaux;    // Imov warped by the level's motion
+    float *W;             // scratch: Iaux warped by the iterate
+    float2 *corr, *mid;   // scratch: the correction; the motion before the last smoothing
+    long stride;
+    int dx, dy, P, niter;
+    float sigma_isq, sigma_xsq;  // Demons.cpp:48-49
+    DemonsTable fluid, diff;
+    int kw;
+    int mode;             // 0 Composition, 1 Addition, 2 neither (launch_demons_update's)
+    unsigned *status;
+    int *iters;
+    int nloops, loop;
+    float *errs;
+    int maxn;
+};
+// conv as launch_hs_loop's
+void launch_demons_loop(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st);
 
 void launch_d2f(const double *in, int npairs, int dimx, int dimy, float *out, long so, int P,
                 hipStream_t st);
@@ -117,6 +152,9 @@ struct BLevel {
     long stride = 0;
     BField<float> Iref, Imov, Iaux, It;
     BField<float2> motion[2], dI, est[2];
+    // Demons: It holds the image warped by the iterate and dI the correction;
+    // mid (Demons only) the motion before the sigma_diffusion smoothing
+    BField<float2> mid;
     int mcur = 0;
 };
 
@@ -160,9 +198,17 @@ class Batch {
     void downsample_levels(int which, int npairs);
     void images_in_place(bool shared_ref);
     size_t chunk_pairs() const;
+    DemonsLoopArgs demons_args(BLevel &L, int s, int loop) const;
     int B_, dimx_, dimy_, nscales_, nrefine_, nloops_ = 0;
     std::vector<int> niter_, ldx_, ldy_;
-    float alpha_;
+    int reg_;
+    std::vector<float> params_;
+    float alpha_ = 0.0f;
+    // Demons: the two Gaussian tables (sigma_fluid, then sigma_diffusion), as
+    // Registration's DemonsKernels
+    std::vector<double> kfluid_, kdiff_;
+    float *d_kf_ = nullptr;
+    double *d_kd_ = nullptr;
     bool fixed_ = false, shared_ = false, have_images_ = false;
     int device_ = -1, home_ = -1;
     bool ready_ = false;
