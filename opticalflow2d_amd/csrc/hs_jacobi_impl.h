@@ -1003,6 +1003,12 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi3_mid_kernel(
 // registers.  A lane touches only its own words (no barrier, 16-B stride
 // across lanes).  4 slots x 2 words x 16 B x 256 threads = 32 KB per block:
 // four blocks per CU fit the 160 KB.
+// the quad's division-range decision on the bits of sc (see its row step)
+constexpr unsigned kQuadRangeLo = 77u << 24, kQuadRangeSpan = (157u - 77u) << 24;
+__device__ __forceinline__ unsigned quad_range_key(float v) {
+    return (__float_as_uint(v) << 1) - kQuadRangeLo;
+}
+
 template <int WAVES, bool XCD = true, int MINB = 4, int PRIO = 1, bool ALT = true>
 __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
     const float2 *__restrict__ uo, float2 *__restrict__ un, const float2 *__restrict__ dI,
@@ -1096,8 +1102,12 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
         const v2f pr0 = q[0] * g0, pr1 = q[1] * g1;
         const float sc0 = (g.t.x + pr0.x) + pr0.y, sc1 = (g.t.y + pr1.x) + pr1.y;
         Row<2> o;
-        const float mn = fminf(fabsf(sc0), fabsf(sc1)), mx = fmaxf(fabsf(sc0), fabsf(sc1));
-        if (grange && __builtin_amdgcn_ballot_w64(!(mn >= 0x1p-50f && mx < 0x1p30f)) == 0) {
+        // 2^-50 <= |sc| < 2^30 for both px, on the bits: the sign shifted out,
+        // the biased exponent 77 <= e < 157 as one unsigned compare of the
+        // larger key (0, denormals, inf and NaN are outside); integer
+        // instructions, no canonicalising max of a float min / max
+        const unsigned key = max(quad_range_key(sc0), quad_range_key(sc1));
+        if (grange && __builtin_amdgcn_ballot_w64(!(key < kQuadRangeSpan)) == 0) {
             const float2 f0 = div2_unscaled(g0.x * sc0, g0.y * sc0, g.b.x, g.b.z);
             const float2 f1 = div2_unscaled(g1.x * sc1, g1.y * sc1, g.b.y, g.b.w);
             o.v[0] = make_float2(q[0].x - f0.x, q[0].y - f0.y);
@@ -1110,14 +1120,22 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
         return o;
     };
     const bool in1 = x + 1 < dimx;
+    // this wave holds column dimx - 1 of an odd dimx, so one lane's px 1 lies
+    // in the padding: wave-uniform, only that strip selects px 1 out of the norms
+    const bool odd_w = __builtin_amdgcn_ballot_w64(x + 1 == dimx) != 0;
     auto mag = [](float a, float b) { return __builtin_amdgcn_sqrtf(a * a + b * b); };
     auto norms = [&](const Row<2> &nw, const Row<2> &od, float &sd, float &sp) {
         sd += mag(nw.v[0].x - od.v[0].x, nw.v[0].y - od.v[0].y);
         sp += mag(od.v[0].x, od.v[0].y);
         const float d1 = mag(nw.v[1].x - od.v[1].x, nw.v[1].y - od.v[1].y);
         const float p1 = mag(od.v[1].x, od.v[1].y);
-        sd += in1 ? d1 : 0.0f;  // a select, not a product: padding may hold 0/0
-        sp += in1 ? p1 : 0.0f;
+        if (odd_w) {
+            sd += in1 ? d1 : 0.0f;  // a select, not a product: padding may hold 0/0
+            sp += in1 ? p1 : 0.0f;
+        } else {
+            sd += d1;
+            sp += p1;
+        }
     };
     // one band, marched in direction D as jacobi3_body's
     auto march = [&](auto dirc) __attribute__((always_inline)) {
