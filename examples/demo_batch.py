@@ -7,7 +7,11 @@ stopping on its own iteration) and the per-frame iteration counts are printed.
 With --reg 3 the registrations are Thirion's Demons (parameters 1, 0.25, 1.5,
 2.5, kernel width 5, Composition).
 
-    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
+    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3] [--report]
+
+--report adds the deformation analysis of the batch, one call each for all
+frames: how many frames fold and the worst minimum Jacobian, the inverse of
+every frame's motion, and MSE / NCC against frame 0 before and after.
 """
 import argparse
 import os
@@ -29,6 +33,8 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.3)
     ap.add_argument("--reg", type=int, default=0, choices=[0, 3],
                     help="0 Horn-Schunck (alpha), 3 Thirion's Demons")
+    ap.add_argument("--report", action="store_true",
+                    help="print the batch's Jacobian, inverse and quality summary")
     a = ap.parse_args()
     n, B = a.size, a.frames
     ref, _ = S.texture_pair(n, seed=3, sigma=3.0)
@@ -45,6 +51,10 @@ def main():
         iters = b.iterations()
         warped = b.warp(frames)
         info = b.info()
+        if a.report:
+            _, stats = b.jacobian(jac=False)
+            _, inv = b.inverse_motion()
+            quality = b.quality(ref, frames)
     print(f"{B} frames of {n} x {n} against frame 0: {info['launches']} kernel launches, "
           f"loop kernels {info['loop_us']} us")
     print("frame  shift (px)      iterations (coarse, fine)  mean motion (px)    rms before -> after")
@@ -55,6 +65,14 @@ def main():
     for k in range(B):
         print(f"{k + 1:5d}  ({shifts[k, 0]:5.2f}, {shifts[k, 1]:5.2f})  {str(iters[k].tolist()):>24}  "
               f"({mean[k, 0]:5.2f}, {mean[k, 1]:5.2f})     {before[k]:.4f} -> {after[k]:.4f}")
+    if a.report:
+        folded = sum(s["folded"] > 0 for s in stats)
+        print(f"folded pairs {folded} of {B}, worst min Jacobian {min(s['min'] for s in stats):.4f}")
+        print(f"inverse: mean {np.mean([i['iterations'] for i in inv]):.1f} iterations, "
+              f"worst residual {max(i['residual'] for i in inv):.3e} px")
+        mq = {k: np.mean([q[k] for q in quality]) for k in quality[0]}
+        print(f"mean MSE {mq['mse_before']:.3e} -> {mq['mse_after']:.3e}, "
+              f"mean NCC {mq['ncc_before']:.4f} -> {mq['ncc_after']:.4f}")
 
 
 if __name__ == "__main__":

@@ -410,6 +410,38 @@ int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap);
  * level 0: where the iterate lives (0: global memory), threads of a pair's
  * workgroup}; returns the number of values */
 int of2d_batch_info(const of2d_batch *b, int *info, int n);
+/* Deformation analysis of every pair's level-0 motion (of2d_jacobian,
+ * of2d_invert_motion and of2d_quality per pair): one or two kernel launches
+ * whatever nbatch is, one workgroup per pair, every fp64 sum in a fixed order
+ * (two calls give the same bits).  The maps and the inverse are those of the
+ * one-pair entries on that pair alone, bit for bit; a pair's mean, mse and ncc
+ * are fp64 sums in another order than the one-pair kernels' and agree with
+ * them to the sums' rounding.  The motion is zero before the first estimate
+ * and for a pair whose status is OF2D_ERR_RUNTIME: such a pair reports J = 1
+ * everywhere, a zero inverse that converged at its first update, and
+ * after == before; there is no special case for it.  The statistics, info and
+ * quality are small (5, 4 and 4 doubles per pair) and always return to host
+ * memory, so these calls (their _device forms too) wait for the library's
+ * stream.  They leave the stored images and the motion as they are: a later
+ * of2d_batch_estimate gives the bits it would have given without them.
+ * Refused with OF2D_ERR_INVALID_ARGUMENT and a message before any device
+ * work: NULL stats, info or out (of of2d_batch_quality; the others' maps are
+ * optional), NULL Iref or Imov, max_iter < 1, tol not finite or <= 0, and for
+ * the Jacobian and the inverse dimx < 2 or dimy < 2.
+ *
+ * jac: nbatch x [dimx*dimy] (boundary layout) or NULL; stats: nbatch x 5 as
+ * of2d_jacobian's */
+int of2d_batch_jacobian(of2d_batch *b, double *jac, double *stats);
+/* every pair runs the loop of of2d_invert_motion inside the kernel and stops
+ * on its own update (OF2D_INVERT_CHUNK plays no part).  out: nbatch x planar
+ * [dimx*dimy*2] as of2d_batch_get_motion's, or NULL; info: nbatch x 4 as
+ * of2d_invert_motion's */
+int of2d_batch_invert_motion(of2d_batch *b, int max_iter, double tol, double *out, double *info);
+/* Iref (one image with shared_ref, else nbatch) and Imov as
+ * of2d_batch_set_images takes them; out: nbatch x {mse_before, ncc_before,
+ * mse_after, ncc_after} */
+int of2d_batch_quality(of2d_batch *b, const double *Iref, int shared_ref, const double *Imov,
+                       double *out);
 int of2d_batch_destroy(of2d_batch *b);
 /* b == NULL: the message of the last refused of2d_batch_create of this thread */
 const char *of2d_batch_last_error(const of2d_batch *b);
@@ -475,6 +507,17 @@ int of2d_batch_set_images_device(of2d_batch *b, const of2d_darray *Iref, int sha
 int of2d_batch_get_motion_device(of2d_batch *b, const of2d_darray *out, void *stream);
 int of2d_batch_warp_device(of2d_batch *b, const of2d_darray *Imov, const of2d_darray *out,
                            void *stream);
+/* of2d_batch_jacobian, _invert_motion, _quality with the maps, the inverse and
+ * the images as device arrays (jac: pair, x, y, or NULL; out: pair, x, y,
+ * component; Iref, Imov as of2d_batch_set_images_device's).  stats, info and
+ * out of the quality are host memory: the calls wait for the library's stream
+ * after ordering the caller's stream behind their last use of its arrays. */
+int of2d_batch_jacobian_device(of2d_batch *b, const of2d_darray *jac, double *stats,
+                               void *stream);
+int of2d_batch_invert_motion_device(of2d_batch *b, int max_iter, double tol,
+                                    const of2d_darray *out, double *info, void *stream);
+int of2d_batch_quality_device(of2d_batch *b, const of2d_darray *Iref, int shared_ref,
+                              const of2d_darray *Imov, double *out, void *stream);
 
 /* ---- library info ---- */
 const char *of2d_version(void);

@@ -123,6 +123,15 @@ PRODUCT_SIGNATURES = {
     "of2d_batch_set_images_device": (C.c_int, [C.c_void_p, _darr, C.c_int, _darr, C.c_void_p]),
     "of2d_batch_get_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
     "of2d_batch_warp_device": (C.c_int, [C.c_void_p, _darr, _darr, C.c_void_p]),
+    "of2d_batch_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "of2d_batch_invert_motion": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                           C.c_void_p]),
+    "of2d_batch_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "of2d_batch_jacobian_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p, C.c_void_p]),
+    "of2d_batch_invert_motion_device": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _darr,
+                                                  C.c_void_p, C.c_void_p]),
+    "of2d_batch_quality_device": (C.c_int, [C.c_void_p, _darr, C.c_int, _darr, C.c_void_p,
+                                            C.c_void_p]),
     "of2d_version": (C.c_char_p, []),
     "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }
@@ -184,6 +193,11 @@ PRIM_SIGNATURES = {
     "of2d_prim_pack_image": (C.c_int, [_darr, C.c_int, C.c_int, C.c_int, _f32p]),
     "of2d_prim_unpack_image": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
     "of2d_prim_unpack_motion": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
+    "of2d_prim_batch_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _f32p_opt, _f64p]),
+    "of2d_prim_batch_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                         _f32p, _f64p, _f32p_opt]),
+    "of2d_prim_batch_similarity": (C.c_int, [_f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int,
+                                             _f64p]),
 }
 
 SIGNATURES = {**PRODUCT_SIGNATURES, **PRIM_SIGNATURES}  # everything lib() binds

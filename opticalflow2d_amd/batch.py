@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _device, _lib
 from ._lib import check
-from .registration import Regularisation
+from .registration import Regularisation, _invert_args, _invert_info, _jac_stats
 
 #: most pixels a batch image may have (include/of2d.h OF2D_BATCH_MAXPX)
 BATCH_MAXPX = 512 * 512
@@ -152,6 +152,96 @@ class BatchRegistration:
         self._chk(_lib.lib().of2d_batch_warp(self._h, m, out))
         return np.ascontiguousarray(
             out.reshape(self.nbatch, self.dimy, self.dimx).transpose(0, 2, 1))
+
+    # ---- deformation analysis of every pair's motion (of2d_batch_jacobian,
+    # _invert_motion, _quality): one or two launches whatever nbatch is.  The
+    # statistics always come back as host values, so the calls wait for the
+    # device.
+    def jacobian(self, jac=True, out=None):
+        """``(maps, stats)``: the Jacobian determinant map of every pair's
+        motion, ``[nbatch, dimx, dimy]``, and a list of
+        :meth:`ImageRegistration.jacobian`'s ``stats`` dicts.  ``jac=False``:
+        ``(None, stats)``.  ``out`` (a CUDA tensor of the maps' shape, float32
+        or float64, any strides) receives the maps on the device
+        (of2d_batch_jacobian_device) and is returned."""
+        L = _lib.lib()
+        st = np.zeros((self.nbatch, 5), np.float64)
+        maps = None
+        if out is not None:
+            shape = (self.nbatch, self.dimx, self.dimy)
+            out = _device.output(out, shape, None, self._device)
+            a = _device.darray(out, shape, (0, 1, 2), "out")
+            self._chk(L.of2d_batch_jacobian_device(self._h, C.byref(a), st.ctypes.data,
+                                                   _device.stream_of(out)))
+            maps = out
+        elif jac:
+            buf = np.zeros(self.nbatch * self.dimx * self.dimy, np.float64)
+            self._chk(L.of2d_batch_jacobian(self._h, buf.ctypes.data, st.ctypes.data))
+            maps = np.ascontiguousarray(
+                buf.reshape(self.nbatch, self.dimy, self.dimx).transpose(0, 2, 1))
+        else:
+            self._chk(L.of2d_batch_jacobian(self._h, None, st.ctypes.data))
+        return maps, [_jac_stats(s) for s in st]
+
+    def inverse_motion(self, max_iter: int = 50, tol: float = 1e-3, out=None):
+        """``(v, info)``: the inverse of every pair's motion, ``[nbatch, dimx,
+        dimy, 2]``, and a list of :meth:`ImageRegistration.inverse_motion`'s
+        ``info`` dicts; every pair stops on its own update.  ``out`` (a CUDA
+        tensor of that shape) receives the fields on the device
+        (of2d_batch_invert_motion_device) and is returned."""
+        max_iter, tol = _invert_args(max_iter, tol)
+        L = _lib.lib()
+        info = np.zeros((self.nbatch, 4), np.float64)
+        if out is not None:
+            shape = (self.nbatch, self.dimx, self.dimy, 2)
+            out = _device.output(out, shape, None, self._device)
+            a = _device.darray(out, shape, (0, 1, 2, 3), "out")
+            self._chk(L.of2d_batch_invert_motion_device(self._h, max_iter, tol, C.byref(a),
+                                                        info.ctypes.data,
+                                                        _device.stream_of(out)))
+            v = out
+        else:
+            buf = np.zeros(self.nbatch * 2 * self.dimx * self.dimy, np.float64)
+            self._chk(L.of2d_batch_invert_motion(self._h, max_iter, tol, buf.ctypes.data,
+                                                 info.ctypes.data))
+            v = np.ascontiguousarray(
+                buf.reshape(self.nbatch, 2, self.dimy, self.dimx).transpose(0, 3, 2, 1))
+        return v, [_invert_info(i) for i in info]
+
+    def quality(self, Iref, Imov) -> list:
+        """Per pair :meth:`ImageRegistration.quality`'s dict: MSE and zero-mean
+        NCC of ``Iref`` against ``Imov`` and against ``Imov`` warped by the
+        pair's motion.  The images are :meth:`register`'s (``Iref`` one image
+        or a stack); two CUDA tensors are read where they are
+        (of2d_batch_quality_device)."""
+        L = _lib.lib()
+        q = np.zeros((self.nbatch, 4), np.float64)
+        stack = (self.nbatch, self.dimx, self.dimy)
+        if _device.all_cuda(Iref=Iref, Imov=Imov):
+            shared = Iref.dim() == 2
+            if shared:
+                r = _device.darray(Iref, stack[1:], (1, 2), "Iref")
+            elif tuple(Iref.shape) == stack:
+                r = _device.darray(Iref, stack, (0, 1, 2), "Iref")
+            else:
+                raise ValueError(f"Iref is {tuple(Iref.shape)}, expected {stack[1:]} or {stack}")
+            m = _device.darray(Imov, stack, (0, 1, 2), "Imov")
+            self._chk(L.of2d_batch_quality_device(self._h, C.byref(r), int(shared), C.byref(m),
+                                                  q.ctypes.data, _device.stream_of(Imov)))
+        else:
+            r = np.asarray(Iref, dtype=np.float64)
+            shared = r.ndim == 2
+            if shared:
+                if r.shape != stack[1:]:
+                    raise ValueError(f"Iref is {r.shape}, expected {stack[1:]} or {stack}")
+                r = np.ascontiguousarray(r.T).reshape(-1)
+            else:
+                r = self._stack(r, "Iref")
+            m = self._stack(Imov, "Imov")
+            self._chk(L.of2d_batch_quality(self._h, r.ctypes.data, int(shared), m.ctypes.data,
+                                           q.ctypes.data))
+        keys = ("mse_before", "ncc_before", "mse_after", "ncc_after")
+        return [dict(zip(keys, (float(v) for v in row))) for row in q]
 
     def iterations(self) -> np.ndarray:
         """``[nbatch, loops]`` iterations run, loops in execution order

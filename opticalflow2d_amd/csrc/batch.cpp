@@ -69,6 +69,10 @@ Batch::~Batch() { release_device(); }
 void Batch::release_device() {
     lv_.clear();
     if (d_stage_) (void)hipFree(d_stage_);
+    if (d_words_) (void)hipFree(d_words_);
+    d_words_ = nullptr;
+    qref_.release();
+    qref_pairs_ = 0;
     if (d_status_) (void)hipFree(d_status_);
     if (d_iters_) (void)hipFree(d_iters_);
     if (d_errs_) (void)hipFree(d_errs_);
@@ -104,10 +108,7 @@ void Batch::set_option(const std::string &key, double v) {
 }
 
 // pairs per staging round of the boundary copies (64 MiB of doubles at most)
-size_t Batch::chunk_pairs() const {
-    const size_t n0 = (size_t)dimx_ * dimy_;
-    return std::min<size_t>(B_, std::max<size_t>(1, ((size_t)8 << 20) / (2 * n0)));
-}
+size_t Batch::chunk_pairs() const { return stage_chunk_pairs(B_, dimx_, dimy_); }
 
 void Batch::ensure_device() {
     if (ready_) {
@@ -446,6 +447,186 @@ void Batch::warp_device(const DArrayView &in, const DArrayView &out, hipStream_t
                 nullptr, st_);
     launch_unpack_image(L0.It.p, L0.stride, L0.P, B_, dimx_, dimy_, out, st_);
     stream_after(user, st_, ev_io_[1]);
+}
+
+// ------------------------------------------------------------ analysis
+// (of2d_batch.h; the kernels: batch_analysis_kernels.hip.)  Scratch at level 0,
+// free between estimates as warp's: It holds the Jacobian maps or the warped
+// images, Iaux the moving images, est[0] the inverse (estimate() zeroes est[0]
+// before every loop and writes est[1] before reading it, and nothing reads
+// either after an estimate).  The stored images and the motion are only read.
+double *Batch::analysis_words() {
+    if (!d_words_) OF2D_HIP(hipMalloc(&d_words_, sizeof(double) * 5 * (size_t)B_));
+    return d_words_;
+}
+
+void Batch::fetch_words(double *host, int per_pair) {
+    OF2D_HIP(hipMemcpyAsync(host, d_words_, sizeof(double) * per_pair * (size_t)B_,
+                            hipMemcpyDeviceToHost, st_));
+    OF2D_HIP(hipStreamSynchronize(st_));
+}
+
+void Batch::ensure_quality_reference(int npairs) {
+    if (qref_pairs_ >= npairs) return;
+    qref_pairs_ = 0;
+    qref_.alloc(dimx_, dimy_, npairs);
+    OF2D_HIP(hipDeviceSynchronize());  // null-stream memset, as ensure_reference
+    qref_pairs_ = npairs;
+}
+
+void Batch::run_jacobian(bool map) {
+    BLevel &L0 = lv_[0];
+    JacobianArgs a;
+    a.u = L0.motion[L0.mcur].p;
+    a.stride = L0.stride;
+    a.dx = dimx_;
+    a.dy = dimy_;
+    a.P = L0.P;
+    a.jac = map ? L0.It.p : nullptr;
+    a.stats = analysis_words();
+    launch_batch_jacobian(a, B_, st_);
+}
+
+void Batch::jacobian(double *jac, double *stats) {
+    if (const char *why = jacobian_refusal(dimx_, dimy_)) throw std::invalid_argument(why);
+    DeviceScope scope;
+    ensure_device();
+    BLevel &L0 = lv_[0];
+    run_jacobian(jac != nullptr);
+    if (jac)
+        for (const StageRound &r : stage_rounds(B_, stage_pairs_, L0.stride, dimx_, dimy_)) {
+            launch_f2d(L0.It.p + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_, r.nk, st_);
+            OF2D_HIP(hipMemcpyAsync(jac + r.image, d_stage_,
+                                    sizeof(double) * r.nk * (size_t)dimx_ * dimy_,
+                                    hipMemcpyDeviceToHost, st_));
+            OF2D_HIP(hipStreamSynchronize(st_));  // the staging buffer is reused
+        }
+    fetch_words(stats, 5);
+}
+
+void Batch::jacobian_device(const DArrayView *jac, double *stats, hipStream_t user) {
+    if (const char *why = jacobian_refusal(dimx_, dimy_)) throw std::invalid_argument(why);
+    DeviceScope scope;
+    ensure_device();
+    if (jac) check_device_pointer(jac->ptr, home_, "of2d_batch_jacobian_device: jac");
+    BLevel &L0 = lv_[0];
+    if (jac) stream_after(st_, user, ev_io_[0]);
+    run_jacobian(jac != nullptr);
+    if (jac) {
+        launch_unpack_image(L0.It.p, L0.stride, L0.P, B_, dimx_, dimy_, *jac, st_);
+        stream_after(user, st_, ev_io_[1]);
+    }
+    fetch_words(stats, 5);
+}
+
+void Batch::run_invert(int max_iter, double tol) {
+    BLevel &L0 = lv_[0];
+    InvertArgs a;
+    a.u = L0.motion[L0.mcur].p;
+    a.v = L0.est[0].p;
+    a.stride = L0.stride;
+    a.dx = dimx_;
+    a.dy = dimy_;
+    a.P = L0.P;
+    a.max_iter = max_iter;
+    a.tol = (float)tol;
+    a.info = analysis_words();
+    a.residuals = nullptr;
+    launch_batch_invert(a, B_, st_);
+}
+
+void Batch::invert_motion(int max_iter, double tol, double *out, double *info) {
+    if (const char *why = invert_refusal(dimx_, dimy_, max_iter, tol))
+        throw std::invalid_argument(why);
+    DeviceScope scope;
+    ensure_device();
+    BLevel &L0 = lv_[0];
+    run_invert(max_iter, tol);
+    if (out)
+        for (const StageRound &r : stage_rounds(B_, stage_pairs_, L0.stride, dimx_, dimy_)) {
+            launch_motion_to_planar(L0.est[0].p + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_,
+                                    r.nk, st_);
+            OF2D_HIP(hipMemcpyAsync(out + r.motion, d_stage_,
+                                    sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
+                                    hipMemcpyDeviceToHost, st_));
+            OF2D_HIP(hipStreamSynchronize(st_));
+        }
+    fetch_words(info, 4);
+}
+
+void Batch::invert_motion_device(int max_iter, double tol, const DArrayView &out, double *info,
+                                 hipStream_t user) {
+    if (const char *why = invert_refusal(dimx_, dimy_, max_iter, tol))
+        throw std::invalid_argument(why);
+    DeviceScope scope;
+    ensure_device();
+    check_device_pointer(out.ptr, home_, "of2d_batch_invert_motion_device: out");
+    BLevel &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    run_invert(max_iter, tol);
+    launch_unpack_motion(L0.est[0].p, L0.stride, L0.P, B_, dimx_, dimy_, out, st_);
+    stream_after(user, st_, ev_io_[1]);
+    fetch_words(info, 4);
+}
+
+// Iref in qref_ (one image or B), Imov in Iaux: the warp, then {mse, ncc} of
+// (Iref, Imov) and of (Iref, warped) into a pair's four words
+void Batch::run_quality(bool shared_ref) {
+    BLevel &L0 = lv_[0];
+    launch_warp(L0.Iaux.p, L0.motion[L0.mcur].p, L0.It.p, L0.stride, dimx_, dimy_, L0.P, B_,
+                nullptr, st_);
+    SimilarityArgs a;
+    a.a = qref_.p;
+    a.sa = shared_ref ? 0 : L0.stride;
+    a.b = L0.Iaux.p;
+    a.sb = L0.stride;
+    a.dx = dimx_;
+    a.dy = dimy_;
+    a.P = L0.P;
+    a.out = analysis_words();
+    a.so = 4;
+    launch_batch_similarity(a, B_, st_);
+    a.b = L0.It.p;
+    a.out += 2;
+    launch_batch_similarity(a, B_, st_);
+}
+
+void Batch::quality(const double *ref, bool shared_ref, const double *mov, double *out) {
+    DeviceScope scope;
+    ensure_device();
+    ensure_quality_reference(shared_ref ? 1 : B_);
+    BLevel &L0 = lv_[0];
+    for (int which = 0; which < 2; which++) {
+        const double *src = which ? mov : ref;
+        float *dst = which ? L0.Iaux.p : qref_.p;
+        const int npairs = (!which && shared_ref) ? 1 : B_;
+        for (const StageRound &r : stage_rounds(npairs, stage_pairs_, L0.stride, dimx_, dimy_)) {
+            OF2D_HIP(hipMemcpyAsync(d_stage_, src + r.image,
+                                    sizeof(double) * r.nk * (size_t)dimx_ * dimy_,
+                                    hipMemcpyHostToDevice, st_));
+            launch_d2f(d_stage_, r.nk, dimx_, dimy_, dst + r.field, L0.stride, L0.P, st_);
+            OF2D_HIP(hipStreamSynchronize(st_));  // the staging buffer is reused
+        }
+    }
+    run_quality(shared_ref);
+    fetch_words(out, 4);
+}
+
+void Batch::quality_device(const DArrayView &ref, bool shared_ref, const DArrayView &mov,
+                           double *out, hipStream_t user) {
+    DeviceScope scope;
+    ensure_device();
+    check_device_pointer(ref.ptr, home_, "of2d_batch_quality_device: Iref");
+    check_device_pointer(mov.ptr, home_, "of2d_batch_quality_device: Imov");
+    const int nref = shared_ref ? 1 : B_;
+    ensure_quality_reference(nref);
+    BLevel &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_image(ref, nref, dimx_, dimy_, qref_.p, L0.stride, L0.P, st_);
+    launch_pack_image(mov, B_, dimx_, dimy_, L0.Iaux.p, L0.stride, L0.P, st_);
+    stream_after(user, st_, ev_io_[1]);  // the caller's arrays are free again
+    run_quality(shared_ref);
+    fetch_words(out, 4);
 }
 
 std::vector<float> Batch::last_errors(int pair) const {

@@ -179,11 +179,7 @@ int analysis(of2d_ctx *ctx, F &&f) {
     return rc;
 }
 const char *invert_args(int dimx, int dimy, int max_iter, double tol) {
-    if (dimx < 2 || dimy < 2) return "invert: the field needs dimx >= 2 and dimy >= 2";
-    if (max_iter < 1) return "invert: max_iter < 1";
-    if (!std::isfinite(tol) || tol <= 0.0)
-        return "invert: tol must be finite and > 0";
-    return nullptr;
+    return of2d::batch::invert_refusal(dimx, dimy, max_iter, tol);  // batch_plan.h
 }
 }  // namespace
 
@@ -594,6 +590,78 @@ int of2d_batch_warp_device(of2d_batch *b, const of2d_darray *Imov, const of2d_da
                      {{Imov, "Imov", false, e}, {out, "out", true, e}}, [&] {
                          b->b->warp_device(view_of(Imov, e), view_of(out, e),
                                            static_cast<hipStream_t>(stream));
+                     });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ batched analysis
+namespace {
+// a refusal of a batch entry before any device work
+int refuse_batch(of2d_batch *b, const std::string &why) {
+    b->err = why;
+    return OF2D_ERR_INVALID_ARGUMENT;
+}
+}  // namespace
+
+extern "C" {
+
+int of2d_batch_jacobian(of2d_batch *b, double *jac, double *stats) {
+    if (!b) return refuse(nullptr, "of2d_batch_jacobian: b is NULL");
+    if (!stats) return refuse_batch(b, "of2d_batch_jacobian: stats is NULL");
+    return guarded(b->err, [&] { b->b->jacobian(jac, stats); });
+}
+
+int of2d_batch_invert_motion(of2d_batch *b, int max_iter, double tol, double *out, double *info) {
+    if (!b) return refuse(nullptr, "of2d_batch_invert_motion: b is NULL");
+    if (!info) return refuse_batch(b, "of2d_batch_invert_motion: info is NULL");
+    return guarded(b->err, [&] { b->b->invert_motion(max_iter, tol, out, info); });
+}
+
+int of2d_batch_quality(of2d_batch *b, const double *Iref, int shared_ref, const double *Imov,
+                       double *out) {
+    if (!b) return refuse(nullptr, "of2d_batch_quality: b is NULL");
+    if (!Iref || !Imov || !out)
+        return refuse_batch(b, "of2d_batch_quality: Iref, Imov or out is NULL");
+    return guarded(b->err, [&] { b->b->quality(Iref, shared_ref != 0, Imov, out); });
+}
+
+int of2d_batch_jacobian_device(of2d_batch *b, const of2d_darray *jac, double *stats,
+                               void *stream) {
+    if (!b) return refuse(nullptr, "of2d_batch_jacobian_device: b is NULL");
+    if (!stats) return refuse_batch(b, "of2d_batch_jacobian_device: stats is NULL");
+    const Extents e = {{b->b->nbatch(), b->b->dimx(), b->b->dimy(), 0}};
+    auto run = [&] {
+        of2d::DArrayView v;
+        if (jac) v = view_of(jac, e);
+        b->b->jacobian_device(jac ? &v : nullptr, stats, static_cast<hipStream_t>(stream));
+    };
+    if (!jac) return guarded(b->err, run);
+    return device_io(b, "of2d_batch_jacobian_device", {{jac, "jac", true, e}}, run);
+}
+
+int of2d_batch_invert_motion_device(of2d_batch *b, int max_iter, double tol,
+                                    const of2d_darray *out, double *info, void *stream) {
+    if (!b) return refuse(nullptr, "of2d_batch_invert_motion_device: b is NULL");
+    if (!info) return refuse_batch(b, "of2d_batch_invert_motion_device: info is NULL");
+    const Extents e = {{b->b->nbatch(), b->b->dimx(), b->b->dimy(), 2}};
+    return device_io(b, "of2d_batch_invert_motion_device", {{out, "out", true, e}}, [&] {
+        b->b->invert_motion_device(max_iter, tol, view_of(out, e), info,
+                                   static_cast<hipStream_t>(stream));
+    });
+}
+
+int of2d_batch_quality_device(of2d_batch *b, const of2d_darray *Iref, int shared_ref,
+                              const of2d_darray *Imov, double *out, void *stream) {
+    if (!b) return refuse(nullptr, "of2d_batch_quality_device: b is NULL");
+    if (!out) return refuse_batch(b, "of2d_batch_quality_device: out is NULL");
+    const int dx = b->b->dimx(), dy = b->b->dimy(), nb = b->b->nbatch();
+    const Extents er = {{shared_ref ? 0 : nb, dx, dy, 0}}, em = {{nb, dx, dy, 0}};
+    return device_io(b, "of2d_batch_quality_device",
+                     {{Iref, "Iref", false, er}, {Imov, "Imov", false, em}}, [&] {
+                         b->b->quality_device(view_of(Iref, er), shared_ref != 0,
+                                              view_of(Imov, em), out,
+                                              static_cast<hipStream_t>(stream));
                      });
 }
 

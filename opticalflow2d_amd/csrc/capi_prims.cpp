@@ -989,4 +989,73 @@ int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
     });
 }
 
+// ------------------------------------------------------------------ batched analysis kernels
+int of2d_prim_batch_jacobian(const float *u, int B, int dimx, int dimy, float *jac,
+                             double *stats) {
+    if (!u || !stats) return refuse(nullptr, "of2d_prim_batch_jacobian: u or stats is NULL");
+    if (B < 1 || B > of2d::batch::kMaxPairs)
+        return refuse(nullptr, "of2d_prim_batch_jacobian: B outside [1, 65535]");
+    if (const char *why = of2d::batch::jacobian_refusal(dimx, dimy)) return refuse(nullptr, why);
+    return prim(true, [&] {
+        of2d::batch::BField<float2> f;
+        of2d::batch::BField<float> j;
+        upload_pairs(f, u, B, dimx, dimy);
+        if (jac) upload_pairs(j, nullptr, B, dimx, dimy);
+        of2d::DevArray<double> ds;
+        ds.alloc(5 * (size_t)B);
+        const long stride = of2d::batch::pair_stride(dimx, dimy);
+        const int P = of2d::pitch_for(dimx);
+        of2d::batch::launch_batch_jacobian({f.p, stride, dimx, dimy, P, j.p, ds.p}, B, nullptr);
+        for (int k = 0; jac && k < B; k++)
+            download(jac + (size_t)k * dimx * dimy, j.p + k * stride, P, dimx, dimy);
+        fetch(stats, ds.p, 5 * (size_t)B);
+    });
+}
+
+int of2d_prim_batch_invert(const float *u, int B, int dimx, int dimy, int max_iter, double tol,
+                           float *v, double *info, float *residuals) {
+    if (!u || !v || !info) return refuse(nullptr, "of2d_prim_batch_invert: u, v or info is NULL");
+    if (B < 1 || B > of2d::batch::kMaxPairs)
+        return refuse(nullptr, "of2d_prim_batch_invert: B outside [1, 65535]");
+    if (const char *why = of2d::batch::invert_refusal(dimx, dimy, max_iter, tol))
+        return refuse(nullptr, why);
+    return prim(true, [&] {
+        of2d::batch::BField<float2> f, w;
+        upload_pairs(f, u, B, dimx, dimy);
+        upload_pairs(w, nullptr, B, dimx, dimy);
+        of2d::DevArray<double> di;
+        di.alloc(4 * (size_t)B);
+        of2d::DevArray<float> dr;
+        if (residuals) dr.alloc((size_t)B * max_iter);
+        const long stride = of2d::batch::pair_stride(dimx, dimy);
+        const int P = of2d::pitch_for(dimx);
+        of2d::batch::launch_batch_invert(
+            {f.p, w.p, stride, dimx, dimy, P, max_iter, (float)tol, di.p, dr.p}, B, nullptr);
+        for (int k = 0; k < B; k++)
+            download(v + (size_t)k * dimx * dimy * 2, w.p + k * stride, P, dimx, dimy);
+        fetch(info, di.p, 4 * (size_t)B);
+        if (residuals) fetch(residuals, dr.p, (size_t)B * max_iter);
+    });
+}
+
+int of2d_prim_batch_similarity(const float *a, int shared_a, const float *b, int B, int dimx,
+                               int dimy, double *out) {
+    if (!a || !b || !out) return refuse(nullptr, "of2d_prim_batch_similarity: a, b or out is NULL");
+    if (B < 1 || B > of2d::batch::kMaxPairs)
+        return refuse(nullptr, "of2d_prim_batch_similarity: B outside [1, 65535]");
+    if (dimx < 1 || dimy < 1) return refuse(nullptr, "similarity: empty image");
+    return prim(true, [&] {
+        of2d::batch::BField<float> x, y;
+        upload_pairs(x, a, shared_a ? 1 : B, dimx, dimy);
+        upload_pairs(y, b, B, dimx, dimy);
+        of2d::DevArray<double> ds;
+        ds.alloc(2 * (size_t)B);
+        const long stride = of2d::batch::pair_stride(dimx, dimy);
+        of2d::batch::launch_batch_similarity(
+            {x.p, shared_a ? 0 : stride, y.p, stride, dimx, dimy, of2d::pitch_for(dimx), ds.p, 2},
+            B, nullptr);
+        fetch(out, ds.p, 2 * (size_t)B);
+    });
+}
+
 }  // extern "C"

@@ -163,4 +163,37 @@ __device__ __forceinline__ void gradients_px(const float *__restrict__ Iref,
     It[idx] = Ia[idx] - Iref[idx];
 }
 
+// Image::jacobian (src/Image.cpp:189-218): the determinant of id + u at pixel
+// (i, j), (1 + dudx.x)(1 + dudy.y) - dudx.y * dudy.x, with partial_x /
+// partial_y of the motion (gradients.h:9-32: central /2.0f, one-sided on the
+// borders).  dimx, dimy >= 2.  jacobian_kernel (analysis_kernels.hip) evaluates
+// the same expression from its LDS tile.
+__device__ __forceinline__ float jacobian_px(const float2 *__restrict__ u, int i, int j, int dimx,
+                                             int dimy, int P) {
+    const long idx = (long)j * P + i;
+    const float2 m = u[idx];
+    float2 dx, dy;
+    if (i == 0) {
+        const float2 a = u[idx + 1];
+        dx = make_float2(a.x - m.x, a.y - m.y);
+    } else if (i == dimx - 1) {
+        const float2 b = u[idx - 1];
+        dx = make_float2(m.x - b.x, m.y - b.y);
+    } else {
+        const float2 a = u[idx + 1], b = u[idx - 1];
+        dx = make_float2((a.x - b.x) / 2.0f, (a.y - b.y) / 2.0f);
+    }
+    if (j == 0) {
+        const float2 a = u[idx + P];
+        dy = make_float2(a.x - m.x, a.y - m.y);
+    } else if (j == dimy - 1) {
+        const float2 b = u[idx - P];
+        dy = make_float2(m.x - b.x, m.y - b.y);
+    } else {
+        const float2 a = u[idx + P], b = u[idx - P];
+        dy = make_float2((a.x - b.x) / 2.0f, (a.y - b.y) / 2.0f);
+    }
+    return (1.0f + dx.x) * (1.0f + dy.y) - dx.y * dy.x;
+}
+
 }  // namespace of2d

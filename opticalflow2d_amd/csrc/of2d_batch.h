@@ -1,6 +1,7 @@
 // of2d_batch.h — B independent Horn-Schunck or Thirion's Demons registrations
-// of one size in one call (batch.cpp, batch_kernels.hip,
-// batch_demons_kernels.hip).
+// of one size in one call, and the deformation analysis of their motions
+// (batch.cpp, batch_kernels.hip, batch_demons_kernels.hip,
+// batch_analysis_kernels.hip).
 //
 // Layout: the B fields of a pyramid level live in one allocation, pair k at
 // k * stride elements, each laid out exactly as a Field<T> (of2d_host.h): the
@@ -20,6 +21,7 @@
 #include <utility>
 #include <vector>
 
+#include "batch_plan.h"
 #include "of2d_device.h"
 
 namespace of2d {
@@ -116,6 +118,50 @@ void launch_accumulate(const float2 *m_old, const float2 *v0, const float2 *v1, 
 // m, the allocation's base, per pair)
 void launch_zero_failed(float2 *m, long stride, int B, const unsigned *status, hipStream_t st);
 
+// ---- analysis of every pair in one launch (batch_analysis_kernels.hip,
+// DESIGN.md §4.6.2): one workgroup of kLoopThreads per pair, fixed-order fp64
+// sums, no float atomics; two calls on the same input give the same bits.
+// Fields are in the batch layout (stride = pair_stride, pitch P).
+//
+// The Jacobian determinant of id + u per pixel (jacobian_px) and per pair
+// stats[5 * pair ...] = {min, max, mean, count(J <= 0), count(J < 0.5f)};
+// dx, dy >= 2
+struct JacobianArgs {
+    const float2 *u;
+    long stride;
+    int dx, dy, P;
+    float *jac;     // the map, a float field per pair (pixels only are written), or nullptr
+    double *stats;  // [B][5]
+};
+void launch_batch_jacobian(const JacobianArgs &a, int B, hipStream_t st);
+// invert_field's whole loop per pair (of2d_device.h), v_0 = 0 (v need not be
+// zeroed: the first update does not read it): info[4 * pair ...] =
+// {updates applied, m of the last one, out-of-bounds pixels at the last
+// evaluated iterate, converged}; residuals[pair][k] = m_k, 0 beyond the last
+// update.  Every pair stops on its own update.  dx, dy >= 2, max_iter >= 1
+struct InvertArgs {
+    const float2 *u;
+    float2 *v;  // the result, updated in place; not u
+    long stride;
+    int dx, dy, P, max_iter;
+    float tol;
+    double *info;      // [B][4]
+    float *residuals;  // [B][max_iter] or nullptr
+};
+void launch_batch_invert(const InvertArgs &a, int B, hipStream_t st);
+// {mse, ncc} of images a and b of every pair (launch_similarity's definition:
+// ncc is NaN when an image is constant) at out[pair * so], out[pair * so + 1]
+struct SimilarityArgs {
+    const float *a;
+    long sa;  // a's pair stride, 0 for one image shared by every pair
+    const float *b;
+    long sb;
+    int dx, dy, P;
+    double *out;
+    long so;
+};
+void launch_batch_similarity(const SimilarityArgs &a, int B, hipStream_t st);
+
 template <class T>
 struct BField {
     T *base = nullptr;
@@ -176,6 +222,30 @@ class Batch {
                            hipStream_t user);
     void get_motion_device(const DArrayView &out, hipStream_t user);
     void warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user);
+    // ---- analysis of the level-0 motion, per pair (batch_analysis_kernels.hip).
+    // One or two launches whatever nbatch is.  The motion is zero before the
+    // first estimate and for a pair whose status is OF2D_ERR_RUNTIME: such a
+    // pair reports J = 1 everywhere, a zero inverse that converged at its first
+    // update, and after == before, by the kernels' own arithmetic (no special
+    // case).  The statistics, info and quality (5, 4 and 4 doubles per pair)
+    // always return to host memory: every call here synchronises the library's
+    // stream.  No call touches the images set_images stored or the motion: a
+    // later estimate() gives the bits it would have given without them.
+    //
+    // jac (optional): nbatch maps as images; stats: nbatch x 5
+    void jacobian(double *jac, double *stats);
+    // out (optional): nbatch fields as get_motion's; info: nbatch x 4
+    void invert_motion(int max_iter, double tol, double *out, double *info);
+    // ref: one image (shared_ref) or nbatch, mov: nbatch, as set_images takes
+    // them; out: nbatch x {mse_before, ncc_before, mse_after, ncc_after}
+    void quality(const double *ref, bool shared_ref, const double *mov, double *out);
+    // the same with the arrays on the device, ordered with the caller's stream
+    // (jac may be null)
+    void jacobian_device(const DArrayView *jac, double *stats, hipStream_t user);
+    void invert_motion_device(int max_iter, double tol, const DArrayView &out, double *info,
+                              hipStream_t user);
+    void quality_device(const DArrayView &ref, bool shared_ref, const DArrayView &mov, double *out,
+                        hipStream_t user);
     int nbatch() const { return B_; }
     int dimx() const { return dimx_; }
     int dimy() const { return dimy_; }
@@ -198,6 +268,12 @@ class Batch {
     void downsample_levels(int which, int npairs);
     void images_in_place(bool shared_ref);
     size_t chunk_pairs() const;
+    double *analysis_words();
+    void ensure_quality_reference(int npairs);
+    void run_jacobian(bool map);
+    void run_invert(int max_iter, double tol);
+    void run_quality(bool shared_ref);
+    void fetch_words(double *host, int per_pair);
     DemonsLoopArgs demons_args(BLevel &L, int s, int loop) const;
     int B_, dimx_, dimy_, nscales_, nrefine_, nloops_ = 0;
     std::vector<int> niter_, ldx_, ldy_;
@@ -216,6 +292,12 @@ class Batch {
     hipStream_t st_ = nullptr;
     std::vector<BLevel> lv_;
     double *d_stage_ = nullptr;
+    // analysis: 5 doubles per pair (allocated on first use), and quality's
+    // copy of the reference images (qref_pairs_ of them; the stored Iref stays
+    // as set_images left it)
+    double *d_words_ = nullptr;
+    BField<float> qref_;
+    int qref_pairs_ = 0;
     size_t stage_pairs_ = 0;
     unsigned *d_status_ = nullptr;
     int *d_iters_ = nullptr;

@@ -229,6 +229,20 @@ int of2d_prim_unpack_image(const float *in_host, int npairs, int dimx, int dimy,
 int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
                             const of2d_darray *out);
 
+/* ---- batched analysis kernels (batch_analysis_kernels.hip), one launch each ----
+ * Dense host stacks of B pairs: u, v float [B][dimy][dimx][2], images and jac
+ * float [B][dimy][dimx].  stats: B x 5, info: B x 4 (of2d_jacobian's and
+ * of2d_invert_motion's per pair); jac and residuals (float [B][max_iter]) may
+ * be NULL; a: one image with shared_a, else B; out: B x {mse, ncc}.  Refusals
+ * as for of2d_field_jacobian / _invert / of2d_image_similarity, and B < 1 or
+ * > 65535. */
+int of2d_prim_batch_jacobian(const float *u, int B, int dimx, int dimy, float *jac,
+                             double *stats);
+int of2d_prim_batch_invert(const float *u, int B, int dimx, int dimy, int max_iter, double tol,
+                           float *v, double *info, float *residuals);
+int of2d_prim_batch_similarity(const float *a, int shared_a, const float *b, int B, int dimx,
+                               int dimy, double *out);
+
 #ifdef __cplusplus
 }
 #endif

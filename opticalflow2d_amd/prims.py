@@ -284,6 +284,51 @@ class prim:
         cls._call("of2d_prim_unpack_motion", m, npairs, dimx, dimy, C.byref(o))
         return out
 
+    # The batched analysis kernels (batch_analysis_kernels.hip), one launch
+    # each on stacks with a leading pair axis: u ``[B, dimy, dimx, 2]``, images
+    # ``[B, dimy, dimx]``.
+    @classmethod
+    def batch_jacobian(cls, u, jac=True):
+        """``(maps [B, dimy, dimx] or None, stats [B, 5])``."""
+        u = cls._f(u)
+        if u.ndim != 4 or u.shape[3] != 2:
+            raise ValueError(f"a stack of motion fields is [B, dimy, dimx, 2], got {u.shape}")
+        B, dimy, dimx, _ = u.shape
+        out = np.zeros((B, dimy, dimx), np.float32) if jac else None
+        st = np.zeros((B, 5), np.float64)
+        cls._call("of2d_prim_batch_jacobian", u, B, dimx, dimy, out, st)
+        return out, st
+
+    @classmethod
+    def batch_invert(cls, u, max_iter=50, tol=1e-3, residuals=True):
+        """``(v [B, dimy, dimx, 2], info [B, 4], residuals [B, max_iter] or None)``."""
+        u = cls._f(u)
+        if u.ndim != 4 or u.shape[3] != 2:
+            raise ValueError(f"a stack of motion fields is [B, dimy, dimx, 2], got {u.shape}")
+        B, dimy, dimx, _ = u.shape
+        v = np.zeros_like(u)
+        info = np.zeros((B, 4), np.float64)
+        res = np.zeros((B, max(int(max_iter), 1)), np.float32) if residuals else None
+        cls._call("of2d_prim_batch_invert", u, B, dimx, dimy, int(max_iter), float(tol), v, info,
+                  res)
+        return v, info, res
+
+    @classmethod
+    def batch_similarity(cls, a, b):
+        """``[B, 2]`` = (mse, ncc) per pair; ``a`` is ``[B, dimy, dimx]`` or one
+        ``[dimy, dimx]`` image shared by every pair."""
+        b = cls._f(b)
+        if b.ndim != 3:
+            raise ValueError(f"a stack of images is [B, dimy, dimx], got {b.shape}")
+        a = cls._f(a)
+        shared = a.ndim == 2
+        if a.shape != (b.shape[1:] if shared else b.shape):
+            raise ValueError(f"a is {a.shape}, expected {b.shape[1:]} or {b.shape}")
+        B, dimy, dimx = b.shape
+        out = np.zeros((B, 2), np.float64)
+        cls._call("of2d_prim_batch_similarity", a, int(shared), b, B, dimx, dimy, out)
+        return out
+
     # Curvature, one call each (csrc/of2d_prims.h).  curv_rhs and
     # curv_construct take fields in the layout above; curv_eigen and curv_dct2d
     # speak ``[dimx, dimy]`` arrays as :func:`dct2d` does.
