@@ -411,7 +411,11 @@ __global__ __launch_bounds__(64 * WAVES) void jacobi2_kernel(
             q.y = (((l.y + r.y) + m.v[k].y) + p.v[k].y) / 4.0f;
             const int xi = x + k;
             q = zero_if(yb || xi == 0 || xi == dimx - 1, q);
-            o.v[k] = update_px(q, g.v[k].x, g.v[k].y, t[k], alphasq, b);
+            // the zero test on image pixels only: the last lane of an odd
+            // width holds padding, whose denominator is 0 when alpha = 0
+            unsigned bk = 0;
+            o.v[k] = update_px(q, g.v[k].x, g.v[k].y, t[k], alphasq, bk);
+            b |= xi < dimx ? bk : 0u;
         }
         return o;
     };
