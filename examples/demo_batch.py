@@ -5,9 +5,12 @@ Every frame is the first one translated a little further; BatchRegistration
 runs the 64 Horn-Schunck registrations together (one workgroup per frame, each
 stopping on its own iteration) and the per-frame iteration counts are printed.
 With --reg 3 the registrations are Thirion's Demons (parameters 1, 0.25, 1.5,
-2.5, kernel width 5, Composition).
+2.5, kernel width 5, Composition); --diffeomorphic with it turns on the batch's
+option of that name: Diffeomorphic Demons, every frame with its own number of
+squarings per iteration.
 
-    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3] [--report]
+    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
+                                  [--diffeomorphic] [--report]
 
 --report adds the deformation analysis of the batch, one call each for all
 frames: how many frames fold and the worst minimum Jacobian, the inverse of
@@ -33,9 +36,13 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.3)
     ap.add_argument("--reg", type=int, default=0, choices=[0, 3],
                     help="0 Horn-Schunck (alpha), 3 Thirion's Demons")
+    ap.add_argument("--diffeomorphic", action="store_true",
+                    help="with --reg 3: Diffeomorphic Demons (the option 'diffeomorphic')")
     ap.add_argument("--report", action="store_true",
                     help="print the batch's Jacobian, inverse and quality summary")
     a = ap.parse_args()
+    if a.diffeomorphic and a.reg != 3:
+        ap.error("--diffeomorphic is an option of --reg 3")
     n, B = a.size, a.frames
     ref, _ = S.texture_pair(n, seed=3, sigma=3.0)
     # frame k: the first frame moved along a slow arc, up to ~2.5 px
@@ -45,7 +52,8 @@ def main():
     frames = np.stack([S.texture_pair(n, seed=3, sigma=3.0, shift=(sx, sy))[1]
                        for sx, sy in shifts])
     params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
-    with BatchRegistration(B, (n, n), [a.niter, a.niter], 1, params, reg=a.reg) as b:
+    options = {"diffeomorphic": 1} if a.diffeomorphic else {}
+    with BatchRegistration(B, (n, n), [a.niter, a.niter], 1, params, reg=a.reg, **options) as b:
         b.register(ref, frames)  # one reference shared by every frame
         motion = b.motion()
         iters = b.iterations()

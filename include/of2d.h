@@ -380,9 +380,26 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * 1 (Diffusion) or != 6 (Demons; the reference's message), a Demons
  * kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
- * Options: "fixed_iters", "device" (before first use); an unknown key is
- * refused ("demons_separable" among them: the batch smooths with the direct
- * convolution only).  Splitting one pair over several workgroups is not offered: with
+ * Options: "fixed_iters", "device" (before first use), "diffeomorphic"; an
+ * unknown key is refused ("demons_separable" among them: the batch smooths
+ * with the direct convolution only).
+ *
+ * "diffeomorphic" (0, the default, or 1): Diffeomorphic Demons.  With 1, a
+ * batch created with reg = OF2D_REG_THIRIONS_DEMONS and accumulation 0
+ * (Composition) is per pair the one-pair OF2D_REG_DIFFEOMORPHIC_DEMONS
+ * registration with parameters [sigma_i, sigma_x, sigma_diffusion,
+ * sigma_fluid, kernel_width]: the smoothed correction goes through
+ * Motion::exp (scaling and squaring) before it is composed with the motion.
+ * Each pair takes its own number of squarings in every iteration, the
+ * reference's; there is no bound on it and no status for one.  The next
+ * of2d_batch_estimate takes the value; 0 is Thirion's Demons bit for bit.
+ * Refused with OF2D_ERR_INVALID_ARGUMENT, the handle still usable and the
+ * option unchanged: on a batch of another method ("diffeomorphic: the batch is
+ * not a Thirion's Demons batch"), with another accumulation ("diffeomorphic:
+ * accumulation must be Composition (0)"), and for a value other than 0 or 1.
+ * (reg = OF2D_REG_DIFFEOMORPHIC_DEMONS itself stays refused at create.)
+ *
+ * Splitting one pair over several workgroups is not offered: with
  * fewer pairs than compute units most of the device idles. */
 typedef struct of2d_batch of2d_batch;
 #define OF2D_BATCH_MAXPX (512 * 512)

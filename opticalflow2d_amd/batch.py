@@ -33,7 +33,14 @@ class BatchRegistration:
     carries the one-pair path's six parameters ``[sigma_i, sigma_x,
     sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
     method is refused.  The other keyword options map to
-    ``of2d_batch_set_option``: ``fixed_iters``, ``device``.
+    ``of2d_batch_set_option``: ``fixed_iters``, ``device``, ``diffeomorphic``.
+    ``diffeomorphic=1`` on a ``reg=3`` batch whose accumulation is 0
+    (Composition) makes every pair the one-pair
+    ``Regularisation.DiffeomorphicDemons`` (4) registration with the first five
+    parameters, bit for bit: the smoothed correction goes through
+    ``Motion::exp`` with the pair's own number of squarings.  It is refused
+    (``InvalidArgument``) on any other batch; ``set_option("diffeomorphic", 0)``
+    returns the next ``register`` to Thirion's Demons.
     With convergence on, every pair stops on its own iteration; the errors are
     those of ``logger_fp64=1`` (fp64 sums in a fixed order).
     """

@@ -103,6 +103,17 @@ void Batch::set_option(const std::string &key, double v) {
     else if (key == "device") {
         if (ready_) throw std::invalid_argument("option 'device' must be set before first use");
         device_ = (int)v;
+    } else if (key == "diffeomorphic") {
+        // DemonsDiffeomorphic::get_update is DemonsThirions' with Composition
+        // plus exp(): an option of such a batch, taken by the next estimate.
+        // A refusal changes nothing.
+        if (reg_ != 3)
+            throw std::invalid_argument("diffeomorphic: the batch is not a Thirion's Demons batch");
+        if ((int)params_[5] != 0)
+            throw std::invalid_argument("diffeomorphic: accumulation must be Composition (0)");
+        if (!(v == 0 || v == 1))  // a NaN too
+            throw std::invalid_argument("diffeomorphic: the value must be 0 or 1");
+        diffeo_ = v == 1;
     } else
         throw std::invalid_argument("unknown option: " + key);
 }
@@ -378,6 +389,7 @@ DemonsLoopArgs Batch::demons_args(BLevel &L, int s, int loop) const {
     // static_cast<MotionAccumulation>((int) regparams[5]), as loop_demons
     const int accum = (int)params_[5];
     a.mode = accum == 0 ? 0 : (accum == 1 ? 1 : 2);
+    a.diffeomorphic = diffeo_ ? 1 : 0;  // set_option admits it with mode 0 only
     a.status = d_status_;
     a.iters = d_iters_;
     a.nloops = nloops_;

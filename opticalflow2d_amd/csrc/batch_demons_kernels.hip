@@ -29,6 +29,20 @@
 //
 // A zero denominator (coord2d.h:95-100) sets the pair's kStatusDivZero; the
 // workgroup learns it at the barrier after stage 2 and leaves the loop.
+//
+// EXP (option "diffeomorphic"): DemonsDiffeomorphic::get_update
+// (DemonsDiffeomorphic.cpp:15-35), which is the Composition update with
+// correspondence->exp() (Motion.cpp:247-275) between stages 3 and 4:
+//   3   mid  = c (*) G(sigma_fluid), and the thread's maximum of Motion::maxabs
+//   3a  nsq  = max(0, (int)ceil(1 + log2(sqrt(block maximum)))), through LDS
+//   3b  mid *= 2^-nsq                                (only if nsq > 0)
+//   3c  nsq squarings u <- u o u, mid -> corr -> mid -> ...
+//   4   mid  = accumulate(u, E), E the buffer that holds the last squaring
+// each followed by a barrier.  nsq is the pair's own, read from LDS after a
+// barrier by every thread, so the branches and the loop it governs are
+// block-uniform; for finite floats it is at most 65.  The expressions are
+// maxabs_partial_kernel's, exp_prepare_kernel's and exp_scale_kernel's
+// (demons_kernels.hip); the squaring is accumulate_px (see there).
 #include "of2d_batch.h"
 
 #include "field_px.h"
@@ -102,7 +116,7 @@ __device__ __forceinline__ bool conv_direct(const float2 *__restrict__ f, const 
     return true;
 }
 
-template <int WAVES, bool CONV, int KW>
+template <int WAVES, bool CONV, int KW, bool EXP>
 __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs a) {
     constexpr int T = 64 * WAVES;
     const long pair = blockIdx.x;
@@ -164,19 +178,97 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
         if (bad) s_bad = 1;
         __syncthreads();
         if (s_bad) break;  // block-uniform: the reference throws here
-        // 3 + 4. the smoothed correction and the motion update
-        for (int idx = tid; idx < npx; idx += T) {
-            const int j = idx / dx, i = idx - j * dx;
-            const long o = (long)j * P + i;
-            float2 c;
-            if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
-            const float2 own = src[o];
-            float2 m = own;  // another enum value: no update
-            if (a.mode == 0)
-                m = accumulate_px(src, c, own, i, j, dx, dy, P);
-            else if (a.mode == 1)
-                m = make_float2(own.x + c.x, own.y + c.y);  // Field::operator+=
-            M[o] = m;
+        if constexpr (EXP) {
+            __shared__ int s_nsq;
+            // 3. the smoothed correction into mid, and Motion::maxabs
+            // (Motion.cpp:51-58: .y squared twice, in double) as
+            // maxabs_partial_kernel has it; the comparison drops a NaN term as
+            // std::max does
+            float mx = 0.0f;
+            for (int idx = tid; idx < npx; idx += T) {
+                const int j = idx / dx, i = idx - j * dx;
+                const long o = (long)j * P + i;
+                float2 c;
+                if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
+                M[o] = c;
+                const double y = (double)c.y;
+                const float s = (float)(y * y + y * y);
+                mx = (mx < s) ? s : mx;
+            }
+            // 3a. the block's maximum (a thread without a pixel brings 0; the
+            // barrier inside is stage 3's) and the squaring count,
+            // exp_prepare_kernel's expressions (Motion.cpp:253-261): a NaN or
+            // out-of-int ceil converts to INT_MIN as on x86-64
+            mx = block_max<WAVES>(mx, wave, lane);
+            if (tid == 0) {
+                const float ma = sqrtf(mx);
+                const float c = ceilf(1.0f + log2f(ma));
+                int nsq = (c == c && c > -2147483648.0f && c < 2147483648.0f) ? (int)c
+                                                                              : (int)0x80000000;
+                s_nsq = nsq < 0 ? 0 : nsq;
+            }
+            __syncthreads();
+            const int nsq = s_nsq;  // block-uniform
+            const float2 *E = M;    // the buffer that holds exp(c)
+            if (nsq > 0) {          // Motion::exp returns early otherwise
+                // 3b. Field<vector2d>::operator*=((float)std::pow(2, -nsq)),
+                // exact; the thread's own pixels, in place
+                const float sc = ldexpf(1.0f, -nsq);
+                for (int idx = tid; idx < npx; idx += T) {
+                    const int j = idx / dx, i = idx - j * dx;
+                    const long o = (long)j * P + i;
+                    float2 v = M[o];
+                    v.x *= sc;
+                    v.y *= sc;
+                    M[o] = v;
+                }
+                __syncthreads();
+                // 3c. u <- u o u (Motion.cpp:268-272: Mtmp = *this;
+                // this->accumulate(*Mtmp)).  accumulate_px(f, f[o], f[o], ...)
+                // is exp_square_kernel's expression: the same products and
+                // sums in the same order with selects for its conditional
+                // terms, c where floor(x + c) is outside the grid or the
+                // weight is 0, and v / w skipped only where w is exactly 1.
+                // A squaring gathers: from one buffer into the other (corr is
+                // free once stage 3 has read it)
+                float2 *from = M, *to = C;
+                for (int q = 0; q < nsq; ++q) {
+                    for (int idx = tid; idx < npx; idx += T) {
+                        const int j = idx / dx, i = idx - j * dx;
+                        const long o = (long)j * P + i;
+                        const float2 c = from[o];
+                        to[o] = accumulate_px(from, c, c, i, j, dx, dy, P);
+                    }
+                    __syncthreads();
+                    float2 *t = from;
+                    from = to;
+                    to = t;
+                }
+                E = from;
+            }
+            // 4. motion->accumulate(*correspondence): E is read at the thread's
+            // own pixel only and the gather is from src, so the write is in
+            // place when E is mid
+            for (int idx = tid; idx < npx; idx += T) {
+                const int j = idx / dx, i = idx - j * dx;
+                const long o = (long)j * P + i;
+                M[o] = accumulate_px(src, E[o], src[o], i, j, dx, dy, P);
+            }
+        } else {
+            // 3 + 4. the smoothed correction and the motion update
+            for (int idx = tid; idx < npx; idx += T) {
+                const int j = idx / dx, i = idx - j * dx;
+                const long o = (long)j * P + i;
+                float2 c;
+                if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
+                const float2 own = src[o];
+                float2 m = own;  // another enum value: no update
+                if (a.mode == 0)
+                    m = accumulate_px(src, c, own, i, j, dx, dy, P);
+                else if (a.mode == 1)
+                    m = make_float2(own.x + c.x, own.y + c.y);  // Field::operator+=
+                M[o] = m;
+            }
         }
         __syncthreads();
         // 5. the smoothed motion into the other buffer, and the Logger's terms
@@ -214,25 +306,32 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
 }  // namespace
 
 namespace {
-template <int KW>
+template <int KW, bool EXP>
 void launch_width(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st) {
     if (conv)
-        hipLaunchKernelGGL((demons_loop_kernel<kLoopWaves, true, KW>), dim3(B),
+        hipLaunchKernelGGL((demons_loop_kernel<kLoopWaves, true, KW, EXP>), dim3(B),
                            dim3(kLoopThreads), 0, st, a);
     else
-        hipLaunchKernelGGL((demons_loop_kernel<kLoopWaves, false, KW>), dim3(B),
+        hipLaunchKernelGGL((demons_loop_kernel<kLoopWaves, false, KW, EXP>), dim3(B),
                            dim3(kLoopThreads), 0, st, a);
+}
+template <bool EXP>
+void launch_exp(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st) {
+    switch (a.kw) {
+        case 3: launch_width<3, EXP>(a, B, conv, st); break;
+        case 5: launch_width<5, EXP>(a, B, conv, st); break;
+        case 7: launch_width<7, EXP>(a, B, conv, st); break;
+        default: launch_width<0, EXP>(a, B, conv, st); break;
+    }
 }
 }  // namespace
 
 // the usual widths are compiled in; every other one takes the runtime loops
 void launch_demons_loop(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st) {
-    switch (a.kw) {
-        case 3: launch_width<3>(a, B, conv, st); break;
-        case 5: launch_width<5>(a, B, conv, st); break;
-        case 7: launch_width<7>(a, B, conv, st); break;
-        default: launch_width<0>(a, B, conv, st); break;
-    }
+    if (a.diffeomorphic)
+        launch_exp<true>(a, B, conv, st);
+    else
+        launch_exp<false>(a, B, conv, st);
     OF2D_HIP(hipGetLastError());
 }
 

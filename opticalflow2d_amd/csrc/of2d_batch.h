@@ -65,7 +65,8 @@ struct DemonsTable {
 };
 // Thirion's Demons (batch_demons_kernels.hip): the pair's whole loop of
 // DemonsThirions::get_update, staged through the pair's slices of W, corr and
-// mid with a barrier after each stage
+// mid with a barrier after each stage; with `diffeomorphic` the loop of
+// DemonsDiffeomorphic::get_update
 struct DemonsLoopArgs {
     float2 *u0, *u1;      // the iterate's two buffers; iteration t reads u[t & 1]
     const float *Iref;
@@ -79,6 +80,9 @@ struct DemonsLoopArgs {
     DemonsTable fluid, diff;
     int kw;
     int mode;             // 0 Composition, 1 Addition, 2 neither (launch_demons_update's)
+    // option "diffeomorphic": Motion::exp of the smoothed correction before the
+    // update (DemonsDiffeomorphic::get_update); mode is 0
+    int diffeomorphic;
     unsigned *status;
     int *iters;
     int nloops, loop;
@@ -286,6 +290,7 @@ class Batch {
     float *d_kf_ = nullptr;
     double *d_kd_ = nullptr;
     bool fixed_ = false, shared_ = false, have_images_ = false;
+    bool diffeo_ = false;  // option "diffeomorphic" (reg 3, Composition only)
     int device_ = -1, home_ = -1;
     bool ready_ = false;
     int ref_pairs_ = 0;  // images Iref holds at every level: 0, 1 (shared) or B

@@ -18,7 +18,16 @@ implies at 72 B per pixel and iteration, every array of a stage counted once
 (warp: u 8, Iaux 4, W out 4; correction: W 4, Iref 4, c out 8; smoothing and
 update: c 8, u 8, mid out 8; smoothing: mid 8, u' out 8).
 
-Writes profiles/batch_demons_bench.log.  Not run by any test.
+--diffeomorphic: the batch runs with the option
+"diffeomorphic" and the sequence is one-pair Diffeomorphic Demons (reg 4), with
+parameters whose squarings are live, [1, 2, 1, 1, kw 5]: |c| reaches 1 and an
+iteration takes 0, 1 or 2 squarings (the count is the pair's own in the batch;
+the one-pair path enqueues its bound every iteration).  The bytes per pixel and
+iteration are then a lower bound: a squaring adds 16 (one field in, one out),
+the scaling 16, and the split of stages 3 and 4 another 16.
+
+Writes profiles/batch_demons_bench.log, or profiles/batch_diffeo_bench.log with
+--diffeomorphic.  Not run by any test.
 """
 import argparse
 import json
@@ -35,6 +44,7 @@ from batch_bench import timed  # noqa: E402
 
 NITER = 100
 PARAMS = [1.0, 0.25, 1.5, 2.5, 5, 0]
+DIFFEO_PARAMS = [1.0, 2.0, 1.0, 1.0, 5, 0]  # the one-pair reg 4 takes the first five
 BYTES_PX_ITER = 72.0
 SHIFTS = [(1.5, -0.75), (0.6, 0.4), (-1.1, 0.3), (0.9, 1.2), (-0.4, -0.8), (1.3, 0.2),
           (0.2, -1.4), (-0.7, 0.9)]
@@ -50,15 +60,16 @@ def pairs(n, count):
     return refs, movs
 
 
-def child_batch(sizes, batches):
+def child_batch(sizes, batches, diffeo=False):
     from opticalflow2d_amd import BatchRegistration, _lib, set_print_sink
     set_print_sink(lambda s: None)
     L = _lib.lib()
     for n in sizes:
         for B in batches:
             refs, movs = pairs(n, B)
-            with BatchRegistration(B, (n, n), [NITER], 0, PARAMS, reg=3, device=0,
-                                   fixed_iters=1) as b:
+            opt = {"diffeomorphic": 1} if diffeo else {}
+            with BatchRegistration(B, (n, n), [NITER], 0, DIFFEO_PARAMS if diffeo else PARAMS,
+                                   reg=3, device=0, fixed_iters=1, **opt) as b:
                 t_reg = timed(lambda: b.register(refs, movs))
                 t_est = timed(lambda: b._chk(L.of2d_batch_estimate(b._h)))
                 it = b.iterations()
@@ -74,7 +85,7 @@ def child_batch(sizes, batches):
             print(json.dumps(row), flush=True)
 
 
-def child_sequence(sizes, batches):
+def child_sequence(sizes, batches, diffeo=False):
     import ctypes
     from opticalflow2d_amd import ImageRegistration, _lib, set_print_sink
     # bind what the baseline library exports
@@ -84,7 +95,8 @@ def child_sequence(sizes, batches):
     set_print_sink(lambda s: None)
     for n in sizes:
         refs, movs = pairs(n, 8)  # pair k of the batch's inputs is pair k % 8
-        with ImageRegistration((n, n), [NITER], 0, 3, PARAMS, device=0, fixed_iters=1) as r:
+        reg, params = (4, DIFFEO_PARAMS[:5]) if diffeo else (3, PARAMS)
+        with ImageRegistration((n, n), [NITER], 0, reg, params, device=0, fixed_iters=1) as r:
             for B in batches:
                 iters = []
 
@@ -105,18 +117,26 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sizes", type=int, nargs="+", default=[128, 256])
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 16, 64, 256])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_demons_bench.log"))
+    ap.add_argument("--diffeomorphic", action="store_true",
+                    help="the batch's option against one-pair Diffeomorphic Demons (reg 4)")
+    ap.add_argument("--out", help="default: profiles/batch_demons_bench.log, or "
+                    "profiles/batch_diffeo_bench.log with --diffeomorphic")
     ap.add_argument("--child", choices=["batch", "sequence"])
     a = ap.parse_args()
+    if not a.out:
+        a.out = os.path.join(ROOT, "profiles", "batch_diffeo_bench.log" if a.diffeomorphic
+                             else "batch_demons_bench.log")
     if a.child == "batch":
-        return child_batch(a.sizes, a.batches)
+        return child_batch(a.sizes, a.batches, a.diffeomorphic)
     if a.child == "sequence":
-        return child_sequence(a.sizes, a.batches)
+        return child_sequence(a.sizes, a.batches, a.diffeomorphic)
     if not a.baseline_lib or not os.path.exists(a.baseline_lib):
         sys.exit("--baseline-lib: the parent commit's libof2d.so is required "
                  "(the baseline is never the code under test)")
     rows = []
     common = ["--sizes", *map(str, a.sizes), "--batches", *map(str, a.batches)]
+    if a.diffeomorphic:
+        common.append("--diffeomorphic")
     for rnd in range(a.rounds):
         for side in ("batch", "sequence"):
             env = dict(os.environ)
@@ -136,11 +156,14 @@ def main():
         return statistics.median(r[key] for r in rows
                                  if r["side"] == side and r["n"] == n and r["B"] == B)
 
-    lines = ["# tools/batch_demons_bench.py: BatchRegistration(reg=3) against ImageRegistration "
-             "(Thirion's Demons) in sequence",
+    what = ("BatchRegistration(reg=3, diffeomorphic=1) against ImageRegistration "
+            "(Diffeomorphic Demons, reg 4)" if a.diffeomorphic else
+            "BatchRegistration(reg=3) against ImageRegistration (Thirion's Demons)")
+    shown = DIFFEO_PARAMS if a.diffeomorphic else PARAMS
+    lines = [f"# tools/batch_demons_bench.py: {what} in sequence",
              f"# rounds {a.rounds}, sides interleaved per round; every figure: the minimum over a "
              "round's repetitions (2 to 20, 0.5 s), then the median of the rounds",
-             f"# niter {NITER} fixed, nscales 0, params {PARAMS}; sequence: B registrations one "
+             f"# niter {NITER} fixed, nscales 0, params {shown}; sequence: B registrations one "
              "after another on one object, baseline library "
              + os.path.basename(os.path.abspath(a.baseline_lib)),
              "# s/pair: register() = upload + estimate; est: estimate alone; ratio: sequence / "
