@@ -138,20 +138,56 @@ __device__ __forceinline__ float2 update_px(float2 q, float gx, float gy, float 
 // more puts the denominator at 2^40 or more, so hs_precheck_kernel's
 // denominator test already implies its upper gradient test.  The bounds stay
 // as they are: the argument above is made for them.
+//
+// The quad (jacobi4_kernel) leaves div_fixup out where it is the identity
+// (div2_quot without div2_fixup).  div_fixup(q, b, a) looks at b and a first: a NaN
+// operand, 0 / 0 and inf / inf give NaN, b == 0 or |a| == inf gives inf,
+// a == 0 or |b| == inf gives 0, each with the sign of a xor b; exponents of a
+// and b so far apart that the quotient leaves the float32 range give inf or
+// 0; every other case returns |q| with the sign of a xor b.  With
+// b in [2^-40, 2^40), so finite, normal and positive, and a in +-[2^-80, 2^50],
+// finite, normal and not 0, whose exponent lies within 90 of b's, only that
+// last case is left.  And q carries the sign already: r > 0, so
+// q0 = a * r has the sign of a and is not 0 (|q0| >= 2^-121), and each
+// refinement fma(e, r, q) adds a correction of a few ulp of q, which cannot
+// reach 0 or change the sign.  So for a != 0 the fix-up returns q itself.
+// The case that is left is a == +-0, which is a gradient of exactly 0 (sc is
+// not 0 on this path).  a = +0 gives q = +0 throughout, which is the fix-up's
+// value.  a = -0 does not: q0 = -0 * r = -0, e = fma(-b, -0, -0) = +0 + -0 =
+// +0, and q = fma(+0, r, -0) = +0, where the fix-up (and the IEEE quotient)
+// gives -0.  It reaches the motion where the stencil mean is -0 too: -0 - -0 =
+// +0 but -0 - +0 = -0.  So the quad skips the fix-up only in row steps of a
+// gradient row none of whose lanes holds a component +-0, a decision taken once
+// per row where the row is completed (the row's z word), and keeps it in all
+// others.  A gradient of inf or NaN never comes this way: it makes its lane's
+// sc = (It + q.x * gx) + q.y * gy inf or NaN, and the step takes the IEEE
+// sequence.  Held to the oracle's bits by tests/test_gpu_hs_quad_fixup.py: no
+// zero gradient, one zero (+0 and -0) beside It of either sign on an owned, a halo and a
+// padding-side lane, zero rows at every march position, and a at both ends of
+// its range.  (That file cannot see the sign of a zero of the iterate, which
+// the composed motion does not keep: a -0 numerator is covered by this
+// argument, not by a test that fails without the row's word.)
 __device__ __forceinline__ float recip_refined(float b) {
     const float r0 = __builtin_amdgcn_rcpf(b);
     return __builtin_fmaf(__builtin_fmaf(-b, r0, 1.0f), r0, r0);
 }
-// (ax / b, ay / b) for b with refined reciprocal r, both components packed
-__device__ __forceinline__ float2 div2_unscaled(float ax, float ay, float b, float r) {
+// (ax / b, ay / b) for b with refined reciprocal r, both components packed:
+// the refined quotients (div2_quot) and their fix-up (div2_fixup)
+__device__ __forceinline__ float2 div2_quot(float ax, float ay, float b, float r) {
     const v2f a = {ax, ay}, nb = {-b, -b}, rr = {r, r};
     v2f q = a * rr;
     v2f e = __builtin_elementwise_fma(nb, q, a);
     q = __builtin_elementwise_fma(e, rr, q);
     e = __builtin_elementwise_fma(nb, q, a);
     q = __builtin_elementwise_fma(e, rr, q);
+    return make_float2(q.x, q.y);
+}
+__device__ __forceinline__ float2 div2_fixup(float2 q, float ax, float ay, float b) {
     return make_float2(__builtin_amdgcn_div_fixupf(q.x, b, ax),
                        __builtin_amdgcn_div_fixupf(q.y, b, ay));
+}
+__device__ __forceinline__ float2 div2_unscaled(float ax, float ay, float b, float r) {
+    return div2_fixup(div2_quot(ax, ay, b, r), ax, ay, b);
 }
 // frexp exponent of v within [lo, hi] (0, inf and NaN have exponent 0)
 template <int LO, int HI>
@@ -1043,10 +1079,14 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
     // a gradient row in use, as the two 16-B words that are parked: a = the
     // gradients of the lane's two px (gx0, gy0, gx1, gy1), b = (den0, den1, rcp0,
     // rcp1); and It.  (Vector values, not arrays: an array member the optimiser
-    // fails to split keeps the row in scratch.)
+    // fails to split keeps the row in scratch.)  z: 0 when no gradient component
+    // of any lane of the wave's row is +-0 (wave-uniform), so that the row's
+    // steps may leave the division's fix-up out (recip_refined's comment); it
+    // travels with It as scalar state, not through the park.
     struct G {
         v4f a, b;
         float2 t;
+        unsigned z;
     };
     const bool grange = *range_flag == 0;
     // a gradient row is loaded raw (dI, It) and completed with the shared
@@ -1065,7 +1105,21 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
     auto fin = [&](const GR &r) {
         const float den0 = (alphasq + r.g.x * r.g.x) + r.g.y * r.g.y;
         const float den1 = (alphasq + r.g.z * r.g.z) + r.g.w * r.g.w;
-        return G{r.g, v4f{den0, den1, recip_refined(den0), recip_refined(den1)}, r.t};
+        // z != 0: a gradient component of some lane is +-0, halo lanes and
+        // padding included (they run the stencil step too).  The smallest of
+        // the four magnitudes has the bits of +0 exactly when one of them is
+        // +-0: the minimum instructions keep denormals (the kernel's float
+        // mode) and return the other operand for a NaN.  Written out, because
+        // fminf() brings a canonicalising v_max per operand, and four compares
+        // ORed as lane masks push the kernel into SGPR spills: 3 VALU
+        // instructions per row, the compare's lane mask taken as it is (uicmp,
+        // 32 = equal) and folded into one scalar word.
+        float zm;
+        asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(zm) : "v"(r.g.x), "v"(r.g.y), "v"(r.g.z));
+        asm("v_min_f32 %0, |%1|, |%2|" : "=v"(zm) : "v"(zm), "v"(r.g.w));
+        const unsigned long long zb = __builtin_amdgcn_uicmp(__float_as_uint(zm), 0u, 32);
+        return G{r.g, v4f{den0, den1, recip_refined(den0), recip_refined(den1)}, r.t,
+                 (unsigned)zb | (unsigned)(zb >> 32)};
     };
     // the lane's own words of slot `slot` (volatile: every put and get is a DS
     // instruction in program order, none forwarded through registers)
@@ -1075,9 +1129,9 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
         pk[(2 * slot) * 64 * WAVES] = g.a;
         pk[(2 * slot + 1) * 64 * WAVES] = g.b;
     };
-    auto get = [&](int slot, float2 t) {
+    auto get = [&](int slot, float2 t, unsigned z) {
         const v4f a = pk[(2 * slot) * 64 * WAVES], b = pk[(2 * slot + 1) * 64 * WAVES];
-        return G{a, b, t};
+        return G{a, b, t, z};
     };
     const bool xedge_w = __builtin_amdgcn_ballot_w64(x == 0 || x == dimx - 1 || x + 1 == 0 ||
                                                      x + 1 == dimx - 1) != 0;
@@ -1112,8 +1166,15 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
         // instructions, no canonicalising max of a float min / max
         const unsigned key = max(quad_range_key(sc0), quad_range_key(sc1));
         if (grange && __builtin_amdgcn_ballot_w64(!(key < kQuadRangeSpan)) == 0) {
-            const float2 f0 = div2_unscaled(g0.x * sc0, g0.y * sc0, g.b.x, g.b.z);
-            const float2 f1 = div2_unscaled(g1.x * sc1, g1.y * sc1, g.b.y, g.b.w);
+            const float ax0 = g0.x * sc0, ay0 = g0.y * sc0, ax1 = g1.x * sc1, ay1 = g1.y * sc1;
+            float2 f0 = div2_quot(ax0, ay0, g.b.x, g.b.z);
+            float2 f1 = div2_quot(ax1, ay1, g.b.y, g.b.w);
+            // the fix-up only where a numerator of the row may be +-0; the two
+            // fast paths share the quotients and the subtraction
+            if (__builtin_expect(g.z != 0, 0)) {
+                f0 = div2_fixup(f0, ax0, ay0, g.b.x);
+                f1 = div2_fixup(f1, ax1, ay1, g.b.y);
+            }
             o.v[0] = make_float2(q[0].x - f0.x, q[0].y - f0.y);
             o.v[1] = make_float2(q[1].x - f1.x, q[1].y - f1.y);
         } else {
@@ -1154,6 +1215,7 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
         Row<2> wj, wj1;       // u2 at sp, sp+1
         Row<2> xm1, xj;       // u3 at sp-1, sp
         float2 tj, tj1, tj2;  // It at sp .. sp+2 (the rest of those rows: slots sp .. sp+2 & 3)
+        unsigned zj, zj1, zj2;  // and their zero words (G::z), scalar
         {
             // halo rows first, so that their inputs die before the band's rows
             // are loaded: u1 at -3..-1, u2 at -2..-1, then the rows the march keeps
@@ -1168,12 +1230,14 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
             const G gj = fin(ldgr(J(0)));
             put(0, gj);
             tj = gj.t;
+            zj = gj.z;
             const Row<2> vj = S(0, a3, uj, uj1, gj);
             const Row<2> qm1 = S(-1, pm2, pm1, vj, gm1);
             uj2 = ldu(J(2));
             const G gj1 = fin(ldgr(J(1)));
             put(1, gj1);
             tj1 = gj1.t;
+            zj1 = gj1.z;
             vj1 = S(1, uj, uj1, uj2, gj1);
             wj = S(0, pm1, vj, vj1, gj);
             xm1 = S(-1, qm2, qm1, wj, gm1);
@@ -1181,6 +1245,7 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
             const G gj2 = fin(ldgr(J(2)));
             put(2, gj2);
             tj2 = gj2.t;
+            zj2 = gj2.z;
             vj2 = S(2, uj1, uj2, uj3, gj2);
             wj1 = S(1, vj, vj1, vj2, gj1);
             xj = S(0, qm1, wj, wj1, gj);
@@ -1207,11 +1272,11 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
                 nu = ldu(J(sp + 5));
                 ng = ldgr(J(sp + 4));
             }
-            const G gj2 = get((slot + 2) & 3, tj2);
+            const G gj2 = get((slot + 2) & 3, tj2, zj2);
             const Row<2> vj3 = S(sp + 3, uj2, uj3, a4, gj3);  // u1
-            const G gj1 = get((slot + 1) & 3, tj1);
+            const G gj1 = get((slot + 1) & 3, tj1, zj1);
             const Row<2> wj2 = S(sp + 2, vj1, vj2, vj3, gj2);  // u2
-            const G gj = get(slot, tj);
+            const G gj = get(slot, tj, zj);
             const Row<2> xj1 = S(sp + 1, wj, wj1, wj2, gj1);  // u3
             const Row<2> z = S(sp, xm1, xj, xj1, gj);         // u4
             if (own) {
@@ -1237,6 +1302,9 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
             tj = tj1;
             tj1 = tj2;
             tj2 = gj3.t;
+            zj = zj1;
+            zj1 = zj2;
+            zj2 = gj3.z;
         };
         int sp = 0;
         for (; sp + 4 < n; sp += 4) {
