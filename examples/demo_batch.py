@@ -10,11 +10,18 @@ option of that name: Diffeomorphic Demons, every frame with its own number of
 squarings per iteration.
 
     python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
-                                  [--diffeomorphic] [--report]
+                                  [--diffeomorphic] [--report] [--track T]
 
 --report adds the deformation analysis of the batch, one call each for all
 frames: how many frames fold and the worst minimum Jacobian, the inverse of
 every frame's motion, and MSE / NCC against frame 0 before and after.
+
+--track T is another workload: T time frames of --frames slices each
+(synthetic.cine_series: every slice's displacement grows a little from frame to
+frame), registered frame after frame on one batch with warm_start=1, so that
+frame t starts from frame t-1's motion, against a second batch that starts
+every frame from zero.  It prints the mean iterations per pair of each frame,
+warm against cold.
 """
 import argparse
 import os
@@ -26,6 +33,32 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from opticalflow2d_amd import BatchRegistration  # noqa: E402
 from opticalflow2d_amd import synthetic as S  # noqa: E402
+
+
+def track(a):
+    """T frames of B slices, frame after frame: warm_start=1 against the default."""
+    n, B, T = a.size, a.frames, a.track
+    refs, frames, shifts = S.cine_series(n, B, T)
+    params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
+    options = {"diffeomorphic": 1} if a.diffeomorphic else {}
+    rows = []
+    with BatchRegistration(B, (n, n), [a.niter], 0, params, reg=a.reg, warm_start=1,
+                           **options) as warm, \
+            BatchRegistration(B, (n, n), [a.niter], 0, params, reg=a.reg, **options) as cold:
+        for t in range(T):
+            warm.register(refs, frames[t])
+            cold.register(refs, frames[t])
+            inner = (slice(None), slice(8, n - 8), slice(8, n - 8))
+            rms = [np.sqrt(((b.warp(frames[t]) - refs) ** 2)[inner].mean()) for b in (warm, cold)]
+            rows.append((np.abs(shifts[t]).max(), warm.iterations().mean(),
+                         cold.iterations().mean(), rms[0], rms[1]))
+    print(f"{T} frames of {B} slices of {n} x {n}, frame t from frame t-1's motion "
+          f"(warm_start=1) against every frame from zero")
+    print("frame  max shift (px)  mean iterations per pair: warm    cold   rms after: warm    cold")
+    for t, (sh, wi, ci, wr, cr) in enumerate(rows):
+        print(f"{t + 1:5d}  {sh:14.2f}  {wi:30.1f}  {ci:6.1f}  {wr:16.4f}  {cr:.4f}")
+    print(f"mean iterations per pair and frame: warm {np.mean([r[1] for r in rows]):.1f}, "
+          f"cold {np.mean([r[2] for r in rows]):.1f}")
 
 
 def main():
@@ -40,9 +73,13 @@ def main():
                     help="with --reg 3: Diffeomorphic Demons (the option 'diffeomorphic')")
     ap.add_argument("--report", action="store_true",
                     help="print the batch's Jacobian, inverse and quality summary")
+    ap.add_argument("--track", type=int, default=0, metavar="T",
+                    help="T time frames of --frames slices, frame after frame with warm_start=1")
     a = ap.parse_args()
     if a.diffeomorphic and a.reg != 3:
         ap.error("--diffeomorphic is an option of --reg 3")
+    if a.track:
+        return track(a)
     n, B = a.size, a.frames
     ref, _ = S.texture_pair(n, seed=3, sigma=3.0)
     # frame k: the first frame moved along a slow arc, up to ~2.5 px

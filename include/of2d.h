@@ -77,6 +77,23 @@ int of2d_set_images(of2d_ctx *ctx, const double *Iref, const double *Imov);
 int of2d_estimate(of2d_ctx *ctx);
 /* get-motion branch (:105-117): out is double [dimx*dimy*2], planar */
 int of2d_get_motion(of2d_ctx *ctx, double *out);
+/* A motion from outside (not in the reference): a prior, another tool's field,
+ * a coarser run's result.  motion is double [dimx*dimy*2], planar as
+ * of2d_get_motion writes it; every value is cast to float and stored as given
+ * (non-finite values are not looked for: the sampling kernels' behaviour for
+ * them applies downstream).  It replaces the level-0 motion, so
+ * of2d_get_motion, of2d_warp and the analysis entries see it at once, and,
+ * when nscales >= 1, the motion of level nscales by Motion::downSample of it.
+ * An estimate never resets the motion (ImageRegistration.cpp:133-156: a second
+ * of2d_estimate continues from the first), so the next of2d_estimate starts
+ * from the supplied field at every level: level nscales from its own motion,
+ * the levels between from Motion::downSample of level 0, and level 0 itself
+ * is overwritten by the upsample when nscales >= 1.  No images are needed.
+ * Every regularisation takes it. */
+int of2d_set_motion(of2d_ctx *ctx, const double *motion);
+/* every level's motion back to zero (and Fluid's velocity, which also
+ * survives an estimate): the next of2d_estimate gives a new context's bits */
+int of2d_reset_motion(of2d_ctx *ctx);
 /* warp branch (:120-137): out is double [dimx*dimy] */
 int of2d_warp(of2d_ctx *ctx, const double *Imov, double *out);
 /* close branch (:140-147) */
@@ -359,8 +376,8 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * moving image by the iterate and differentiates it in every iteration.)  The pyramid and refine sequence, the per-pixel
  * arithmetic and therefore the motion of every pair are those of of2d_create /
  * of2d_estimate on that pair alone (a new context's first estimate: every
- * of2d_batch_estimate starts from a zero motion field), bit for bit when the
- * pair runs the same number of iterations.
+ * of2d_batch_estimate starts from a zero motion field, unless "warm_start" is
+ * 1), bit for bit when the pair runs the same number of iterations.
  *
  * Convergence (the default; "fixed_iters" 0): each pair stops on its own
  * iteration by the reference's test (error < 0.001f after iteration > 1).  The
@@ -380,7 +397,8 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * 1 (Diffusion) or != 6 (Demons; the reference's message), a Demons
  * kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
- * Options: "fixed_iters", "device" (before first use), "diffeomorphic"; an
+ * Options: "fixed_iters", "device" (before first use), "diffeomorphic",
+ * "warm_start"; an
  * unknown key is refused ("demons_separable" among them: the batch smooths
  * with the direct convolution only).
  *
@@ -399,6 +417,26 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * accumulation must be Composition (0)"), and for a value other than 0 or 1.
  * (reg = OF2D_REG_DIFFEOMORPHIC_DEMONS itself stays refused at create.)
  *
+ * "warm_start" (0, the default, or 1), every method; the next
+ * of2d_batch_estimate takes the value.  With 0 every estimate starts every
+ * pair from zero motion.  With 1 an estimate resets no motion: per pair it is
+ * of2d_estimate on a reused context (ImageRegistration::estimate_motion on a
+ * reused object), bit for bit, with the reference's carry-over rule: level
+ * nscales is never downsampled into and continues from its own motion of the
+ * previous call; the levels between are downsampled from level 0; level 0 is
+ * overwritten by the upsample whenever nscales >= 1.  So with a pyramid only
+ * the coarsest level's motion carries over; to continue from the
+ * full-resolution result at every level, hand it back first:
+ * of2d_batch_get_motion_device then of2d_batch_set_motion_device (below).
+ * A pair that fails (zero denominator) under warm_start has its motion zeroed
+ * at every level, so its next estimate starts as a fresh handle's (the
+ * one-pair context keeps the failed level's motion instead).  The status,
+ * iteration counts and errors are per call either way.  The launches of an
+ * estimate (of2d_batch_info) are max(nscales - 1, 0) + loops * (4, Demons 3)
+ * + nscales + 1; with warm_start the last term, the zeroing of failed pairs,
+ * is nscales + 1, one per level.  A value other than 0 or 1 is refused with
+ * "warm_start: the value must be 0 or 1", the option unchanged.
+ *
  * Splitting one pair over several workgroups is not offered: with
  * fewer pairs than compute units most of the device idles. */
 typedef struct of2d_batch of2d_batch;
@@ -413,6 +451,18 @@ int of2d_batch_set_images(of2d_batch *b, const double *Iref, int shared_ref, con
 int of2d_batch_estimate(of2d_batch *b);
 /* nbatch x planar [dimx*dimy*2], as of2d_get_motion per pair */
 int of2d_batch_get_motion(of2d_batch *b, double *out);
+/* of2d_set_motion per pair: motion is nbatch x planar [dimx*dimy*2], the
+ * layout of2d_batch_get_motion writes (set(get()) is the identity on the
+ * bits).  Level 0's motion, and with nscales >= 1 level nscales's by
+ * Motion::downSample of it.  of2d_batch_get_motion, _warp and the analysis
+ * entries see the field at once, so they also serve a field the batch did not
+ * estimate.  The next of2d_batch_estimate starts from it at every level with
+ * "warm_start" 1 and ignores it with 0.  No images are needed; the status of
+ * the last estimate stays. */
+int of2d_batch_set_motion(of2d_batch *b, const double *motion);
+/* every level's motion back to zero: the next estimate, warm or not, gives a
+ * fresh handle's bits */
+int of2d_batch_reset_motion(of2d_batch *b);
 /* pair k's image (Imov: nbatch images) warped by pair k's motion */
 int of2d_batch_warp(of2d_batch *b, const double *Imov, double *out);
 /* out[nbatch]: OF2D_OK or OF2D_ERR_RUNTIME per pair of the last estimate */
@@ -516,6 +566,13 @@ int of2d_set_images_device(of2d_ctx *ctx, const of2d_darray *Iref, const of2d_da
 int of2d_get_motion_device(of2d_ctx *ctx, const of2d_darray *out, void *stream);
 int of2d_warp_device(of2d_ctx *ctx, const of2d_darray *Imov, const of2d_darray *out,
                      void *stream);
+/* of2d_set_motion / of2d_batch_set_motion from a device array with the axes
+ * (pair,) x, y, component, validated as of2d_get_motion_device's out is (an
+ * input: strides of 0 are allowed).  One launch packs all nbatch fields; the
+ * library's stream waits for `stream` and `stream` waits for the pack, and the
+ * calls wait for their own stream as of2d_set_images_device does. */
+int of2d_set_motion_device(of2d_ctx *ctx, const of2d_darray *motion, void *stream);
+int of2d_batch_set_motion_device(of2d_batch *b, const of2d_darray *motion, void *stream);
 /* of2d_batch_set_images, _get_motion, _warp on device arrays: one launch moves
  * all nbatch pairs, without the host entries' staging rounds.  With shared_ref
  * Iref is one image and its pair stride is ignored. */

@@ -132,6 +132,12 @@ PRODUCT_SIGNATURES = {
                                                   C.c_void_p, C.c_void_p]),
     "of2d_batch_quality_device": (C.c_int, [C.c_void_p, _darr, C.c_int, _darr, C.c_void_p,
                                             C.c_void_p]),
+    "of2d_set_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "of2d_set_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
+    "of2d_reset_motion": (C.c_int, [C.c_void_p]),
+    "of2d_batch_set_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "of2d_batch_set_motion_device": (C.c_int, [C.c_void_p, _darr, C.c_void_p]),
+    "of2d_batch_reset_motion": (C.c_int, [C.c_void_p]),
     "of2d_version": (C.c_char_p, []),
     "of2d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
 }

@@ -33,7 +33,12 @@ class BatchRegistration:
     carries the one-pair path's six parameters ``[sigma_i, sigma_x,
     sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
     method is refused.  The other keyword options map to
-    ``of2d_batch_set_option``: ``fixed_iters``, ``device``, ``diffeomorphic``.
+    ``of2d_batch_set_option``: ``fixed_iters``, ``device``, ``diffeomorphic``,
+    ``warm_start``.  ``warm_start=1`` (every method) makes :meth:`register`
+    continue from the motion the handle holds, as a reused
+    :class:`ImageRegistration` does, bit for bit per pair; see
+    :meth:`set_motion` for a start from outside and for the pyramid's
+    carry-over rule.  The default 0 starts every call from zero.
     ``diffeomorphic=1`` on a ``reg=3`` batch whose accumulation is 0
     (Composition) makes every pair the one-pair
     ``Regularisation.DiffeomorphicDemons`` (4) registration with the first five
@@ -139,6 +144,34 @@ class BatchRegistration:
         self._chk(_lib.lib().of2d_batch_get_motion_device(self._h, C.byref(a),
                                                           _device.stream_of(out)))
         return out
+
+    def set_motion(self, m) -> None:
+        """Replace every pair's motion by ``m``: a numpy array ``[nbatch, dimx,
+        dimy, 2]`` (of2d_batch_set_motion) or a CUDA tensor of that shape,
+        float32 or float64, any strides, read where it is in the order of its
+        device's current stream (of2d_batch_set_motion_device).  Values are
+        cast to float32.  :meth:`motion`, :meth:`warp` and the analysis see
+        the field at once; with ``warm_start=1`` the next :meth:`register`
+        starts from it at every pyramid level, with ``warm_start=0`` it is
+        ignored.  ``b.set_motion(b.motion_device())`` makes a warm estimate
+        with a pyramid continue from the full-resolution result (otherwise
+        only the coarsest level's motion carries over)."""
+        shape = (self.nbatch, self.dimx, self.dimy, 2)
+        if _device.is_cuda(m):
+            a = _device.darray(m, shape, (0, 1, 2, 3), "motion")
+            self._chk(_lib.lib().of2d_batch_set_motion_device(self._h, C.byref(a),
+                                                              _device.stream_of(m)))
+            return
+        m = np.asarray(m, dtype=np.float64)
+        if m.shape != shape:
+            raise ValueError(f"motion is {m.shape}, expected {shape}")
+        buf = np.ascontiguousarray(m.transpose(0, 3, 2, 1))
+        self._chk(_lib.lib().of2d_batch_set_motion(self._h, buf.ctypes.data))
+
+    def reset_motion(self) -> None:
+        """Every pair's motion back to zero at every level: the next
+        :meth:`register`, warm or not, gives a fresh handle's result."""
+        self._chk(_lib.lib().of2d_batch_reset_motion(self._h))
 
     def warp(self, Imov, out=None):
         """Pair k's image warped by pair k's motion, ``[nbatch, dimx, dimy]``.

@@ -114,6 +114,11 @@ void Batch::set_option(const std::string &key, double v) {
         if (!(v == 0 || v == 1))  // a NaN too
             throw std::invalid_argument("diffeomorphic: the value must be 0 or 1");
         diffeo_ = v == 1;
+    } else if (key == "warm_start") {
+        // taken by the next estimate; a refusal changes nothing
+        if (!(v == 0 || v == 1))  // a NaN too
+            throw std::invalid_argument("warm_start: the value must be 0 or 1");
+        warm_ = v == 1;
     } else
         throw std::invalid_argument("unknown option: " + key);
 }
@@ -261,7 +266,11 @@ void Batch::images_in_place(bool shared_ref) {
 }
 
 // ImageRegistration::estimate_motion (:133-156) for every pair, each from a
-// zero motion field (as a new ImageRegistration's first estimate)
+// zero motion field (as a new ImageRegistration's first estimate); with
+// warm_start from the motion every level holds, as a reused ImageRegistration
+// (estimate_motion resets nothing): level nscales continues from its own
+// motion, the levels between are downsampled from level 0, and level 0 is
+// overwritten by the upsample when nscales >= 1
 void Batch::estimate() {
     DeviceScope scope;
     ensure_device();
@@ -272,10 +281,12 @@ void Batch::estimate() {
     launches_ = 0;
     pair_err_.clear();
     OF2D_HIP(hipMemsetAsync(d_status_, 0, sizeof(unsigned) * B_, st_));
-    for (BLevel &L : lv_) {
-        L.mcur = 0;
-        OF2D_HIP(hipMemsetAsync(L.motion[0].base, 0, L.motion[0].bytes(), st_));
-    }
+    const bool warm = warm_;
+    if (!warm)
+        for (BLevel &L : lv_) {
+            L.mcur = 0;
+            OF2D_HIP(hipMemsetAsync(L.motion[0].base, 0, L.motion[0].bytes(), st_));
+        }
     BLevel &L0 = lv_[0];
     int loop = 0;
     for (int s = nscales_; s >= 0; s--) {
@@ -333,9 +344,13 @@ void Batch::estimate() {
             launches_++;
         }
     }
-    // a divide-by-zero pair's motion is left zero
-    launch_zero_failed(L0.motion[L0.mcur].base, L0.stride, B_, d_status_, st_);
-    launches_++;
+    // a divide-by-zero pair's motion is left zero; with warm_start at every
+    // level, so that the pair's next estimate starts as a fresh handle's
+    for (int s = 0; s <= (warm ? nscales_ : 0); s++) {
+        BLevel &L = lv_[s];
+        launch_zero_failed(L.motion[L.mcur].base, L.stride, B_, d_status_, st_);
+        launches_++;
+    }
     OF2D_HIP(hipMemcpyAsync(h_status_.data(), d_status_, sizeof(unsigned) * B_,
                             hipMemcpyDeviceToHost, st_));
     if (nloops_ > 0)
@@ -412,6 +427,57 @@ void Batch::get_motion(double *out) {
                                 hipMemcpyDeviceToHost, st_));
         OF2D_HIP(hipStreamSynchronize(st_));
     }
+}
+
+// get_motion's reverse into level 0's current buffer, through the same
+// staging rounds; then the coarsest level (motion_in_place)
+void Batch::set_motion(const double *in) {
+    DeviceScope scope;
+    ensure_device();
+    BLevel &L0 = lv_[0];
+    for (const StageRound &r : stage_rounds(B_, stage_pairs_, L0.stride, dimx_, dimy_)) {
+        OF2D_HIP(hipMemcpyAsync(d_stage_, in + r.motion,
+                                sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
+                                hipMemcpyHostToDevice, st_));
+        launch_planar_to_motion(d_stage_, r.nk, dimx_, dimy_, L0.motion[L0.mcur].p + r.field,
+                                L0.stride, L0.P, st_);
+        OF2D_HIP(hipStreamSynchronize(st_));  // the staging buffer is reused
+    }
+    motion_in_place();
+}
+
+void Batch::set_motion_device(const DArrayView &in, hipStream_t user) {
+    DeviceScope scope;
+    ensure_device();
+    check_device_pointer(in.ptr, home_, "of2d_batch_set_motion_device: motion");
+    BLevel &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_motion(in, B_, dimx_, dimy_, L0.motion[L0.mcur].p, L0.stride, L0.P, st_);
+    stream_after(user, st_, ev_io_[1]);  // the caller's array is free again
+    motion_in_place();
+}
+
+// Level nscales is the one level a warm estimate neither downsamples into nor
+// overwrites before reading: it takes Motion::downSample of the supplied
+// field, so that the estimate starts from it at every level
+void Batch::motion_in_place() {
+    if (nscales_ >= 1) {
+        BLevel &L0 = lv_[0], &L = lv_[nscales_];
+        launch_downsample_motion(L0.motion[L0.mcur].p, L0.stride, L0.dx, L0.dy, L0.P,
+                                 L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P, B_, nullptr, st_);
+    }
+    OF2D_HIP(hipStreamSynchronize(st_));
+}
+
+// every level as allocate_device left it
+void Batch::reset_motion() {
+    DeviceScope scope;
+    ensure_device();
+    for (BLevel &L : lv_) {
+        L.mcur = 0;
+        for (BField<float2> &m : L.motion) OF2D_HIP(hipMemsetAsync(m.base, 0, m.bytes(), st_));
+    }
+    OF2D_HIP(hipStreamSynchronize(st_));
 }
 
 // pair k's image by pair k's motion (WrapperOpticalFlow2d.cpp:120-137 per pair);

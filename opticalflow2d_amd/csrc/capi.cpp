@@ -111,6 +111,17 @@ int of2d_get_motion(of2d_ctx *ctx, double *out) {
     return guarded(ctx->err, [&] { ctx->reg->get_motion(out); });
 }
 
+int of2d_set_motion(of2d_ctx *ctx, const double *motion) {
+    if (!ctx) return refuse(nullptr, "of2d_set_motion: ctx is NULL");
+    if (!motion) return refuse(ctx, "of2d_set_motion: motion is NULL");
+    return guarded(ctx->err, [&] { ctx->reg->set_motion(motion); });
+}
+
+int of2d_reset_motion(of2d_ctx *ctx) {
+    if (!ctx) return refuse(nullptr, "of2d_reset_motion: ctx is NULL");
+    return guarded(ctx->err, [&] { ctx->reg->reset_motion(); });
+}
+
 int of2d_warp(of2d_ctx *ctx, const double *Imov, double *out) {
     if (!ctx || !Imov || !out) return OF2D_ERR_INVALID_ARGUMENT;
     return guarded(ctx->err, [&] { ctx->reg->warp(Imov, out); });
@@ -421,6 +432,20 @@ int of2d_batch_get_motion(of2d_batch *b, double *out) {
     return guarded(b->err, [&] { b->b->get_motion(out); });
 }
 
+int of2d_batch_set_motion(of2d_batch *b, const double *motion) {
+    if (!b) return refuse(nullptr, "of2d_batch_set_motion: b is NULL");
+    if (!motion) {
+        b->err = "of2d_batch_set_motion: motion is NULL";
+        return OF2D_ERR_INVALID_ARGUMENT;
+    }
+    return guarded(b->err, [&] { b->b->set_motion(motion); });
+}
+
+int of2d_batch_reset_motion(of2d_batch *b) {
+    if (!b) return refuse(nullptr, "of2d_batch_reset_motion: b is NULL");
+    return guarded(b->err, [&] { b->b->reset_motion(); });
+}
+
 int of2d_batch_warp(of2d_batch *b, const double *Imov, double *out) {
     if (!b) return refuse(nullptr, "of2d_batch_warp: b is NULL");
     if (!Imov || !out) {
@@ -551,6 +576,20 @@ int of2d_get_motion_device(of2d_ctx *ctx, const of2d_darray *out, void *stream) 
     const Extents e = {{0, ctx ? ctx->reg->dimx() : 0, ctx ? ctx->reg->dimy() : 0, 2}};
     return device_io(ctx, "of2d_get_motion_device", {{out, "out", true, e}}, [&] {
         ctx->reg->get_motion_device(view_of(out, e), static_cast<hipStream_t>(stream));
+    });
+}
+
+int of2d_set_motion_device(of2d_ctx *ctx, const of2d_darray *motion, void *stream) {
+    const Extents e = {{0, ctx ? ctx->reg->dimx() : 0, ctx ? ctx->reg->dimy() : 0, 2}};
+    return device_io(ctx, "of2d_set_motion_device", {{motion, "motion", false, e}}, [&] {
+        ctx->reg->set_motion_device(view_of(motion, e), static_cast<hipStream_t>(stream));
+    });
+}
+
+int of2d_batch_set_motion_device(of2d_batch *b, const of2d_darray *motion, void *stream) {
+    const Extents e = {{b ? b->b->nbatch() : 0, b ? b->b->dimx() : 0, b ? b->b->dimy() : 0, 2}};
+    return device_io(b, "of2d_batch_set_motion_device", {{motion, "motion", false, e}}, [&] {
+        b->b->set_motion_device(view_of(motion, e), static_cast<hipStream_t>(stream));
     });
 }
 

@@ -9,6 +9,10 @@
 //   unpack motion  pitched float2 fields -> strided float | double with a
 //                  component stride (Motion::copy_motion_to_input's planar
 //                  layout, src/Motion.cpp:23-39, or an interleaved [.., 2])
+//   pack motion    the reverse, (float) of each component: a caller's field
+//                  into the pitched float2 fields (the set_motion entries);
+//                  and the host form's planar double fields from the staging
+//                  buffer (planar_to_motion_kernel)
 //
 // The conversions are exact or a single rounding, so results are bit for bit
 // those of the host boundary (d2f_kernel, f2d_kernel, motion_to_planar_kernel
@@ -73,12 +77,16 @@ template <>
 struct Pair<float> {
     using type = float2;
     static __device__ __forceinline__ float2 make(float2 v) { return v; }
+    static __device__ __forceinline__ float2 narrow(float2 v) { return v; }
 };
 template <>
 struct Pair<double> {
     using type = double2;
     static __device__ __forceinline__ double2 make(float2 v) {
         return make_double2((double)v.x, (double)v.y);
+    }
+    static __device__ __forceinline__ float2 narrow(double2 v) {
+        return make_float2((float)v.x, (float)v.y);
     }
 };
 // both components of a motion vector; VEC2: sc == 1 and p aligned to the pair
@@ -89,6 +97,15 @@ __device__ __forceinline__ void store_motion(T *p, long long sc, float2 v) {
     } else {
         p[0] = (T)v.x;
         p[sc] = (T)v.y;
+    }
+}
+// the same read, each component cast to float
+template <class T, bool VEC2>
+__device__ __forceinline__ float2 load_motion(const T *p, long long sc) {
+    if constexpr (VEC2) {
+        return Pair<T>::narrow(*reinterpret_cast<const typename Pair<T>::type *>(p));
+    } else {
+        return make_float2((float)p[0], (float)p[sc]);
     }
 }
 
@@ -284,6 +301,97 @@ void launch_unpack_motion(const float2 *m, long sm, int P, int npairs, int dimx,
         launch_unpack_motion_t<double>(m, sm, P, npairs, dimx, dimy, out, st);
     else
         launch_unpack_motion_t<float>(m, sm, P, npairs, dimx, dimy, out, st);
+}
+
+// ------------------------------------------------------------ pack motion
+// unpack motion's mirror: only the fields' pixels are written (the ghost
+// j-lines and the pitch's slack keep their zeros)
+template <class T, bool VEC2>
+__global__ __launch_bounds__(kBx *kBy) void pack_motion_rows_kernel(const T *__restrict__ in,
+                                                                    IoStrides s, int dimx,
+                                                                    int dimy,
+                                                                    float2 *__restrict__ m,
+                                                                    long sm, int P) {
+    OF2D_IO_ROWS_PROLOGUE
+    m[k * sm + (long)j * P + i] = load_motion<T, VEC2>(in + (k * s.p + i * s.x + j * s.y), s.c);
+}
+
+template <class T, bool VEC2>
+__global__ __launch_bounds__(kBx *kBy) void pack_motion_tr_kernel(const T *__restrict__ in,
+                                                                  IoStrides s, int dimx, int dimy,
+                                                                  float2 *__restrict__ m, long sm,
+                                                                  int P) {
+    __shared__ float2 tile[kTile][kTileS];  // [x][y]: row writes, column reads (above)
+    OF2D_IO_TILE_PROLOGUE
+    {
+        const int y = y0 + tx;
+        for (int xx = ty; xx < kTile; xx += kBy) {
+            const int x = x0 + xx;
+            if (x < dimx && y < dimy)
+                tile[xx][tx] = load_motion<T, VEC2>(in + (k * s.p + x * s.x + y * s.y), s.c);
+        }
+    }
+    __syncthreads();
+    const int x = x0 + tx;
+    for (int yy = ty; yy < kTile; yy += kBy) {
+        const int y = y0 + yy;
+        if (x < dimx && y < dimy) m[k * sm + (long)y * P + x] = tile[tx][yy];
+    }
+}
+
+namespace {
+template <class T>
+void launch_pack_motion_t(const DArrayView &in, int npairs, int dimx, int dimy, float2 *m, long sm,
+                          int P, hipStream_t st) {
+    const IoStrides s = strides_of(in);
+    const bool rows = rows_pattern(in);
+    const dim3 g = rows ? grid_rows(dimx, dimy, npairs) : grid_tiles(dimx, dimy, npairs);
+    const dim3 b(kBx, kBy);
+    const T *p = static_cast<const T *>(in.ptr);
+    // one load of both components, under launch_unpack_motion_t's conditions
+    const bool vec2 = s.c == 1 && reinterpret_cast<uintptr_t>(p) % (2 * sizeof(T)) == 0 &&
+                      s.p % 2 == 0 && s.x % 2 == 0 && s.y % 2 == 0;
+    if (rows && vec2)
+        hipLaunchKernelGGL((pack_motion_rows_kernel<T, true>), g, b, 0, st, p, s, dimx, dimy, m,
+                           sm, P);
+    else if (rows)
+        hipLaunchKernelGGL((pack_motion_rows_kernel<T, false>), g, b, 0, st, p, s, dimx, dimy, m,
+                           sm, P);
+    else if (vec2)
+        hipLaunchKernelGGL((pack_motion_tr_kernel<T, true>), g, b, 0, st, p, s, dimx, dimy, m, sm,
+                           P);
+    else
+        hipLaunchKernelGGL((pack_motion_tr_kernel<T, false>), g, b, 0, st, p, s, dimx, dimy, m, sm,
+                           P);
+    OF2D_HIP(hipGetLastError());
+}
+}  // namespace
+
+void launch_pack_motion(const DArrayView &in, int npairs, int dimx, int dimy, float2 *m, long sm,
+                        int P, hipStream_t st) {
+    if (in.f64)
+        launch_pack_motion_t<double>(in, npairs, dimx, dimy, m, sm, P, st);
+    else
+        launch_pack_motion_t<float>(in, npairs, dimx, dimy, m, sm, P, st);
+}
+
+// The host form, motion_to_planar_kernel's mirror: npairs planar double fields
+// (x-plane, then y-plane, x fastest: Motion::copy_motion_to_input's layout)
+// from the staging buffer into the pitched float2 fields
+__global__ __launch_bounds__(kBx *kBy) void planar_to_motion_kernel(const double *__restrict__ in,
+                                                                    int dimx, int dimy,
+                                                                    float2 *__restrict__ m,
+                                                                    long sm, int P) {
+    OF2D_IO_ROWS_PROLOGUE
+    const long long n = (long long)dimx * dimy, q = k * 2 * n + (long long)j * dimx + i;
+    m[k * sm + (long)j * P + i] = make_float2((float)in[q], (float)in[q + n]);
+}
+
+void launch_planar_to_motion(const double *in, int npairs, int dimx, int dimy, float2 *m, long sm,
+                             int P, hipStream_t st) {
+    hipLaunchKernelGGL(planar_to_motion_kernel, grid_rows(dimx, dimy, npairs), dim3(kBx, kBy), 0,
+                       st, in, dimx, dimy, m, sm, P);
+    OF2D_HIP(hipGetLastError());
 }
 
 }  // namespace of2d

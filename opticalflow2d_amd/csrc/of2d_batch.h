@@ -226,6 +226,14 @@ class Batch {
                            hipStream_t user);
     void get_motion_device(const DArrayView &out, hipStream_t user);
     void warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user);
+    // ---- a motion from outside (include/of2d.h, of2d_batch_set_motion): into
+    // level 0's current buffer, and as Motion::downSample of it into level
+    // nscales's; no images are needed and the last estimate's status stays.
+    // in: nbatch fields as get_motion writes them
+    void set_motion(const double *in);
+    void set_motion_device(const DArrayView &in, hipStream_t user);
+    // every level's motion <- 0, mcur <- 0: a fresh handle's
+    void reset_motion();
     // ---- analysis of the level-0 motion, per pair (batch_analysis_kernels.hip).
     // One or two launches whatever nbatch is.  The motion is zero before the
     // first estimate and for a pair whose status is OF2D_ERR_RUNTIME: such a
@@ -257,6 +265,9 @@ class Batch {
     const std::vector<unsigned> &status() const { return h_status_; }
     const std::vector<int> &iterations() const { return h_iters_; }
     std::vector<float> last_errors(int pair) const;
+    // launches of an estimate: max(nscales - 1, 0) downsamples + nloops * (4,
+    // Demons 3) + nscales upsamples + 1 zeroing of failed pairs; with
+    // warm_start nscales + 1 zeroings, one per level
     // {launches of the last estimate, loops per pair, levels, loop kernels'
     // device time of the last estimate in microseconds, then per level from 0:
     // iterate placement (0: global memory), threads of the pair's workgroup}
@@ -271,6 +282,7 @@ class Batch {
     void ensure_reference(int npairs);
     void downsample_levels(int which, int npairs);
     void images_in_place(bool shared_ref);
+    void motion_in_place();
     size_t chunk_pairs() const;
     double *analysis_words();
     void ensure_quality_reference(int npairs);
@@ -291,6 +303,7 @@ class Batch {
     double *d_kd_ = nullptr;
     bool fixed_ = false, shared_ = false, have_images_ = false;
     bool diffeo_ = false;  // option "diffeomorphic" (reg 3, Composition only)
+    bool warm_ = false;    // option "warm_start": estimate() resets no motion
     int device_ = -1, home_ = -1;
     bool ready_ = false;
     int ref_pairs_ = 0;  // images Iref holds at every level: 0, 1 (shared) or B

@@ -506,6 +506,12 @@ void launch_unpack_image(const float *in, long si, int P, int npairs, int dimx, 
                          const DArrayView &out, hipStream_t st);
 void launch_unpack_motion(const float2 *m, long sm, int P, int npairs, int dimx, int dimy,
                           const DArrayView &out, hipStream_t st);
+// launch_unpack_motion's mirror, each component cast to float; and the host
+// form: npairs planar double fields (as launch_motion_to_planar writes them)
+void launch_pack_motion(const DArrayView &in, int npairs, int dimx, int dimy, float2 *m, long sm,
+                        int P, hipStream_t st);
+void launch_planar_to_motion(const double *in, int npairs, int dimx, int dimy, float2 *m, long sm,
+                             int P, hipStream_t st);
 // `waiter` behind everything enqueued on `signal` so far
 inline void stream_after(hipStream_t waiter, hipStream_t signal, hipEvent_t ev) {
     OF2D_HIP(hipEventRecord(ev, signal));

@@ -195,6 +195,14 @@ class Registration {
     void set_images_device(const DArrayView &ref, const DArrayView &mov, hipStream_t user);
     void get_motion_device(const DArrayView &out, hipStream_t user);
     void warp_device(const DArrayView &in, const DArrayView &out, hipStream_t user);
+    // A motion from outside (include/of2d.h, of2d_set_motion): into level 0's
+    // motion[mcur], and as Motion::downSample of it into level nscales's; the
+    // next estimate() continues from it as from its own last result.  in:
+    // planar as get_motion's out
+    void set_motion(const double *in);
+    void set_motion_device(const DArrayView &in, hipStream_t user);
+    // every level's motion (and Fluid's velocity) <- 0: a new object's state
+    void reset_motion();
     // Deformation analysis of the level-0 motion, on the device (include/of2d.h
     // of2d_jacobian, of2d_invert_motion, of2d_quality); the motion is only read
     void jacobian(double *jac, double *stats);
@@ -231,6 +239,7 @@ class Registration {
     void ensure_device();
     void downsample_levels(int which);
     void images_in_place();
+    void motion_in_place();
     void estimate_level(int s);
     int loop_hs(Level &L, int niter, float alpha, int &final_buf);
     int loop_demons(Level &L, int niter, int &final_buf);

@@ -909,6 +909,57 @@ void Registration::get_motion(double *out) {
     OF2D_HIP(hipStreamSynchronize(st_));
 }
 
+// A motion from outside (include/of2d.h, of2d_set_motion): get_motion's
+// reverse into level 0's current buffer, then the coarsest level
+void Registration::set_motion(const double *in) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    Level &L0 = lv_[0];
+    OF2D_HIP(hipMemcpyAsync(d_stage_, in, sizeof(double) * 2 * dimx_ * dimy_,
+                            hipMemcpyHostToDevice, st_));
+    launch_planar_to_motion(d_stage_, 1, dimx_, dimy_, L0.cur_motion(), 0, L0.P, st_);
+    motion_in_place();
+}
+
+void Registration::set_motion_device(const DArrayView &in, hipStream_t user) {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    check_device_pointer(in.ptr, home_, "of2d_set_motion_device: motion");
+    Level &L0 = lv_[0];
+    stream_after(st_, user, ev_io_[0]);
+    launch_pack_motion(in, 1, dimx_, dimy_, L0.cur_motion(), 0, L0.P, st_);
+    stream_after(user, st_, ev_io_[1]);  // the caller's array is free again
+    motion_in_place();
+}
+
+// Level nscales is the one level estimate() neither downsamples into nor
+// overwrites before reading (ImageRegistration.cpp:133-156): it takes
+// Motion::downSample of the supplied field, so that the next estimate starts
+// from it at every level
+void Registration::motion_in_place() {
+    if (nscales_ >= 1) {
+        Level &L0 = lv_[0], &L = lv_[nscales_];
+        launch_downsample_motion(L0.cur_motion(), L0.dx, L0.dy, L0.P, L.cur_motion(), L.dx, L.dy,
+                                 L.P, st_);
+    }
+    OF2D_HIP(hipStreamSynchronize(st_));
+}
+
+// Every level as a new object's: the motion, and Fluid's velocity, the one
+// other field that survives an estimate (OpticalFlowFluid's member, vb's v
+// half here: each SOR sweep starts from the last one's result)
+void Registration::reset_motion() {
+    DeviceScope scope;  // the caller's device again on return
+    ensure_device();
+    for (Level &L : lv_) {
+        L.mcur = 0;
+        L.motion[0].zero(st_);
+        L.motion[1].zero(st_);
+        if (reg_ == 5) L.vb.zero(st_);
+    }
+    OF2D_HIP(hipStreamSynchronize(st_));
+}
+
 // WrapperOpticalFlow2d.cpp:120-137: Imov.set_image; Imov.warp2d(motion[0])
 void Registration::warp(const double *in, double *out) {
     DeviceScope scope;  // the caller's device again on return

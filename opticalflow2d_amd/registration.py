@@ -310,6 +310,30 @@ class ImageRegistration:
         self._chk(_lib.lib().of2d_get_motion_device(self._h, C.byref(a), _device.stream_of(out)))
         return out
 
+    def set_motion(self, m) -> None:
+        """Replace the motion by ``m``: a numpy array ``[dimx, dimy, 2]``
+        (of2d_set_motion) or a CUDA tensor of that shape, float32 or float64,
+        any strides (of2d_set_motion_device).  Values are cast to float32.
+        :meth:`motion`, :meth:`warp` and the analysis see it at once, and the
+        next :meth:`estimate` continues from it at every pyramid level, as it
+        continues from its own last result."""
+        shape = (self.dimx, self.dimy, 2)
+        if _device.is_cuda(m):
+            a = _device.darray(m, shape, (1, 2, 3), "motion")
+            self._chk(_lib.lib().of2d_set_motion_device(self._h, C.byref(a),
+                                                        _device.stream_of(m)))
+            return
+        m = np.asarray(m, dtype=np.float64)
+        if m.shape != shape:
+            raise ValueError(f"motion is {m.shape}, expected {shape}")
+        buf = np.ascontiguousarray(m.reshape(-1, order="F"))
+        self._chk(_lib.lib().of2d_set_motion(self._h, buf.ctypes.data))
+
+    def reset_motion(self) -> None:
+        """The motion of every level back to zero (Fluid: the velocity too):
+        the next :meth:`estimate` gives a new object's result."""
+        self._chk(_lib.lib().of2d_reset_motion(self._h))
+
     def warp(self, Imov, out=None):
         """``Imov`` warped by the current motion.  A CUDA tensor gives a CUDA
         tensor of its dtype, or ``out`` (of2d_warp_device)."""

@@ -69,6 +69,26 @@ def texture_pair(n: int = 256, seed: int = 0, sigma: float = 2.0, shift=(1.5, -0
     return a, _bilinear_shift(a, *shift)
 
 
+def cine_series(n: int, nslices: int, nframes: int, seed: int = 3, sigma: float = 3.0,
+                step: float = 0.3, ntextures: int = 8):
+    """A cine stack for the batch's warm start (examples/demo_batch.py --track,
+    tools/batch_warm_bench.py): ``nslices`` reference slices (``ntextures``
+    different `texture_pair` textures, repeated) and ``nframes`` time frames of
+    them, slice k of frame t being its reference displaced by ``step * (t + 1)``
+    px along the slice's own direction: a displacement that grows slowly from
+    frame to frame.  Returns (refs [nslices, n, n], frames [nframes, nslices,
+    n, n], shifts [nframes, nslices, 2])."""
+    tex = [texture_pair(n, seed=seed + q, sigma=sigma, shift=(0.0, 0.0))[0]
+           for q in range(min(ntextures, nslices))]
+    ang = 2.0 * np.pi * (np.arange(nslices) * 0.381966)  # golden-angle directions
+    shifts = np.stack([step * (t + 1) * np.stack([np.cos(ang), np.sin(ang)], axis=1)
+                       for t in range(nframes)])
+    refs = np.stack([tex[k % len(tex)] for k in range(nslices)])
+    frames = np.stack([np.stack([_bilinear_shift(refs[k], *shifts[t, k])
+                                 for k in range(nslices)]) for t in range(nframes)])
+    return refs, frames, shifts
+
+
 def shifted_disk(n: int = 256, shift=(4, 2), radius: float | None = None):
     """Config 4 (Fluid): a sharp-edged disk of diameter n/2 shifted by (4, 2) px;
     Fluid needs strong edges (SURVEY.md §7 'Synthetic inputs')."""
