@@ -196,9 +196,14 @@ PRIM_SIGNATURES = {
                                          C.c_int, _f32p, _u32p, _f64p, _f32p, _u32p]),
     "of2d_prim_elastic_logger": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f64p]),
     "of2d_analysis_time_kernels": (C.c_int, [C.c_int, C.c_int, C.c_int, _f64p]),
-    "of2d_prim_pack_image": (C.c_int, [_darr, C.c_int, C.c_int, C.c_int, _f32p]),
+    "of2d_prim_pack_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_int)]),
+    "of2d_prim_pack_image": (C.c_int, [_darr, C.c_int, C.c_int, C.c_int, _f32p, _f32p_opt]),
     "of2d_prim_unpack_image": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
     "of2d_prim_unpack_motion": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _darr]),
+    "of2d_prim_pack_motion": (C.c_int, [_darr, C.c_int, C.c_int, C.c_int, _f32p, _f32p_opt]),
+    "of2d_prim_planar_to_motion": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, _f32p,
+                                             _f32p_opt]),
     "of2d_prim_batch_jacobian": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _f32p_opt, _f64p]),
     "of2d_prim_batch_invert": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                          _f32p, _f64p, _f32p_opt]),

@@ -928,26 +928,55 @@ void upload_pairs(of2d::batch::BField<T> &f, const float *host, int npairs, int 
     for (int k = 0; host && k < npairs; k++)
         upload(f.p + k * stride, of2d::pitch_for(dimx), host + k * per, dimx, dimy);
 }
+// the pack entries' target: npairs pitched fields with kPackSentinel in every
+// byte, not the allocator's zeros, so that a stray store of 0 shows in `raw`
+constexpr int kPackSentinel = 0xC5;  // as a float -6328.72: finite, unlikely
+template <class T>
+void sentinel_pairs(of2d::batch::BField<T> &f, int npairs, int dimx, int dimy) {
+    f.alloc(dimx, dimy, npairs);
+    OF2D_HIP(hipMemset(f.base, kPackSentinel, f.bytes()));
+}
+// the pixels of every pair, dense, into out_host; into raw_host (optional) the
+// whole allocation from its base: ghost j-lines and slack too
+template <class T>
+void download_pairs(const of2d::batch::BField<T> &f, int npairs, int dimx, int dimy,
+                    float *out_host, float *raw_host) {
+    const long stride = of2d::batch::pair_stride(dimx, dimy);
+    const size_t per = (size_t)dimx * dimy * (sizeof(T) / sizeof(float));
+    for (int k = 0; k < npairs; k++)
+        download(out_host + k * per, f.p + k * stride, of2d::pitch_for(dimx), dimx, dimy);
+    if (raw_host) OF2D_HIP(hipMemcpy(raw_host, f.base, f.bytes(), hipMemcpyDeviceToHost));
+}
+bool pack_sizes_ok(int npairs, int dimx, int dimy) {
+    return npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 && dimy > 0;
+}
 }  // namespace
 
 extern "C" {
 
-int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host) {
+int of2d_prim_pack_layout(int dimx, int dimy, long long *stride, int *pitch) {
+    if (!stride || !pitch || dimx < 1 || dimy < 1)
+        return refuse(nullptr, "of2d_prim_pack_layout: stride or pitch is NULL, or a size < 1");
+    *stride = of2d::batch::pair_stride(dimx, dimy);
+    *pitch = of2d::pitch_for(dimx);
+    return OF2D_OK;
+}
+
+int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host,
+                         float *raw_host) {
     const Extents e = {{npairs, dimx, dimy, 0}};
-    const bool ok = out_host && npairs > 0 && npairs <= of2d::batch::kMaxPairs && dimx > 0 &&
-                    dimy > 0;
+    const bool ok = out_host && pack_sizes_ok(npairs, dimx, dimy);
     const std::string why =
         ok ? first_refusal("of2d_prim_pack_image", {{in, "in", false, e}})
            : std::string("of2d_prim_pack_image: out_host is NULL or a size is out of range");
     if (!why.empty()) return refuse(nullptr, why.c_str());
     return prim(true, [&] {
         of2d::batch::BField<float> f;
-        upload_pairs(f, nullptr, npairs, dimx, dimy);
-        const long stride = of2d::batch::pair_stride(dimx, dimy);
-        const int P = of2d::pitch_for(dimx);
-        of2d::launch_pack_image(view_of(in, e), npairs, dimx, dimy, f.p, stride, P, nullptr);
-        for (int k = 0; k < npairs; k++)
-            download(out_host + (size_t)k * dimx * dimy, f.p + k * stride, P, dimx, dimy);
+        sentinel_pairs(f, npairs, dimx, dimy);
+        of2d::launch_pack_image(view_of(in, e), npairs, dimx, dimy, f.p,
+                                of2d::batch::pair_stride(dimx, dimy), of2d::pitch_for(dimx),
+                                nullptr);
+        download_pairs(f, npairs, dimx, dimy, out_host, raw_host);
     });
 }
 
@@ -986,6 +1015,46 @@ int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
                                    of2d::pitch_for(dimx), npairs, dimx, dimy, view_of(out, e),
                                    nullptr);
         OF2D_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
+int of2d_prim_pack_motion(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host,
+                          float *raw_host) {
+    const Extents e = {{npairs, dimx, dimy, 2}};
+    const bool ok = out_host && pack_sizes_ok(npairs, dimx, dimy);
+    const std::string why =
+        ok ? first_refusal("of2d_prim_pack_motion", {{in, "in", false, e}})
+           : std::string("of2d_prim_pack_motion: out_host is NULL or a size is out of range");
+    if (!why.empty()) return refuse(nullptr, why.c_str());
+    return prim(true, [&] {
+        int dev = 0;
+        (void)hipGetDevice(&dev);  // without a device the pointer check below refuses
+        of2d::check_device_pointer(in->ptr, dev, "of2d_prim_pack_motion: in");
+        of2d::batch::BField<float2> f;
+        sentinel_pairs(f, npairs, dimx, dimy);
+        of2d::launch_pack_motion(view_of(in, e), npairs, dimx, dimy, f.p,
+                                 of2d::batch::pair_stride(dimx, dimy), of2d::pitch_for(dimx),
+                                 nullptr);
+        download_pairs(f, npairs, dimx, dimy, out_host, raw_host);
+    });
+}
+
+int of2d_prim_planar_to_motion(const double *planar_host, int npairs, int dimx, int dimy,
+                               float *out_host, float *raw_host) {
+    if (!planar_host || !out_host || !pack_sizes_ok(npairs, dimx, dimy))
+        return refuse(nullptr, "of2d_prim_planar_to_motion: planar_host or out_host is NULL or a "
+                               "size is out of range");
+    return prim(true, [&] {
+        const size_t n = 2 * (size_t)npairs * dimx * dimy;
+        of2d::DevArray<double> in;
+        in.alloc(n);
+        OF2D_HIP(hipMemcpy(in.p, planar_host, n * sizeof(double), hipMemcpyHostToDevice));
+        of2d::batch::BField<float2> f;
+        sentinel_pairs(f, npairs, dimx, dimy);
+        of2d::launch_planar_to_motion(in.p, npairs, dimx, dimy, f.p,
+                                      of2d::batch::pair_stride(dimx, dimy),
+                                      of2d::pitch_for(dimx), nullptr);
+        download_pairs(f, npairs, dimx, dimy, out_host, raw_host);
     });
 }
 

@@ -222,12 +222,27 @@ int of2d_analysis_time_kernels(int dimx, int dimy, int nlaunch, double *us);
  * stream: pack `in` into npairs pitched fields and download them dense, float
  * [npairs][dimy][dimx]; upload dense fields (m_host interleaved x, y as the
  * other primitives' motion) and unpack them into `out`.  Refusals as for the
- * of2d_*_device entries, with the message in of2d_gateway_last_error. */
-int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host);
+ * of2d_*_device entries, with the message in of2d_gateway_last_error.
+ * The pack entries (an image stack, a motion stack [npairs][dimy][dimx][2], and
+ * the host form's planar doubles [npairs][2][dimy][dimx]) fill the pitched
+ * fields with the byte 0xC5 before the launch (as a float -6328.72), not with
+ * the allocator's zeros.  raw_host (optional) receives the whole allocation
+ * from its base, npairs * stride elements of the field's type: every pair's
+ * ghost j-line above (P elements), its dimy rows of pitch P, the ghost j-line
+ * below and the slack; what no store touched holds the sentinel.
+ * of2d_prim_pack_layout reports that stride and P, in elements.
+ * of2d_prim_pack_motion also refuses a pointer that is no device pointer. */
+int of2d_prim_pack_layout(int dimx, int dimy, long long *stride, int *pitch);
+int of2d_prim_pack_image(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host,
+                         float *raw_host);
 int of2d_prim_unpack_image(const float *in_host, int npairs, int dimx, int dimy,
                            const of2d_darray *out);
 int of2d_prim_unpack_motion(const float *m_host, int npairs, int dimx, int dimy,
                             const of2d_darray *out);
+int of2d_prim_pack_motion(const of2d_darray *in, int npairs, int dimx, int dimy, float *out_host,
+                          float *raw_host);
+int of2d_prim_planar_to_motion(const double *planar_host, int npairs, int dimx, int dimy,
+                               float *out_host, float *raw_host);
 
 /* ---- batched analysis kernels (batch_analysis_kernels.hip), one launch each ----
  * Dense host stacks of B pairs: u, v float [B][dimy][dimx][2], images and jac

@@ -253,14 +253,62 @@ class prim:
     # are torch CUDA tensors whose dimension d is the of2d_darray axis
     # ``axes[d]`` (0 pair, 1 x, 2 y, 3 component); the host side is float32 in
     # the layout above with a leading pair axis.
+    #
+    # The pack entries take ``raw=True`` and then return ``(out, raw)``: ``raw``
+    # is the whole allocation of the pitched fields, ``[npairs, stride]`` (a
+    # motion: ``[npairs, stride, 2]``) with ``pack_layout``'s stride, holding
+    # ``PACK_SENTINEL`` in every word that no store touched; pixel (i, j) of a
+    # pair is element ``P + j * P + i`` of its row.
+    PACK_SENTINEL = 0xC5C5C5C5
+
     @classmethod
-    def pack_image(cls, t, axes=(0, 1, 2)):
+    def pack_layout(cls, dimx, dimy):
+        """``(stride, P)`` of the batch's pitched fields, in elements."""
+        stride, P = C.c_longlong(0), C.c_int(0)
+        cls._call("of2d_prim_pack_layout", int(dimx), int(dimy), C.byref(stride), C.byref(P))
+        return int(stride.value), int(P.value)
+
+    @classmethod
+    def _raw(cls, raw, npairs, dimx, dimy, tail=()):
+        if not raw:
+            return None
+        return np.zeros((npairs, cls.pack_layout(dimx, dimy)[0]) + tail, np.float32)
+
+    @classmethod
+    def pack_image(cls, t, axes=(0, 1, 2), raw=False):
         ext = dict(zip(axes, t.shape))
         npairs, dimx, dimy = ext[0], ext[1], ext[2]
         out = np.zeros((npairs, dimy, dimx), np.float32)
+        whole = cls._raw(raw, npairs, dimx, dimy)
         a = _device.darray(t, t.shape, axes, "in")
-        cls._call("of2d_prim_pack_image", C.byref(a), npairs, dimx, dimy, out)
-        return out
+        cls._call("of2d_prim_pack_image", C.byref(a), npairs, dimx, dimy, out, whole)
+        return (out, whole) if raw else out
+
+    @classmethod
+    def pack_motion(cls, t, axes=(0, 1, 2, 3), raw=False):
+        """``t`` with extent 2 on the component axis -> ``[npairs, dimy, dimx, 2]``."""
+        ext = dict(zip(axes, t.shape))
+        npairs, dimx, dimy = ext[0], ext[1], ext[2]
+        if ext[3] != 2:
+            raise ValueError(f"the component axis has extent {ext[3]}, expected 2")
+        out = np.zeros((npairs, dimy, dimx, 2), np.float32)
+        whole = cls._raw(raw, npairs, dimx, dimy, (2,))
+        a = _device.darray(t, t.shape, axes, "in")
+        cls._call("of2d_prim_pack_motion", C.byref(a), npairs, dimx, dimy, out, whole)
+        return (out, whole) if raw else out
+
+    @classmethod
+    def planar_to_motion(cls, a, raw=False):
+        """``a`` float64 ``[npairs, 2, dimy, dimx]`` (``motion_to_planar``'s
+        layout per pair) -> ``[npairs, dimy, dimx, 2]``, by the host form's kernel."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 4 or a.shape[1] != 2:
+            raise ValueError(f"a stack of planar fields is [npairs, 2, dimy, dimx], got {a.shape}")
+        npairs, _, dimy, dimx = a.shape
+        out = np.zeros((npairs, dimy, dimx, 2), np.float32)
+        whole = cls._raw(raw, npairs, dimx, dimy, (2,))
+        cls._call("of2d_prim_planar_to_motion", a, npairs, dimx, dimy, out, whole)
+        return (out, whole) if raw else out
 
     @classmethod
     def unpack_image(cls, a, out, axes=(0, 1, 2)):

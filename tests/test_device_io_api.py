@@ -15,7 +15,8 @@ import pytest
 DEVICE_SYMBOLS = ["of2d_set_images_device", "of2d_get_motion_device", "of2d_warp_device",
                   "of2d_batch_set_images_device", "of2d_batch_get_motion_device",
                   "of2d_batch_warp_device", "of2d_prim_pack_image", "of2d_prim_unpack_image",
-                  "of2d_prim_unpack_motion"]
+                  "of2d_prim_unpack_motion", "of2d_prim_pack_motion", "of2d_prim_planar_to_motion",
+                  "of2d_prim_pack_layout"]
 
 DIMX, DIMY, NB = 16, 12, 3
 FAKE = 0x1000  # never dereferenced: every call below is refused on the host
@@ -155,7 +156,7 @@ def test_primitive_refusals(of2d_lib):
         return L.of2d_gateway_last_error().decode()
 
     for bad, text in BAD_ANY + [NEG_PAIR]:
-        refused(L, L.of2d_prim_pack_image(ref(bad), NB, DIMX, DIMY, host), err(),
+        refused(L, L.of2d_prim_pack_image(ref(bad), NB, DIMX, DIMY, host, None), err(),
                 "of2d_prim_pack_image", "in", text)
     for bad, text in BAD_ANY + BAD_OUT + [BAD_PAIR, NEG_PAIR]:
         refused(L, L.of2d_prim_unpack_image(host, NB, DIMX, DIMY, ref(bad)), err(),
@@ -164,8 +165,61 @@ def test_primitive_refusals(of2d_lib):
         refused(L, L.of2d_prim_unpack_motion(host, NB, DIMX, DIMY, ref(bad)), err(),
                 "of2d_prim_unpack_motion", "out", text)
     for args in [(0, DIMX, DIMY), (NB, 0, DIMY), (NB, DIMX, -1), (65536, DIMX, DIMY)]:
-        assert L.of2d_prim_pack_image(ref(darr()), *args, host) == _lib.OF2D_ERR_INVALID_ARGUMENT
+        assert L.of2d_prim_pack_image(ref(darr()), *args, host, None) == \
+            _lib.OF2D_ERR_INVALID_ARGUMENT
         assert "size is out of range" in err()
+
+
+def test_pack_motion_refusals(of2d_lib):
+    """of2d_prim_pack_motion reads its array: unpack motion's refusals less
+    those of an output (a zero stride is a broadcast), and a host pointer;
+    of2d_prim_planar_to_motion and of2d_prim_pack_layout take host arguments."""
+    from opticalflow2d_amd import _lib
+    L = of2d_lib
+    bad_rc = _lib.OF2D_ERR_INVALID_ARGUMENT
+    host = np.zeros(NB * DIMX * DIMY * 2, np.float32)
+    planar = np.zeros(NB * DIMX * DIMY * 2, np.float64)
+    sizes = [(0, DIMX, DIMY), (NB, 0, DIMY), (NB, DIMX, -1), (65536, DIMX, DIMY)]
+
+    def err():
+        return L.of2d_gateway_last_error().decode()
+
+    for bad, text in BAD_ANY + [NEG_PAIR, NEG_COMP]:
+        refused(L, L.of2d_prim_pack_motion(ref(bad), NB, DIMX, DIMY, host, None), err(),
+                "of2d_prim_pack_motion", "in", text)
+    for args in sizes:
+        assert L.of2d_prim_pack_motion(ref(darr()), *args, host, None) == bad_rc
+        assert err() == "of2d_prim_pack_motion: out_host is NULL or a size is out of range"
+    # a host pointer as the device array: refused before anything is allocated
+    on_host = np.zeros(NB * DIMX * DIMY * 2, np.float32)
+    a = darr(ptr=on_host.ctypes.data, stride=(2 * DIMX * DIMY, 2, 2 * DIMX, 1))
+    assert L.of2d_prim_pack_motion(ref(a), NB, DIMX, DIMY, host, None) == bad_rc
+    assert err() == "of2d_prim_pack_motion: in.ptr is not a device pointer"
+    assert not host.any()
+
+    text = "of2d_prim_planar_to_motion: planar_host or out_host is NULL or a size is out of range"
+    for args in sizes:
+        assert L.of2d_prim_planar_to_motion(planar, *args, host, None) == bad_rc and err() == text
+    # NULL arrays: the table's ndpointer admits no None
+    fn = L.of2d_prim_planar_to_motion
+    saved, fn.argtypes = fn.argtypes, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2
+    try:
+        for p, o in ((None, host.ctypes.data), (planar.ctypes.data, None)):
+            assert fn(p, NB, DIMX, DIMY, o, None) == bad_rc and err() == text
+    finally:
+        fn.argtypes = saved
+
+    stride, P = C.c_longlong(-1), C.c_int(-1)
+    for args in [(0, DIMY, C.byref(stride), C.byref(P)), (DIMX, 0, C.byref(stride), C.byref(P)),
+                 (DIMX, DIMY, None, C.byref(P)), (DIMX, DIMY, C.byref(stride), None)]:
+        assert L.of2d_prim_pack_layout(*args) == bad_rc
+        assert err().startswith("of2d_prim_pack_layout:")
+    assert (stride.value, P.value) == (-1, -1)
+    # of2d_batch.h: a ghost j-line either side of the rows, one pitch unit of slack
+    assert L.of2d_prim_pack_layout(DIMX, DIMY, C.byref(stride), C.byref(P)) == _lib.OF2D_OK
+    assert (stride.value, P.value) == ((DIMY + 2) * 128 + 128, 128)
+    assert L.of2d_prim_pack_layout(129, 1, C.byref(stride), C.byref(P)) == _lib.OF2D_OK
+    assert (stride.value, P.value) == (3 * 256 + 128, 256)
 
 
 # ------------------------------------------------------------ the Python classes

@@ -298,7 +298,9 @@ def test_supplied_motion_pyramid(gpu, oracle):
 
 
 # ------------------------------------------------------------ 5. round trip and use
-@pytest.mark.parametrize("dims", [(37, 21), (1, 9), (9, 1)])
+# the last two: more than one block of the pack kernels along x, and two tiles
+# on both axes
+@pytest.mark.parametrize("dims", [(37, 21), (1, 9), (9, 1), (70, 67), (130, 17)])
 def test_round_trip(gpu, dims):
     B = 3
     rng = np.random.default_rng(11)

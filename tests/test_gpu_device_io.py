@@ -21,8 +21,9 @@ from opticalflow2d_amd import synthetic as S
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -777.0
-# cross the 64 x 64 tile's edge on each axis, sit on it, collapse an axis to 1
-SHAPES = [(64, 64), (65, 63), (1, 70), (70, 1), (130, 17)]
+# cross the 64 x 64 tile's edge on each axis, sit on it, collapse an axis to 1;
+# (70, 67): two tiles on both axes, both ragged (64 | 6 and 64 | 3)
+SHAPES = [(64, 64), (65, 63), (1, 70), (70, 1), (130, 17), (70, 67)]
 NPAIRS = [1, 3]
 DTYPES = [np.float32, np.float64]
 LAYOUTS = ["contiguous", "xfast", "sliced"]

@@ -106,7 +106,7 @@ def test_reset_motion_gives_a_new_object(gpu, method, niter, nscales, dims):
         assert not np.array_equal(r.motion(), want)
 
 
-@pytest.mark.parametrize("dims", [(37, 21), (1, 9), (9, 1)])
+@pytest.mark.parametrize("dims", [(37, 21), (1, 9), (9, 1), (70, 67), (130, 17)])
 def test_set_motion_then_motion_is_the_identity(gpu, dims):
     from opticalflow2d_amd import ImageRegistration
     m = f32(3.0 * np.random.default_rng(5).standard_normal(dims + (2,)))
