@@ -10,7 +10,12 @@ option of that name: Diffeomorphic Demons, every frame with its own number of
 squarings per iteration.
 
     python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
-                                  [--diffeomorphic] [--report] [--track T]
+                                  [--diffeomorphic] [--resident] [--report] [--track T]
+
+--resident (Horn-Schunck only) turns on the batch's option of that name: the
+levels that fit keep the iterate in LDS and the gradients in registers across
+the iterations.  The iteration counts and the motion are the same bits; the
+placement per level is printed.
 
 --report adds the deformation analysis of the batch, one call each for all
 frames: how many frames fold and the worst minimum Jacobian, the inverse of
@@ -35,12 +40,19 @@ from opticalflow2d_amd import BatchRegistration  # noqa: E402
 from opticalflow2d_amd import synthetic as S  # noqa: E402
 
 
+def options_of(a):
+    options = {"diffeomorphic": 1} if a.diffeomorphic else {}
+    if a.resident:
+        options["resident"] = 1
+    return options
+
+
 def track(a):
     """T frames of B slices, frame after frame: warm_start=1 against the default."""
     n, B, T = a.size, a.frames, a.track
     refs, frames, shifts = S.cine_series(n, B, T)
     params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
-    options = {"diffeomorphic": 1} if a.diffeomorphic else {}
+    options = options_of(a)
     rows = []
     with BatchRegistration(B, (n, n), [a.niter], 0, params, reg=a.reg, warm_start=1,
                            **options) as warm, \
@@ -71,6 +83,9 @@ def main():
                     help="0 Horn-Schunck (alpha), 3 Thirion's Demons")
     ap.add_argument("--diffeomorphic", action="store_true",
                     help="with --reg 3: Diffeomorphic Demons (the option 'diffeomorphic')")
+    ap.add_argument("--resident", action="store_true",
+                    help="with --reg 0: the iterate on the CU at the levels that fit "
+                         "(the option 'resident')")
     ap.add_argument("--report", action="store_true",
                     help="print the batch's Jacobian, inverse and quality summary")
     ap.add_argument("--track", type=int, default=0, metavar="T",
@@ -78,6 +93,8 @@ def main():
     a = ap.parse_args()
     if a.diffeomorphic and a.reg != 3:
         ap.error("--diffeomorphic is an option of --reg 3")
+    if a.resident and a.reg != 0:
+        ap.error("--resident is an option of --reg 0")
     if a.track:
         return track(a)
     n, B = a.size, a.frames
@@ -89,7 +106,7 @@ def main():
     frames = np.stack([S.texture_pair(n, seed=3, sigma=3.0, shift=(sx, sy))[1]
                        for sx, sy in shifts])
     params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
-    options = {"diffeomorphic": 1} if a.diffeomorphic else {}
+    options = options_of(a)
     with BatchRegistration(B, (n, n), [a.niter, a.niter], 1, params, reg=a.reg, **options) as b:
         b.register(ref, frames)  # one reference shared by every frame
         motion = b.motion()
@@ -102,6 +119,8 @@ def main():
             quality = b.quality(ref, frames)
     print(f"{B} frames of {n} x {n} against frame 0: {info['launches']} kernel launches, "
           f"loop kernels {info['loop_us']} us")
+    if a.resident:
+        print(f"iterate placement per level from level 0 (1: on the CU): {info['placement']}")
     print("frame  shift (px)      iterations (coarse, fine)  mean motion (px)    rms before -> after")
     inner = (slice(None), slice(8, n - 8), slice(8, n - 8))
     before = np.sqrt(((frames - ref) ** 2)[inner].reshape(B, -1).mean(axis=1))

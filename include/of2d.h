@@ -398,7 +398,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
  * Options: "fixed_iters", "device" (before first use), "diffeomorphic",
- * "warm_start"; an
+ * "warm_start", "resident"; an
  * unknown key is refused ("demons_separable" among them: the batch smooths
  * with the direct convolution only).
  *
@@ -437,6 +437,25 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * is nscales + 1, one per level.  A value other than 0 or 1 is refused with
  * "warm_start: the value must be 0 or 1", the option unchanged.
  *
+ * "resident" (0, the default, or 1), Diffusion batches; set before or after
+ * the device is in use, the next of2d_batch_estimate takes the value.  With 1
+ * every pyramid level that fits runs the Horn-Schunck loop with the pair's
+ * iterate in the compute unit's LDS and dI, It in registers across all
+ * iterations of the loop, instead of moving them through global memory in
+ * every iteration; the other levels run the global-memory loop.  A level
+ * (dx, dy) fits when (dx + 2) * (dy + 2) * 8 + 1024 bytes are within the
+ * 160 KiB of LDS and dx * dy <= 16 * 1024 (16 pixels for each of the
+ * workgroup's 1024 threads): every level up to 128 x 128 does.  Motion, warp,
+ * iteration counts, errors and the per-pair divide-by-zero status are those of
+ * 0, bit for bit; the launches of an estimate are the same; of2d_batch_info
+ * reports placement 1 for the levels that ran so.  Should the runtime refuse
+ * the kernel its LDS, every level runs as with 0 (placement 0) and nothing is
+ * reported as an error.  Composes with "fixed_iters", "warm_start" and
+ * "device".  Refused with OF2D_ERR_INVALID_ARGUMENT, the handle still usable
+ * and the option unchanged: on a Demons batch ("resident: the batch is not a
+ * Diffusion batch") and for a value other than 0 or 1 ("resident: the value
+ * must be 0 or 1").
+ *
  * Splitting one pair over several workgroups is not offered: with
  * fewer pairs than compute units most of the device idles. */
 typedef struct of2d_batch of2d_batch;
@@ -474,8 +493,9 @@ int of2d_batch_iterations(const of2d_batch *b, int *out, int cap);
 int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap);
 /* info = {kernel launches of the last estimate, loops per pair, levels, device
  * time of the last estimate's loop kernels in microseconds, then per level from
- * level 0: where the iterate lives (0: global memory), threads of a pair's
- * workgroup}; returns the number of values */
+ * level 0: where the iterate lived in the last estimate (0: global memory, 1:
+ * on the compute unit, option "resident"; 0 before the first estimate),
+ * threads of a pair's workgroup}; returns the number of values */
 int of2d_batch_info(const of2d_batch *b, int *info, int n);
 /* Deformation analysis of every pair's level-0 motion (of2d_jacobian,
  * of2d_invert_motion and of2d_quality per pair): one or two kernel launches

@@ -94,6 +94,7 @@ void Batch::release_device() {
     if (st_) (void)hipStreamDestroy(st_);
     st_ = nullptr;
     ref_pairs_ = 0;
+    resident_ok_ = -1;
     ready_ = false;
 }
 
@@ -119,6 +120,14 @@ void Batch::set_option(const std::string &key, double v) {
         if (!(v == 0 || v == 1))  // a NaN too
             throw std::invalid_argument("warm_start: the value must be 0 or 1");
         warm_ = v == 1;
+    } else if (key == "resident") {
+        // the Horn-Schunck loop with the iterate on the CU at the levels that
+        // fit (resident_fits), taken by the next estimate; a refusal changes
+        // nothing
+        if (reg_ != 0) throw std::invalid_argument("resident: the batch is not a Diffusion batch");
+        if (!(v == 0 || v == 1))  // a NaN too
+            throw std::invalid_argument("resident: the value must be 0 or 1");
+        resident_ = v == 1;
     } else
         throw std::invalid_argument("unknown option: " + key);
 }
@@ -281,6 +290,12 @@ void Batch::estimate() {
     launches_ = 0;
     pair_err_.clear();
     OF2D_HIP(hipMemsetAsync(d_status_, 0, sizeof(unsigned) * B_, st_));
+    // option "resident": asked of the runtime once per handle; a refusal there
+    // is "no level fits", not an error
+    if (resident_ && resident_ok_ < 0) resident_ok_ = resident_prepare() ? 1 : 0;
+    placement_.assign(nscales_ + 1, 0);
+    if (resident_ && resident_ok_ == 1)
+        for (int s = 0; s <= nscales_; s++) placement_[s] = resident_fits(ldx_[s], ldy_[s]) ? 1 : 0;
     const bool warm = warm_;
     if (!warm)
         for (BLevel &L : lv_) {
@@ -327,6 +342,8 @@ void Batch::estimate() {
             OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
             if (reg_ == 3)
                 launch_demons_loop(demons_args(L, s, loop), B_, conv, st_);
+            else if (placement_[s])
+                launch_hs_resident(a, B_, conv, st_);
             else
                 launch_hs_loop(a, B_, conv, st_);
             OF2D_HIP(hipEventRecord(ev_[2 * loop + 1], st_));
@@ -719,7 +736,8 @@ std::vector<float> Batch::last_errors(int pair) const {
 std::vector<int> Batch::info() const {
     std::vector<int> v = {launches_, nloops_, nscales_ + 1, (int)std::lround(loop_us_)};
     for (int s = 0; s <= nscales_; s++) {
-        v.push_back(0);  // the iterate ping-pongs in global memory at every level
+        // 0: the iterate ping-pongs in global memory; 1: it stays on the CU
+        v.push_back(s < (int)placement_.size() ? placement_[s] : 0);
         v.push_back(kLoopThreads);
     }
     return v;

@@ -54,6 +54,36 @@ struct LoopArgs {
 // order: the logger_fp64 semantics); otherwise exactly niter iterations
 void launch_hs_loop(const LoopArgs &a, int B, bool conv, hipStream_t st);
 
+// ---- option "resident" (batch_resident_kernels.hip): the
+// same loop with the pair's iterate in LDS and dI, It in registers across the
+// iterations.  The fit rule, one predicate on the level's size: the iterate's
+// one LDS copy, (dx + 2) x (dy + 2) float2 with its ghost ring, plus
+// kResidentLdsReserve bytes for the kernel's static LDS (block_sums' scratch
+// and the break flag) fits the CU's 160 KiB, and a thread of the 1024 owns at
+// most kResidentMaxPpt pixels (the largest instantiation; dI, It and the new
+// values of 16 pixels are 80 of the 128 registers a lane of such a workgroup
+// may have).  Every level up to 128 x 128 fits (135 200 B, 16 pixels); 150 x
+// 120 fails on the pixels and 2 x 6000 on the bytes. Batch::estimate chooses
+// the kernel by it and Batch::info reports it (placement 1).
+constexpr int kResidentLdsBudget = 160 * 1024;
+constexpr int kResidentLdsReserve = 1024;
+constexpr int kResidentMaxPpt = 16;
+inline size_t resident_lds_bytes(int dx, int dy) {
+    return (size_t)(dx + 2) * (size_t)(dy + 2) * sizeof(float2);
+}
+inline bool resident_fits(int dx, int dy) {
+    return dx >= 1 && dy >= 1 &&
+           resident_lds_bytes(dx, dy) + kResidentLdsReserve <= (size_t)kResidentLdsBudget &&
+           (long)dx * dy <= (long)kResidentMaxPpt * kLoopThreads;
+}
+// once per device before the first launch: admits the dynamic LDS above the
+// default limit for every instantiation; false when the runtime refuses (the
+// caller then runs launch_hs_loop at every level)
+bool resident_prepare();
+// a, conv: launch_hs_loop's; resident_fits(a.dx, a.dy) must hold.  Dynamic LDS
+// is the level's resident_lds_bytes, so a small level does not reserve a CU
+void launch_hs_resident(const LoopArgs &a, int B, bool conv, hipStream_t st);
+
 // One Gaussian table of the Demons loop on the device (Batch::allocate_device):
 // (float) weights for the sums, double weights for the boundary weight sums,
 // idx = (ii + c) + (jj + c) * kw, and the interior weight sum in the
@@ -270,7 +300,8 @@ class Batch {
     // warm_start nscales + 1 zeroings, one per level
     // {launches of the last estimate, loops per pair, levels, loop kernels'
     // device time of the last estimate in microseconds, then per level from 0:
-    // iterate placement (0: global memory), threads of the pair's workgroup}
+    // iterate placement in the last estimate (0: global memory, 1: on the CU,
+    // option "resident"), threads of the pair's workgroup}
     std::vector<int> info() const;
     // "" or the first pair's divide-by-zero message
     const std::string &pair_error() const { return pair_err_; }
@@ -304,6 +335,12 @@ class Batch {
     bool fixed_ = false, shared_ = false, have_images_ = false;
     bool diffeo_ = false;  // option "diffeomorphic" (reg 3, Composition only)
     bool warm_ = false;    // option "warm_start": estimate() resets no motion
+    // option "resident" (reg 0): the levels that resident_fits run
+    // launch_hs_resident.  resident_ok_: resident_prepare's answer on home_,
+    // -1 before it is asked; placement_: per level, what the last estimate ran
+    bool resident_ = false;
+    int resident_ok_ = -1;
+    std::vector<int> placement_;
     int device_ = -1, home_ = -1;
     bool ready_ = false;
     int ref_pairs_ = 0;  // images Iref holds at every level: 0, 1 (shared) or B
