@@ -10,12 +10,17 @@ option of that name: Diffeomorphic Demons, every frame with its own number of
 squarings per iteration.
 
     python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
-                                  [--diffeomorphic] [--resident] [--report] [--track T]
+                                  [--diffeomorphic] [--resident] [--conv-lds] [--report]
+                                  [--track T]
 
 --resident (Horn-Schunck only) turns on the batch's option of that name: the
 levels that fit keep the iterate in LDS and the gradients in registers across
 the iterations.  The iteration counts and the motion are the same bits; the
 placement per level is printed.
+
+--conv-lds (--reg 3 only) turns on the batch's option "conv_lds": the levels
+that fit keep the field the Demons loop's two convolutions read in LDS.  Again
+the same bits, and the placement per level is printed.
 
 --report adds the deformation analysis of the batch, one call each for all
 frames: how many frames fold and the worst minimum Jacobian, the inverse of
@@ -44,6 +49,8 @@ def options_of(a):
     options = {"diffeomorphic": 1} if a.diffeomorphic else {}
     if a.resident:
         options["resident"] = 1
+    if a.conv_lds:
+        options["conv_lds"] = 1
     return options
 
 
@@ -86,6 +93,9 @@ def main():
     ap.add_argument("--resident", action="store_true",
                     help="with --reg 0: the iterate on the CU at the levels that fit "
                          "(the option 'resident')")
+    ap.add_argument("--conv-lds", action="store_true",
+                    help="with --reg 3: the convolved field in LDS at the levels that fit "
+                         "(the option 'conv_lds')")
     ap.add_argument("--report", action="store_true",
                     help="print the batch's Jacobian, inverse and quality summary")
     ap.add_argument("--track", type=int, default=0, metavar="T",
@@ -95,6 +105,8 @@ def main():
         ap.error("--diffeomorphic is an option of --reg 3")
     if a.resident and a.reg != 0:
         ap.error("--resident is an option of --reg 0")
+    if a.conv_lds and a.reg != 3:
+        ap.error("--conv-lds is an option of --reg 3")
     if a.track:
         return track(a)
     n, B = a.size, a.frames
@@ -121,6 +133,9 @@ def main():
           f"loop kernels {info['loop_us']} us")
     if a.resident:
         print(f"iterate placement per level from level 0 (1: on the CU): {info['placement']}")
+    if a.conv_lds:
+        print(f"convolved field's placement per level from level 0 (1: in LDS): "
+              f"{info['placement']}")
     print("frame  shift (px)      iterations (coarse, fine)  mean motion (px)    rms before -> after")
     inner = (slice(None), slice(8, n - 8), slice(8, n - 8))
     before = np.sqrt(((frames - ref) ** 2)[inner].reshape(B, -1).mean(axis=1))

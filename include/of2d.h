@@ -398,7 +398,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
  * Options: "fixed_iters", "device" (before first use), "diffeomorphic",
- * "warm_start", "resident"; an
+ * "warm_start", "resident", "conv_lds"; an
  * unknown key is refused ("demons_separable" among them: the batch smooths
  * with the direct convolution only).
  *
@@ -456,6 +456,26 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * Diffusion batch") and for a value other than 0 or 1 ("resident: the value
  * must be 0 or 1").
  *
+ * "conv_lds" (0, the default, or 1), Thirion's Demons batches; set before or
+ * after the device is in use, the next of2d_batch_estimate takes the value.
+ * With 1 every pyramid level that fits runs the Demons loop with the field its
+ * two Gaussian convolutions read (the correction, then the motion before the
+ * last smoothing; with "diffeomorphic" every squaring of exp() as well) in the
+ * compute unit's LDS instead of global memory; the other levels run the
+ * global-memory loop.  A level (dx, dy) fits when (dx * dy + dx + 1) * 8 + 1024
+ * bytes are within the 160 KiB of LDS and dx * dy <= 16 * 1024 (16 pixels for
+ * each of the workgroup's 1024 threads): every level up to 128 x 128 does.
+ * Motion, warp, iteration counts, errors and the per-pair divide-by-zero
+ * status are those of 0, bit for bit; the launches of an estimate are the
+ * same; of2d_batch_info reports placement 1 for the levels that ran so.
+ * Should the runtime refuse the kernel its LDS, every level runs as with 0
+ * (placement 0) and nothing is reported as an error.  Composes with
+ * "fixed_iters", "warm_start", "device" and "diffeomorphic".  Refused with
+ * OF2D_ERR_INVALID_ARGUMENT, the handle still usable and the option
+ * unchanged: on a Diffusion batch ("conv_lds: the batch is not a Thirion's
+ * Demons batch") and for a value other than 0 or 1 ("conv_lds: the value must
+ * be 0 or 1").
+ *
  * Splitting one pair over several workgroups is not offered: with
  * fewer pairs than compute units most of the device idles. */
 typedef struct of2d_batch of2d_batch;
@@ -493,8 +513,9 @@ int of2d_batch_iterations(const of2d_batch *b, int *out, int cap);
 int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap);
 /* info = {kernel launches of the last estimate, loops per pair, levels, device
  * time of the last estimate's loop kernels in microseconds, then per level from
- * level 0: where the iterate lived in the last estimate (0: global memory, 1:
- * on the compute unit, option "resident"; 0 before the first estimate),
+ * level 0: the placement in the last estimate (0: global memory; 1: on the
+ * compute unit, the iterate with option "resident", the convolved field with
+ * option "conv_lds"; 0 before the first estimate),
  * threads of a pair's workgroup}; returns the number of values */
 int of2d_batch_info(const of2d_batch *b, int *info, int n);
 /* Deformation analysis of every pair's level-0 motion (of2d_jacobian,

@@ -34,11 +34,15 @@ class BatchRegistration:
     sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
     method is refused.  The other keyword options map to
     ``of2d_batch_set_option``: ``fixed_iters``, ``device``, ``diffeomorphic``,
-    ``warm_start``, ``resident``.  ``resident=1`` (Diffusion only, refused with
+    ``warm_start``, ``resident``, ``conv_lds``.  ``resident=1`` (Diffusion only, refused with
     ``InvalidArgument`` otherwise) keeps a pair's iterate in LDS and its
     gradients in registers across the iterations at every pyramid level that
     fits (all up to 128 x 128; :meth:`info` reports ``placement`` 1 there);
-    results are those of the default 0 bit for bit.  ``warm_start=1`` (every method) makes :meth:`register`
+    results are those of the default 0 bit for bit.  ``conv_lds=1`` (``reg=3``
+    only, refused with ``InvalidArgument`` otherwise) keeps the field that the
+    Demons loop's two convolutions read in LDS at every level that fits (all
+    up to 128 x 128; ``placement`` 1), again with the bits of the default 0.
+    ``warm_start=1`` (every method) makes :meth:`register`
     continue from the motion the handle holds, as a reused
     :class:`ImageRegistration` does, bit for bit per pair; see
     :meth:`set_motion` for a start from outside and for the pyramid's
@@ -315,9 +319,10 @@ class BatchRegistration:
     def info(self) -> dict:
         """``launches`` of the last estimate (independent of nbatch), ``loops``
         per pair, ``loop_us`` (device time of the loop kernels), and per level
-        from level 0 ``placement`` in the last estimate (0: the iterate in
-        global memory, 1: on the compute unit, option ``resident``) and
-        ``threads`` of a pair's workgroup."""
+        from level 0 ``placement`` in the last estimate (0: global memory; 1:
+        on the compute unit, the iterate with option ``resident``, the
+        convolved field with option ``conv_lds``) and ``threads`` of a pair's
+        workgroup."""
         buf = (C.c_int * 256)()
         n = _lib.lib().of2d_batch_info(self._h, buf, 256)
         v = list(buf[: max(n, 0)])

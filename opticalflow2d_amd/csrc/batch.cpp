@@ -95,6 +95,7 @@ void Batch::release_device() {
     st_ = nullptr;
     ref_pairs_ = 0;
     resident_ok_ = -1;
+    conv_lds_ok_ = -1;
     ready_ = false;
 }
 
@@ -128,6 +129,15 @@ void Batch::set_option(const std::string &key, double v) {
         if (!(v == 0 || v == 1))  // a NaN too
             throw std::invalid_argument("resident: the value must be 0 or 1");
         resident_ = v == 1;
+    } else if (key == "conv_lds") {
+        // the Demons loop with the convolved field in LDS at the levels that
+        // fit (conv_lds_fits), taken by the next estimate; a refusal changes
+        // nothing
+        if (reg_ != 3)
+            throw std::invalid_argument("conv_lds: the batch is not a Thirion's Demons batch");
+        if (!(v == 0 || v == 1))  // a NaN too
+            throw std::invalid_argument("conv_lds: the value must be 0 or 1");
+        conv_lds_ = v == 1;
     } else
         throw std::invalid_argument("unknown option: " + key);
 }
@@ -296,6 +306,10 @@ void Batch::estimate() {
     placement_.assign(nscales_ + 1, 0);
     if (resident_ && resident_ok_ == 1)
         for (int s = 0; s <= nscales_; s++) placement_[s] = resident_fits(ldx_[s], ldy_[s]) ? 1 : 0;
+    // option "conv_lds": the same for the Demons loop
+    if (conv_lds_ && conv_lds_ok_ < 0) conv_lds_ok_ = conv_lds_prepare() ? 1 : 0;
+    if (conv_lds_ && conv_lds_ok_ == 1)
+        for (int s = 0; s <= nscales_; s++) placement_[s] = conv_lds_fits(ldx_[s], ldy_[s]) ? 1 : 0;
     const bool warm = warm_;
     if (!warm)
         for (BLevel &L : lv_) {
@@ -340,7 +354,9 @@ void Batch::estimate() {
             a.errs = d_errs_;
             a.maxn = maxn_;
             OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
-            if (reg_ == 3)
+            if (reg_ == 3 && placement_[s])
+                launch_demons_lds(demons_args(L, s, loop), B_, conv, st_);
+            else if (reg_ == 3)
                 launch_demons_loop(demons_args(L, s, loop), B_, conv, st_);
             else if (placement_[s])
                 launch_hs_resident(a, B_, conv, st_);
@@ -736,7 +752,8 @@ std::vector<float> Batch::last_errors(int pair) const {
 std::vector<int> Batch::info() const {
     std::vector<int> v = {launches_, nloops_, nscales_ + 1, (int)std::lround(loop_us_)};
     for (int s = 0; s <= nscales_; s++) {
-        // 0: the iterate ping-pongs in global memory; 1: it stays on the CU
+        // 0: every field of the loop in global memory; 1: the iterate
+        // (resident) or the convolved field (conv_lds) stays on the CU
         v.push_back(s < (int)placement_.size() ? placement_[s] : 0);
         v.push_back(kLoopThreads);
     }

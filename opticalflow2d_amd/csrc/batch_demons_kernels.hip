@@ -43,78 +43,13 @@
 // block-uniform; for finite floats it is at most 65.  The expressions are
 // maxabs_partial_kernel's, exp_prepare_kernel's and exp_scale_kernel's
 // (demons_kernels.hip); the squaring is accumulate_px (see there).
-#include "of2d_batch.h"
-
+#include "batch_demons_px.h"
 #include "field_px.h"
 
 namespace of2d {
 namespace batch {
 
 namespace {
-
-// Field<vector2d>::convolute (Field.tpp:209-269) at pixel (i, j) of the
-// pitched field f: the direct kw x kw sum over the taps whose LINEAR index
-// lin + ii + jj * dimx lies in [0, N) (a tap past an x edge is the
-// neighbouring j-line's pixel), ii outer / jj inner, fp32 products and sums
-// with (float) weights; divided by (float) of the fp64 sum of the valid
-// weights (wfull where every tap is valid: the same additions in the same
-// order).  false: the weight sum is 0 and the reference leaves the pixel.
-// KW > 0: the width at compile time (the taps unrolled, the weights in scalar
-// registers); KW == 0: the runtime width kw_rt.  The same operations in the
-// same order either way.
-template <int KW>
-__device__ __forceinline__ bool conv_direct(const float2 *__restrict__ f, const DemonsTable &k,
-                                            int kw_rt, int i, int j, int dx, int dy, int P,
-                                            float2 &out) {
-    const int kw = KW > 0 ? KW : kw_rt;
-    const int c = (kw - 1) / 2;
-    const long N = (long)dx * dy, lin = (long)j * dx + i;
-    const bool interior = (lin - c - (long)c * dx >= 0) && (lin + c + (long)c * dx < N);
-    float vx = 0.0f, vy = 0.0f;
-    double weight = 0.0;
-#pragma unroll
-    for (int ii = -c; ii <= c; ii++) {
-        // column i + ii of j-line j + jj is pixel (col, j + jj + r)
-        int col = i + ii, r = 0;
-        while (col < 0) {  // once unless c > dx
-            col += dx;
-            r -= 1;
-        }
-        while (col >= dx) {
-            col -= dx;
-            r += 1;
-        }
-        const float *kf = k.kf + (ii + c);
-        if (interior) {
-            const float2 *p = f + (long)(j + r - c) * P + col;
-#pragma unroll
-            for (int q = 0; q <= 2 * c; q++) {  // q = jj + c
-                const float2 t = p[(long)q * P];
-                const float w = kf[q * kw];
-                vx = vx + t.x * w;
-                vy = vy + t.y * w;
-            }
-        } else {
-            const double *kd = k.kd + (ii + c);
-#pragma unroll
-            for (int q = 0; q <= 2 * c; q++) {
-                const int row = j + r + q - c;
-                // 0 <= col < dx: row * dx + col is in [0, N) iff the row is
-                if ((unsigned)row >= (unsigned)dy) continue;  // Field.tpp:245-247
-                const float2 t = f[(long)row * P + col];
-                const float w = kf[q * kw];
-                vx = vx + t.x * w;
-                vy = vy + t.y * w;
-                weight += kd[q * kw];
-            }
-        }
-    }
-    if (interior) weight = k.wfull;
-    if (weight == 0) return false;
-    const float wf = (float)weight;  // coord2d::operator/(const T&) with T = float
-    out = make_float2(vx / wf, vy / wf);
-    return true;
-}
 
 template <int WAVES, bool CONV, int KW, bool EXP>
 __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs a) {
@@ -148,32 +83,11 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
             W[o] = warp_px(Iaux, src[o], Iaux[o], i, j, dx, dy, P);
         }
         __syncthreads();
-        // 2. the correction: gradients.h:9-32 (central / 2.0f, one-sided on the
-        // borders; with one column f[idx + 1] is the next j-line's pixel, as
-        // gradients_px has it), It = W - Iref, Demons.cpp:57
+        // 2. the correction (demons_corr_px, batch_demons_px.h)
         for (int idx = tid; idx < npx; idx += T) {
             const int j = idx / dx, i = idx - j * dx;
             const long o = (long)j * P + i;
-            const float w0 = W[o];
-            float gx, gy;
-            if (i == 0)
-                gx = (dx > 1 ? W[o + 1] : (j < dy - 1 ? W[o + P] : 0.0f)) - w0;
-            else if (i == dx - 1)
-                gx = w0 - W[o - 1];
-            else
-                gx = (W[o + 1] - W[o - 1]) / 2.0f;
-            if (j == 0)
-                gy = W[o + P] - w0;
-            else if (j == dy - 1)
-                gy = w0 - W[o - P];
-            else
-                gy = (W[o + P] - W[o - P]) / 2.0f;
-            const float It = w0 - Iref[o];
-            // dI * It / (dI.x^2 + dI.y^2 + It*It*sigma_isq/sigma_xsq) * -1
-            const float t = (It * It) * a.sigma_isq;
-            const float den = (gx * gx + gy * gy) + t / a.sigma_xsq;
-            bad |= den == 0.0f;
-            C[o] = make_float2(((gx * It) / den) * -1.0f, ((gy * It) / den) * -1.0f);
+            C[o] = demons_corr_px(W, Iref[o], o, i, j, dx, dy, P, a.sigma_isq, a.sigma_xsq, bad);
         }
         if (bad) s_bad = 1;
         __syncthreads();
@@ -181,9 +95,7 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
         if constexpr (EXP) {
             __shared__ int s_nsq;
             // 3. the smoothed correction into mid, and Motion::maxabs
-            // (Motion.cpp:51-58: .y squared twice, in double) as
-            // maxabs_partial_kernel has it; the comparison drops a NaN term as
-            // std::max does
+            // (maxabs_fold, batch_demons_px.h)
             float mx = 0.0f;
             for (int idx = tid; idx < npx; idx += T) {
                 const int j = idx / dx, i = idx - j * dx;
@@ -191,22 +103,13 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
                 float2 c;
                 if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
                 M[o] = c;
-                const double y = (double)c.y;
-                const float s = (float)(y * y + y * y);
-                mx = (mx < s) ? s : mx;
+                mx = maxabs_fold(mx, c);
             }
             // 3a. the block's maximum (a thread without a pixel brings 0; the
-            // barrier inside is stage 3's) and the squaring count,
-            // exp_prepare_kernel's expressions (Motion.cpp:253-261): a NaN or
-            // out-of-int ceil converts to INT_MIN as on x86-64
+            // barrier inside is stage 3's) and the squaring count
+            // (exp_squarings, batch_demons_px.h)
             mx = block_max<WAVES>(mx, wave, lane);
-            if (tid == 0) {
-                const float ma = sqrtf(mx);
-                const float c = ceilf(1.0f + log2f(ma));
-                int nsq = (c == c && c > -2147483648.0f && c < 2147483648.0f) ? (int)c
-                                                                              : (int)0x80000000;
-                s_nsq = nsq < 0 ? 0 : nsq;
-            }
+            if (tid == 0) s_nsq = exp_squarings(mx);
             __syncthreads();
             const int nsq = s_nsq;  // block-uniform
             const float2 *E = M;    // the buffer that holds exp(c)

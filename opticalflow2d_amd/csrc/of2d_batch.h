@@ -122,6 +122,36 @@ struct DemonsLoopArgs {
 // conv as launch_hs_loop's
 void launch_demons_loop(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st);
 
+// ---- option "conv_lds" (batch_demons_lds_kernels.hip): the
+// same loop with the field its two convolutions read (the correction, then the
+// motion before the last smoothing; with `diffeomorphic` every squaring of
+// exp() too) in one dense float2 plane in LDS instead of the corr and mid
+// slices.  The fit rule, one predicate on the level's size: the plane, dx * dy
+// pixels at pitch dx without ghost lines plus dx + 1 zeroed elements that
+// accumulate_px's unconditional b[1], b[P], b[P + 1] loads reach from the last
+// pixels, plus kResidentLdsReserve bytes for the kernel's static LDS fits the
+// CU's 160 KiB, and a thread of the 1024 owns at most kConvLdsMaxPpt pixels
+// (the largest instantiation: their new values are 32 registers).  Every level
+// up to 128 x 128 fits (132 104 B); 129 x 128 fails on the pixels.
+// Batch::estimate chooses the kernel by it and Batch::info reports it
+// (placement 1).
+constexpr int kConvLdsMaxPpt = 16;
+inline size_t conv_lds_bytes(int dx, int dy) {
+    return ((size_t)dx * (size_t)dy + (size_t)dx + 1) * sizeof(float2);
+}
+inline bool conv_lds_fits(int dx, int dy) {
+    return dx >= 1 && dy >= 1 &&
+           conv_lds_bytes(dx, dy) + kResidentLdsReserve <= (size_t)kResidentLdsBudget &&
+           (long)dx * dy <= (long)kConvLdsMaxPpt * kLoopThreads;
+}
+// as resident_prepare: false when the runtime refuses the dynamic LDS (the
+// caller then runs launch_demons_loop at every level)
+bool conv_lds_prepare();
+// a, conv: launch_demons_loop's (corr and mid are not used);
+// conv_lds_fits(a.dx, a.dy) must hold.  Dynamic LDS is the level's
+// conv_lds_bytes
+void launch_demons_lds(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st);
+
 void launch_d2f(const double *in, int npairs, int dimx, int dimy, float *out, long so, int P,
                 hipStream_t st);
 void launch_f2d(const float *in, long si, int P, int dimx, int dimy, double *out, int npairs,
@@ -300,8 +330,9 @@ class Batch {
     // warm_start nscales + 1 zeroings, one per level
     // {launches of the last estimate, loops per pair, levels, loop kernels'
     // device time of the last estimate in microseconds, then per level from 0:
-    // iterate placement in the last estimate (0: global memory, 1: on the CU,
-    // option "resident"), threads of the pair's workgroup}
+    // placement in the last estimate (0: global memory; 1: on the CU, the
+    // iterate with option "resident", the convolved field with option
+    // "conv_lds"), threads of the pair's workgroup}
     std::vector<int> info() const;
     // "" or the first pair's divide-by-zero message
     const std::string &pair_error() const { return pair_err_; }
@@ -340,6 +371,10 @@ class Batch {
     // -1 before it is asked; placement_: per level, what the last estimate ran
     bool resident_ = false;
     int resident_ok_ = -1;
+    // option "conv_lds" (reg 3): the levels that conv_lds_fits run
+    // launch_demons_lds; conv_lds_ok_: conv_lds_prepare's answer, as above
+    bool conv_lds_ = false;
+    int conv_lds_ok_ = -1;
     std::vector<int> placement_;
     int device_ = -1, home_ = -1;
     bool ready_ = false;
