@@ -94,11 +94,18 @@ void Batch::release_device() {
     if (st_) (void)hipStreamDestroy(st_);
     st_ = nullptr;
     ref_pairs_ = 0;
-    resident_ok_ = -1;
-    conv_lds_ok_ = -1;
+    on_cu_ok_ = -1;
     ready_ = false;
 }
 
+// the value of a 0/1 option
+static bool flag_value(const std::string &key, double v) {
+    if (!(v == 0 || v == 1))  // a NaN too
+        throw std::invalid_argument(key + ": the value must be 0 or 1");
+    return v == 1;
+}
+
+// The 0/1 options are taken by the next estimate; a refusal changes nothing
 void Batch::set_option(const std::string &key, double v) {
     if (key == "fixed_iters")
         fixed_ = v != 0;
@@ -107,37 +114,25 @@ void Batch::set_option(const std::string &key, double v) {
         device_ = (int)v;
     } else if (key == "diffeomorphic") {
         // DemonsDiffeomorphic::get_update is DemonsThirions' with Composition
-        // plus exp(): an option of such a batch, taken by the next estimate.
-        // A refusal changes nothing.
+        // plus exp(): an option of such a batch
         if (reg_ != 3)
             throw std::invalid_argument("diffeomorphic: the batch is not a Thirion's Demons batch");
         if ((int)params_[5] != 0)
             throw std::invalid_argument("diffeomorphic: accumulation must be Composition (0)");
-        if (!(v == 0 || v == 1))  // a NaN too
-            throw std::invalid_argument("diffeomorphic: the value must be 0 or 1");
-        diffeo_ = v == 1;
+        diffeo_ = flag_value(key, v);
     } else if (key == "warm_start") {
-        // taken by the next estimate; a refusal changes nothing
-        if (!(v == 0 || v == 1))  // a NaN too
-            throw std::invalid_argument("warm_start: the value must be 0 or 1");
-        warm_ = v == 1;
+        warm_ = flag_value(key, v);
     } else if (key == "resident") {
         // the Horn-Schunck loop with the iterate on the CU at the levels that
-        // fit (resident_fits), taken by the next estimate; a refusal changes
-        // nothing
+        // fit (resident_fits)
         if (reg_ != 0) throw std::invalid_argument("resident: the batch is not a Diffusion batch");
-        if (!(v == 0 || v == 1))  // a NaN too
-            throw std::invalid_argument("resident: the value must be 0 or 1");
-        resident_ = v == 1;
+        on_cu_ = flag_value(key, v);
     } else if (key == "conv_lds") {
         // the Demons loop with the convolved field in LDS at the levels that
-        // fit (conv_lds_fits), taken by the next estimate; a refusal changes
-        // nothing
+        // fit (conv_lds_fits)
         if (reg_ != 3)
             throw std::invalid_argument("conv_lds: the batch is not a Thirion's Demons batch");
-        if (!(v == 0 || v == 1))  // a NaN too
-            throw std::invalid_argument("conv_lds: the value must be 0 or 1");
-        conv_lds_ = v == 1;
+        on_cu_ = flag_value(key, v);
     } else
         throw std::invalid_argument("unknown option: " + key);
 }
@@ -227,23 +222,45 @@ void Batch::set_images(const double *ref, bool shared_ref, const double *mov) {
     DeviceScope scope;  // the caller's device again on return
     ensure_device();
     ensure_reference(shared_ref ? 1 : B_);
-    const size_t n0 = (size_t)dimx_ * dimy_;
     BLevel &L0 = lv_[0];
     for (int which = 0; which < 2; which++) {
         const double *src = which ? mov : ref;
+        float *dst = which ? L0.Imov.p : L0.Iref.p;
         const int npairs = (!which && shared_ref) ? 1 : B_;
-        for (int k0 = 0; k0 < npairs; k0 += (int)stage_pairs_) {
-            const int nk = std::min<int>((int)stage_pairs_, npairs - k0);
-            OF2D_HIP(hipMemcpyAsync(d_stage_, src + k0 * n0, nk * n0 * sizeof(double),
-                                    hipMemcpyHostToDevice, st_));
-            BField<float> &dst0 = which ? L0.Imov : L0.Iref;
-            launch_d2f(d_stage_, nk, dimx_, dimy_, dst0.p + k0 * L0.stride, L0.stride, L0.P, st_);
-            // the staging buffer is reused by the next round
-            OF2D_HIP(hipStreamSynchronize(st_));
-        }
+        for_rounds(npairs, [&](const StageRound &r) { images_in(r, src, dst); });
         downsample_levels(which, npairs);
     }
     images_in_place(shared_ref);
+}
+
+// ---- one staging round's launches (of2d_batch.h, for_rounds)
+void Batch::images_in(const StageRound &r, const double *host, float *field) {
+    const BLevel &L0 = lv_[0];
+    OF2D_HIP(hipMemcpyAsync(d_stage_, host + r.image,
+                            sizeof(double) * r.nk * (size_t)dimx_ * dimy_, hipMemcpyHostToDevice,
+                            st_));
+    launch_d2f(d_stage_, r.nk, dimx_, dimy_, field + r.field, L0.stride, L0.P, st_);
+}
+void Batch::images_out(const StageRound &r, const float *field, double *host) {
+    const BLevel &L0 = lv_[0];
+    launch_f2d(field + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_, r.nk, st_);
+    OF2D_HIP(hipMemcpyAsync(host + r.image, d_stage_,
+                            sizeof(double) * r.nk * (size_t)dimx_ * dimy_, hipMemcpyDeviceToHost,
+                            st_));
+}
+void Batch::motion_in(const StageRound &r, const double *host, float2 *field) {
+    const BLevel &L0 = lv_[0];
+    OF2D_HIP(hipMemcpyAsync(d_stage_, host + r.motion,
+                            sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
+                            hipMemcpyHostToDevice, st_));
+    launch_planar_to_motion(d_stage_, r.nk, dimx_, dimy_, field + r.field, L0.stride, L0.P, st_);
+}
+void Batch::motion_out(const StageRound &r, const float2 *field, double *host) {
+    const BLevel &L0 = lv_[0];
+    launch_motion_to_planar(field + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_, r.nk, st_);
+    OF2D_HIP(hipMemcpyAsync(host + r.motion, d_stage_,
+                            sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
+                            hipMemcpyDeviceToHost, st_));
 }
 
 // the same from the caller's device arrays (include/of2d.h, the stream
@@ -300,16 +317,13 @@ void Batch::estimate() {
     launches_ = 0;
     pair_err_.clear();
     OF2D_HIP(hipMemsetAsync(d_status_, 0, sizeof(unsigned) * B_, st_));
-    // option "resident": asked of the runtime once per handle; a refusal there
-    // is "no level fits", not an error
-    if (resident_ && resident_ok_ < 0) resident_ok_ = resident_prepare() ? 1 : 0;
+    // option "resident" or "conv_lds": asked of the runtime once per handle; a
+    // refusal there is "no level fits", not an error
+    if (on_cu_ && on_cu_ok_ < 0)
+        on_cu_ok_ = (reg_ == 3 ? conv_lds_prepare() : resident_prepare()) ? 1 : 0;
     placement_.assign(nscales_ + 1, 0);
-    if (resident_ && resident_ok_ == 1)
-        for (int s = 0; s <= nscales_; s++) placement_[s] = resident_fits(ldx_[s], ldy_[s]) ? 1 : 0;
-    // option "conv_lds": the same for the Demons loop
-    if (conv_lds_ && conv_lds_ok_ < 0) conv_lds_ok_ = conv_lds_prepare() ? 1 : 0;
-    if (conv_lds_ && conv_lds_ok_ == 1)
-        for (int s = 0; s <= nscales_; s++) placement_[s] = conv_lds_fits(ldx_[s], ldy_[s]) ? 1 : 0;
+    if (on_cu_ && on_cu_ok_ == 1)
+        for (int s = 0; s <= nscales_; s++) placement_[s] = on_cu_fits(s) ? 1 : 0;
     const bool warm = warm_;
     if (!warm)
         for (BLevel &L : lv_) {
@@ -336,33 +350,7 @@ void Batch::estimate() {
                                  L.stride, L.dx, L.dy, L.P, B_, d_status_, st_);
             // motion_est starts at zero
             OF2D_HIP(hipMemsetAsync(L.est[0].base, 0, L.est[0].bytes(), st_));
-            LoopArgs a;
-            a.u0 = L.est[0].p;
-            a.u1 = L.est[1].p;
-            a.dI = L.dI.p;
-            a.It = L.It.p;
-            a.stride = L.stride;
-            a.dx = L.dx;
-            a.dy = L.dy;
-            a.P = L.P;
-            a.niter = niter_[s];
-            a.alphasq = alpha_ * alpha_;  // OpticalFlowDiffusion.cpp:70
-            a.status = d_status_;
-            a.iters = d_iters_;
-            a.nloops = nloops_;
-            a.loop = loop;
-            a.errs = d_errs_;
-            a.maxn = maxn_;
-            OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
-            if (reg_ == 3 && placement_[s])
-                launch_demons_lds(demons_args(L, s, loop), B_, conv, st_);
-            else if (reg_ == 3)
-                launch_demons_loop(demons_args(L, s, loop), B_, conv, st_);
-            else if (placement_[s])
-                launch_hs_resident(a, B_, conv, st_);
-            else
-                launch_hs_loop(a, B_, conv, st_);
-            OF2D_HIP(hipEventRecord(ev_[2 * loop + 1], st_));
+            launch_loop(s, loop, conv);
             // motion->accumulate(*motion_est)
             launch_accumulate(L.motion[L.mcur].p, L.est[0].p, L.est[1].p, L.motion[1 - L.mcur].p,
                               L.stride, L.dx, L.dy, L.P, B_, d_iters_, nloops_, loop, d_status_,
@@ -409,25 +397,49 @@ void Batch::estimate() {
         }
 }
 
-// the loop launch of level s (L) for Thirion's Demons: the iterate in est[],
-// It as the warped image, dI as the correction
-DemonsLoopArgs Batch::demons_args(BLevel &L, int s, int loop) const {
+// loop `loop` of level s, the iterate in est[]: the common arguments, the
+// regulariser's own, the kernel by placement_[s], between the loop's events
+void Batch::launch_loop(int s, int loop, bool conv) {
+    BLevel &L = lv_[s];
+    LoopCommon c;
+    c.u0 = L.est[0].p;
+    c.u1 = L.est[1].p;
+    c.stride = L.stride;
+    c.dx = L.dx;
+    c.dy = L.dy;
+    c.P = L.P;
+    c.niter = niter_[s];
+    c.status = d_status_;
+    c.iters = d_iters_;
+    c.nloops = nloops_;
+    c.loop = loop;
+    c.errs = d_errs_;
+    c.maxn = maxn_;
+    OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
+    if (reg_ == 3) {
+        (placement_[s] ? launch_demons_lds : launch_demons_loop)(demons_args(c, L), B_, conv, st_);
+    } else {
+        LoopArgs a{c};
+        a.dI = L.dI.p;
+        a.It = L.It.p;
+        a.alphasq = alpha_ * alpha_;  // OpticalFlowDiffusion.cpp:70
+        (placement_[s] ? launch_hs_resident : launch_hs_loop)(a, B_, conv, st_);
+    }
+    OF2D_HIP(hipEventRecord(ev_[2 * loop + 1], st_));
+}
+
+// c and Thirion's Demons' own arguments at level L: It as the warped image, dI
+// as the correction
+DemonsLoopArgs Batch::demons_args(const LoopCommon &c, BLevel &L) const {
     const size_t n = kfluid_.size();
     const int kw = (int)(unsigned)params_[4];
-    DemonsLoopArgs a;
-    a.u0 = L.est[0].p;
-    a.u1 = L.est[1].p;
+    DemonsLoopArgs a{c};
     a.Iref = L.Iref.p;
     a.sref = shared_ ? 0 : L.stride;
     a.Iaux = L.Iaux.p;
     a.W = L.It.p;
     a.corr = L.dI.p;
     a.mid = L.mid.p;
-    a.stride = L.stride;
-    a.dx = L.dx;
-    a.dy = L.dy;
-    a.P = L.P;
-    a.niter = niter_[s];
     // Demons.cpp:48-49
     a.sigma_isq = params_[0] * params_[0];
     a.sigma_xsq = params_[1] * params_[1];
@@ -438,28 +450,14 @@ DemonsLoopArgs Batch::demons_args(BLevel &L, int s, int loop) const {
     const int accum = (int)params_[5];
     a.mode = accum == 0 ? 0 : (accum == 1 ? 1 : 2);
     a.diffeomorphic = diffeo_ ? 1 : 0;  // set_option admits it with mode 0 only
-    a.status = d_status_;
-    a.iters = d_iters_;
-    a.nloops = nloops_;
-    a.loop = loop;
-    a.errs = d_errs_;
-    a.maxn = maxn_;
     return a;
 }
 
 void Batch::get_motion(double *out) {
     DeviceScope scope;
     ensure_device();
-    BLevel &L0 = lv_[0];
-    const size_t n0 = (size_t)dimx_ * dimy_;
-    for (int k0 = 0; k0 < B_; k0 += (int)stage_pairs_) {
-        const int nk = std::min<int>((int)stage_pairs_, B_ - k0);
-        launch_motion_to_planar(L0.motion[L0.mcur].p + k0 * L0.stride, L0.stride, L0.P, dimx_,
-                                dimy_, d_stage_, nk, st_);
-        OF2D_HIP(hipMemcpyAsync(out + k0 * 2 * n0, d_stage_, sizeof(double) * 2 * n0 * nk,
-                                hipMemcpyDeviceToHost, st_));
-        OF2D_HIP(hipStreamSynchronize(st_));
-    }
+    const float2 *m = lv_[0].motion[lv_[0].mcur].p;
+    for_rounds(B_, [&](const StageRound &r) { motion_out(r, m, out); });
 }
 
 // get_motion's reverse into level 0's current buffer, through the same
@@ -467,15 +465,8 @@ void Batch::get_motion(double *out) {
 void Batch::set_motion(const double *in) {
     DeviceScope scope;
     ensure_device();
-    BLevel &L0 = lv_[0];
-    for (const StageRound &r : stage_rounds(B_, stage_pairs_, L0.stride, dimx_, dimy_)) {
-        OF2D_HIP(hipMemcpyAsync(d_stage_, in + r.motion,
-                                sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
-                                hipMemcpyHostToDevice, st_));
-        launch_planar_to_motion(d_stage_, r.nk, dimx_, dimy_, L0.motion[L0.mcur].p + r.field,
-                                L0.stride, L0.P, st_);
-        OF2D_HIP(hipStreamSynchronize(st_));  // the staging buffer is reused
-    }
+    float2 *m = lv_[0].motion[lv_[0].mcur].p;
+    for_rounds(B_, [&](const StageRound &r) { motion_in(r, in, m); });
     motion_in_place();
 }
 
@@ -519,20 +510,13 @@ void Batch::warp(const double *in, double *out) {
     DeviceScope scope;
     ensure_device();
     BLevel &L0 = lv_[0];
-    const size_t n0 = (size_t)dimx_ * dimy_;
-    for (int k0 = 0; k0 < B_; k0 += (int)stage_pairs_) {
-        const int nk = std::min<int>((int)stage_pairs_, B_ - k0);
-        const long off = k0 * L0.stride;
-        OF2D_HIP(hipMemcpyAsync(d_stage_, in + k0 * n0, nk * n0 * sizeof(double),
-                                hipMemcpyHostToDevice, st_));
-        launch_d2f(d_stage_, nk, dimx_, dimy_, L0.Iaux.p + off, L0.stride, L0.P, st_);
-        launch_warp(L0.Iaux.p + off, L0.motion[L0.mcur].p + off, L0.It.p + off, L0.stride, dimx_,
-                    dimy_, L0.P, nk, nullptr, st_);
-        launch_f2d(L0.It.p + off, L0.stride, L0.P, dimx_, dimy_, d_stage_, nk, st_);
-        OF2D_HIP(hipMemcpyAsync(out + k0 * n0, d_stage_, nk * n0 * sizeof(double),
-                                hipMemcpyDeviceToHost, st_));
-        OF2D_HIP(hipStreamSynchronize(st_));
-    }
+    // upload, warp and download of a round's pairs before the next round
+    for_rounds(B_, [&](const StageRound &r) {
+        images_in(r, in, L0.Iaux.p);
+        launch_warp(L0.Iaux.p + r.field, L0.motion[L0.mcur].p + r.field, L0.It.p + r.field,
+                    L0.stride, dimx_, dimy_, L0.P, r.nk, nullptr, st_);
+        images_out(r, L0.It.p, out);
+    });
 }
 
 void Batch::get_motion_device(const DArrayView &out, hipStream_t user) {
@@ -602,16 +586,8 @@ void Batch::jacobian(double *jac, double *stats) {
     if (const char *why = jacobian_refusal(dimx_, dimy_)) throw std::invalid_argument(why);
     DeviceScope scope;
     ensure_device();
-    BLevel &L0 = lv_[0];
     run_jacobian(jac != nullptr);
-    if (jac)
-        for (const StageRound &r : stage_rounds(B_, stage_pairs_, L0.stride, dimx_, dimy_)) {
-            launch_f2d(L0.It.p + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_, r.nk, st_);
-            OF2D_HIP(hipMemcpyAsync(jac + r.image, d_stage_,
-                                    sizeof(double) * r.nk * (size_t)dimx_ * dimy_,
-                                    hipMemcpyDeviceToHost, st_));
-            OF2D_HIP(hipStreamSynchronize(st_));  // the staging buffer is reused
-        }
+    if (jac) for_rounds(B_, [&](const StageRound &r) { images_out(r, lv_[0].It.p, jac); });
     fetch_words(stats, 5);
 }
 
@@ -651,17 +627,8 @@ void Batch::invert_motion(int max_iter, double tol, double *out, double *info) {
         throw std::invalid_argument(why);
     DeviceScope scope;
     ensure_device();
-    BLevel &L0 = lv_[0];
     run_invert(max_iter, tol);
-    if (out)
-        for (const StageRound &r : stage_rounds(B_, stage_pairs_, L0.stride, dimx_, dimy_)) {
-            launch_motion_to_planar(L0.est[0].p + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_,
-                                    r.nk, st_);
-            OF2D_HIP(hipMemcpyAsync(out + r.motion, d_stage_,
-                                    sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
-                                    hipMemcpyDeviceToHost, st_));
-            OF2D_HIP(hipStreamSynchronize(st_));
-        }
+    if (out) for_rounds(B_, [&](const StageRound &r) { motion_out(r, lv_[0].est[0].p, out); });
     fetch_words(info, 4);
 }
 
@@ -711,13 +678,7 @@ void Batch::quality(const double *ref, bool shared_ref, const double *mov, doubl
         const double *src = which ? mov : ref;
         float *dst = which ? L0.Iaux.p : qref_.p;
         const int npairs = (!which && shared_ref) ? 1 : B_;
-        for (const StageRound &r : stage_rounds(npairs, stage_pairs_, L0.stride, dimx_, dimy_)) {
-            OF2D_HIP(hipMemcpyAsync(d_stage_, src + r.image,
-                                    sizeof(double) * r.nk * (size_t)dimx_ * dimy_,
-                                    hipMemcpyHostToDevice, st_));
-            launch_d2f(d_stage_, r.nk, dimx_, dimy_, dst + r.field, L0.stride, L0.P, st_);
-            OF2D_HIP(hipStreamSynchronize(st_));  // the staging buffer is reused
-        }
+        for_rounds(npairs, [&](const StageRound &r) { images_in(r, src, dst); });
     }
     run_quality(shared_ref);
     fetch_words(out, 4);

@@ -23,9 +23,7 @@
 // compiled with -ffp-contract=off and IEEE division: the iterates are
 // bit-identical to the one-pair path's and the oracle's.
 //
-// Convergence is the HS loop's (batch_kernels.hip): fp64 sums of logger_mag in
-// a fixed order, logger_error's float arithmetic and the reference's break by
-// the workgroup's first thread: the "logger_fp64" semantics.
+// Entry, convergence, break and exit are the loop frame's (batch_loop.h).
 //
 // A zero denominator (coord2d.h:95-100) sets the pair's kStatusDivZero; the
 // workgroup learns it at the barrier after stage 2 and leaves the loop.
@@ -56,19 +54,18 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
     constexpr int T = 64 * WAVES;
     const long pair = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int *iters = a.iters + pair * a.nloops + a.loop;
-    if (a.status[pair] & kStatusDivZero) {  // an earlier loop's: nothing runs
-        if (tid == 0) *iters = 0;
-        return;
-    }
+    PairSlots ps;
+    if (!loop_entry<CONV>(a, pair, tid, ps)) return;
     float2 *u0 = a.u0 + pair * a.stride, *u1 = a.u1 + pair * a.stride;
     const float *__restrict__ Iref = a.Iref + pair * a.sref;
     const float *__restrict__ Iaux = a.Iaux + pair * a.stride;
     float *W = a.W + pair * a.stride;
     float2 *C = a.corr + pair * a.stride, *M = a.mid + pair * a.stride;
-    float *errs = CONV ? a.errs + (pair * a.nloops + a.loop) * (long)a.maxn : nullptr;
     const int dx = a.dx, dy = a.dy, P = a.P, npx = dx * dy, kw = a.kw;
-    const float nf = (float)(double)npx;  // logger_error: (float)npx
+    // f(idx, i, j, o) for the thread's pixels (batch_loop.h)
+    const auto pixels = [&](auto &&f) __attribute__((always_inline)) {
+        for_pixels<T>(tid, npx, dx, P, f);
+    };
     __shared__ int s_stop, s_bad;
     if (tid == 0) s_stop = s_bad = 0;  // published by the barrier after stage 1
     int n = 0;
@@ -77,18 +74,14 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
         const float2 *src = (it & 1) ? u1 : u0;
         float2 *dst = (it & 1) ? u0 : u1;
         // 1. the moving image by the iterate
-        for (int idx = tid; idx < npx; idx += T) {
-            const int j = idx / dx, i = idx - j * dx;
-            const long o = (long)j * P + i;
+        pixels([&](int, int i, int j, long o) {
             W[o] = warp_px(Iaux, src[o], Iaux[o], i, j, dx, dy, P);
-        }
+        });
         __syncthreads();
         // 2. the correction (demons_corr_px, batch_demons_px.h)
-        for (int idx = tid; idx < npx; idx += T) {
-            const int j = idx / dx, i = idx - j * dx;
-            const long o = (long)j * P + i;
+        pixels([&](int, int i, int j, long o) {
             C[o] = demons_corr_px(W, Iref[o], o, i, j, dx, dy, P, a.sigma_isq, a.sigma_xsq, bad);
-        }
+        });
         if (bad) s_bad = 1;
         __syncthreads();
         if (s_bad) break;  // block-uniform: the reference throws here
@@ -97,14 +90,12 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
             // 3. the smoothed correction into mid, and Motion::maxabs
             // (maxabs_fold, batch_demons_px.h)
             float mx = 0.0f;
-            for (int idx = tid; idx < npx; idx += T) {
-                const int j = idx / dx, i = idx - j * dx;
-                const long o = (long)j * P + i;
+            pixels([&](int, int i, int j, long o) {
                 float2 c;
                 if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
                 M[o] = c;
                 mx = maxabs_fold(mx, c);
-            }
+            });
             // 3a. the block's maximum (a thread without a pixel brings 0; the
             // barrier inside is stage 3's) and the squaring count
             // (exp_squarings, batch_demons_px.h)
@@ -117,14 +108,12 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
                 // 3b. Field<vector2d>::operator*=((float)std::pow(2, -nsq)),
                 // exact; the thread's own pixels, in place
                 const float sc = ldexpf(1.0f, -nsq);
-                for (int idx = tid; idx < npx; idx += T) {
-                    const int j = idx / dx, i = idx - j * dx;
-                    const long o = (long)j * P + i;
+                pixels([&](int, int, int, long o) {
                     float2 v = M[o];
                     v.x *= sc;
                     v.y *= sc;
                     M[o] = v;
-                }
+                });
                 __syncthreads();
                 // 3c. u <- u o u (Motion.cpp:268-272: Mtmp = *this;
                 // this->accumulate(*Mtmp)).  accumulate_px(f, f[o], f[o], ...)
@@ -136,12 +125,10 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
                 // free once stage 3 has read it)
                 float2 *from = M, *to = C;
                 for (int q = 0; q < nsq; ++q) {
-                    for (int idx = tid; idx < npx; idx += T) {
-                        const int j = idx / dx, i = idx - j * dx;
-                        const long o = (long)j * P + i;
+                    pixels([&](int, int i, int j, long o) {
                         const float2 c = from[o];
                         to[o] = accumulate_px(from, c, c, i, j, dx, dy, P);
-                    }
+                    });
                     __syncthreads();
                     float2 *t = from;
                     from = to;
@@ -152,16 +139,12 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
             // 4. motion->accumulate(*correspondence): E is read at the thread's
             // own pixel only and the gather is from src, so the write is in
             // place when E is mid
-            for (int idx = tid; idx < npx; idx += T) {
-                const int j = idx / dx, i = idx - j * dx;
-                const long o = (long)j * P + i;
+            pixels([&](int, int i, int j, long o) {
                 M[o] = accumulate_px(src, E[o], src[o], i, j, dx, dy, P);
-            }
+            });
         } else {
             // 3 + 4. the smoothed correction and the motion update
-            for (int idx = tid; idx < npx; idx += T) {
-                const int j = idx / dx, i = idx - j * dx;
-                const long o = (long)j * P + i;
+            pixels([&](int, int i, int j, long o) {
                 float2 c;
                 if (!conv_direct<KW>(C, a.fluid, kw, i, j, dx, dy, P, c)) c = C[o];
                 const float2 own = src[o];
@@ -171,39 +154,25 @@ __global__ __launch_bounds__(64 * WAVES) void demons_loop_kernel(DemonsLoopArgs 
                 else if (a.mode == 1)
                     m = make_float2(own.x + c.x, own.y + c.y);  // Field::operator+=
                 M[o] = m;
-            }
+            });
         }
         __syncthreads();
         // 5. the smoothed motion into the other buffer, and the Logger's terms
         double v[2] = {0.0, 0.0};
-        for (int idx = tid; idx < npx; idx += T) {
-            const int j = idx / dx, i = idx - j * dx;
-            const long o = (long)j * P + i;
+        pixels([&](int, int i, int j, long o) {
             float2 nw;
             if (!conv_direct<KW>(M, a.diff, kw, i, j, dx, dy, P, nw)) nw = M[o];
             if constexpr (CONV) logger_add(nw, src[o], v[0], v[1]);
             dst[o] = nw;
-        }
+        });
         n = it + 1;
         if constexpr (CONV) {
             block_sums<2, WAVES>(v, wave, lane);
-            if (tid == 0) {
-                // logger_error (registration.cpp) on the device
-                const float prevnorm = (float)v[1] / nf;
-                const float diffnorm = (float)v[0] / nf;
-                const float err = prevnorm == 0 ? 0.0f : diffnorm / prevnorm;
-                errs[it] = err;
-                s_stop = (err < 0.001f && it > 1) ? 1 : 0;
-            }
+            if (tid == 0) s_stop = loop_decide(v[0], v[1], ps, it);
         }
-        // the iterate is complete (and the decision published) for every thread
-        __syncthreads();
-        if constexpr (CONV) {
-            if (s_stop) break;
-        }
+        if (loop_break<CONV>(s_stop)) break;
     }
-    if (tid == 0) *iters = n;
-    if (__any(bad) && lane == 0) atomicOr(a.status + pair, kStatusDivZero);
+    loop_exit(a, pair, tid, lane, ps, n, bad);
 }
 
 }  // namespace

@@ -26,9 +26,9 @@
 // each squaring accumulate_px(plane, c, c, ...) into registers, then barrier,
 // store, barrier (3c; the last one's store is step 4's), then m (4).
 // __syncthreads() is the only synchronisation; no workgroup waits for another.
-// iters, errs, the divide-by-zero exit and the status word are
-// demons_loop_kernel's, and 1024 threads run the Logger sums in its order, so
-// iterates, errors and counts equal that kernel's bit for bit.
+// Entry, convergence, break and exit are the loop frame's (batch_loop.h) and
+// the divide-by-zero exit after stage 2 is demons_loop_kernel's, so iterates,
+// errors and counts equal that kernel's bit for bit.
 #include <utility>
 
 #include "batch_demons_px.h"
@@ -68,18 +68,13 @@ __global__ __launch_bounds__(kLoopThreads) void demons_lds_kernel(DemonsLoopArgs
     __shared__ int s_stop, s_bad;
     const long pair = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int *iters = a.iters + pair * a.nloops + a.loop;
-    if (a.status[pair] & kStatusDivZero) {  // an earlier loop's: nothing runs
-        if (tid == 0) *iters = 0;
-        return;
-    }
+    PairSlots ps;
+    if (!loop_entry<CONV>(a, pair, tid, ps)) return;
     float2 *u0 = a.u0 + pair * a.stride, *u1 = a.u1 + pair * a.stride;
     const float *__restrict__ Iref = a.Iref + pair * a.sref;
     const float *__restrict__ Iaux = a.Iaux + pair * a.stride;
     float *W = a.W + pair * a.stride;
-    float *errs = CONV ? a.errs + (pair * a.nloops + a.loop) * (long)a.maxn : nullptr;
     const int dx = a.dx, dy = a.dy, P = a.P, npx = dx * dy, kw = a.kw;
-    const float nf = (float)(double)npx;  // logger_error: (float)npx
     if (tid == 0) s_stop = s_bad = 0;  // published by the barrier after stage 1
     for (int c = tid; c <= dx; c += T) s_f[npx + c] = make_float2(0.0f, 0.0f);
     int n = 0;
@@ -221,23 +216,11 @@ __global__ __launch_bounds__(kLoopThreads) void demons_lds_kernel(DemonsLoopArgs
         n = it + 1;
         if constexpr (CONV) {
             block_sums<2, kLoopWaves>(v, wave, lane);
-            if (tid == 0) {
-                // logger_error (registration.cpp) on the device
-                const float prevnorm = (float)v[1] / nf;
-                const float diffnorm = (float)v[0] / nf;
-                const float err = prevnorm == 0 ? 0.0f : diffnorm / prevnorm;
-                errs[it] = err;
-                s_stop = (err < 0.001f && it > 1) ? 1 : 0;
-            }
+            if (tid == 0) s_stop = loop_decide(v[0], v[1], ps, it);
         }
-        // the iterate is complete (and the decision published) for every thread
-        __syncthreads();
-        if constexpr (CONV) {
-            if (s_stop) break;
-        }
+        if (loop_break<CONV>(s_stop)) break;
     }
-    if (tid == 0) *iters = n;
-    if (__any(bad) && lane == 0) atomicOr(a.status + pair, kStatusDivZero);
+    loop_exit(a, pair, tid, lane, ps, n, bad);
 }
 
 template <int PPT, bool CONV, int KW, bool EXP>
@@ -302,13 +285,11 @@ void launch_demons_lds(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st
     if (!conv_lds_fits(a.dx, a.dy))
         throw std::invalid_argument("launch_demons_lds: the level does not fit");
     const size_t lds = conv_lds_bytes(a.dx, a.dy);
-    const int ppt = ((long)a.dx * a.dy + kLoopThreads - 1) / kLoopThreads;
-    if (ppt <= 1)
-        launch_ppt<1>(a, B, conv, lds, st);
-    else if (ppt <= 4)
-        launch_ppt<4>(a, B, conv, lds, st);
-    else
-        launch_ppt<kConvLdsMaxPpt>(a, B, conv, lds, st);
+    switch (conv_lds_ppt(a.dx, a.dy)) {
+        case 1: launch_ppt<1>(a, B, conv, lds, st); break;
+        case 4: launch_ppt<4>(a, B, conv, lds, st); break;
+        default: launch_ppt<kConvLdsMaxPpt>(a, B, conv, lds, st); break;
+    }
     OF2D_HIP(hipGetLastError());
 }
 

@@ -9,16 +9,7 @@
 // arithmetic is hs::update_px and the quasi-Laplacian rule of hs_jacobi_impl.h
 // (q = 0 on the border), compiled with -ffp-contract=off and IEEE division:
 // the iterates are bit-identical to the one-pair kernels' and the oracle's.
-//
-// Convergence: after each iteration the workgroup sums logger_mag of
-// (u' - u) and of u over the pair's pixels in fp64, in a fixed order (thread t
-// adds pixels t, t + T, ... in ascending index, then block_sums), and its first
-// thread forms the error with logger_error's float arithmetic and applies the
-// reference's break (err < 0.001f && iteration > 1,
-// ImageRegistrationOpticalFlow.cpp:131-134).  These are fp64 sums, the
-// "logger_fp64" semantics of the one-pair path, not the reference's float
-// running sum (Motion::norm): an error can differ from the reference's in its
-// last bits, and a break that hangs on them can fall one iteration apart.
+// Entry, convergence, break and exit are the loop frame's (batch_loop.h).
 //
 // The passes around the loop are the per-pixel bodies of field_kernels.hip
 // (field_px.h, accumulate_px) with the pair as grid dimension z.
@@ -51,17 +42,12 @@ __global__ __launch_bounds__(64 * WAVES) void hs_loop_kernel(LoopArgs a) {
     constexpr int T = 64 * WAVES;
     const long pair = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int *iters = a.iters + pair * a.nloops + a.loop;
-    if (a.status[pair] & kStatusDivZero) {  // an earlier loop's: nothing runs
-        if (tid == 0) *iters = 0;
-        return;
-    }
+    PairSlots ps;
+    if (!loop_entry<CONV>(a, pair, tid, ps)) return;
     float2 *u0 = a.u0 + pair * a.stride, *u1 = a.u1 + pair * a.stride;
     const float2 *__restrict__ dI = a.dI + pair * a.stride;
     const float *__restrict__ It = a.It + pair * a.stride;
-    float *errs = CONV ? a.errs + (pair * a.nloops + a.loop) * (long)a.maxn : nullptr;
     const int dx = a.dx, dy = a.dy, P = a.P, npx = dx * dy;
-    const float nf = (float)(double)npx;  // logger_error: (float)npx
     __shared__ int s_stop;
     unsigned bad = 0;
     int n = 0;
@@ -69,9 +55,7 @@ __global__ __launch_bounds__(64 * WAVES) void hs_loop_kernel(LoopArgs a) {
         const float2 *src = (it & 1) ? u1 : u0;
         float2 *dst = (it & 1) ? u0 : u1;
         double v[2] = {0.0, 0.0};
-        for (int idx = tid; idx < npx; idx += T) {
-            const int j = idx / dx, i = idx - j * dx;
-            const long o = (long)j * P + i;
+        for_pixels<T>(tid, npx, dx, P, [&](int, int i, int j, long o) {
             // the neighbours of a border pixel lie in the pitch padding or a
             // ghost j-line of the pair's own field; q is zeroed there
             const float2 l = src[o - 1], r = src[o + 1], um = src[o - P], up = src[o + P];
@@ -84,28 +68,15 @@ __global__ __launch_bounds__(64 * WAVES) void hs_loop_kernel(LoopArgs a) {
             const float2 nw = hs::update_px(q, g.x, g.y, It[o], a.alphasq, bad);
             if constexpr (CONV) logger_add(nw, src[o], v[0], v[1]);
             dst[o] = nw;
-        }
+        });
         n = it + 1;
         if constexpr (CONV) {
             block_sums<2, WAVES>(v, wave, lane);
-            if (tid == 0) {
-                // logger_error (registration.cpp) on the device
-                const float prevnorm = (float)v[1] / nf;
-                const float diffnorm = (float)v[0] / nf;
-                const float err = prevnorm == 0 ? 0.0f : diffnorm / prevnorm;
-                errs[it] = err;
-                s_stop = (err < 0.001f && it > 1) ? 1 : 0;
-            }
+            if (tid == 0) s_stop = loop_decide(v[0], v[1], ps, it);
         }
-        // the iterate is complete (and the decision published) for every thread
-        __syncthreads();
-        if constexpr (CONV) {
-            if (s_stop) break;
-        }
+        if (loop_break<CONV>(s_stop)) break;
     }
-    if (tid == 0) *iters = n;
-    // coord2d.h:95-100: a zero denominator on an image pixel, per pair
-    if (__any(bad) && lane == 0) atomicOr(a.status + pair, kStatusDivZero);
+    loop_exit(a, pair, tid, lane, ps, n, (int)bad);
 }
 
 void launch_hs_loop(const LoopArgs &a, int B, bool conv, hipStream_t st) {

@@ -1,6 +1,7 @@
 // batch_plan.h — the host arithmetic of the batch's boundary copies and of its
 // analysis calls (batch.cpp, capi.cpp) that needs no device: the staging
-// rounds, a pair's offsets in them, and the argument checks.  Plain C++ (no
+// rounds, a pair's offsets in them, the argument checks, and the fit rules of
+// the loop's on-CU placements with the instantiation a level runs.  Plain C++ (no
 // HIP header), so that tests/host/batch_plan_test.cpp exercises it on the CPU,
 // with sanitizers too.
 #pragma once
@@ -46,6 +47,65 @@ inline std::vector<StageRound> stage_rounds(int npairs, size_t stage_pairs, long
         v.push_back(r);
     }
     return v;
+}
+
+// ---- the loop's workgroup and its two on-CU placements (DESIGN.md §4.6.5,
+// §4.6.6).  waves of a pair's workgroup in the loop kernels (1024 threads at
+// every level)
+constexpr int kLoopWaves = 16;
+constexpr int kLoopThreads = 64 * kLoopWaves;
+// A level runs on the CU when one predicate on its size holds: its float2
+// elements in LDS (8 bytes each; the kernels assert it) plus
+// kResidentLdsReserve bytes for the kernel's static LDS (block_sums' scratch
+// and the flags) fit the CU's 160 KiB, and a thread of the 1024 owns at most
+// as many pixels as the largest instantiation holds.  Batch::estimate chooses
+// the kernel by it and Batch::info reports it (placement 1).
+constexpr int kResidentLdsBudget = 160 * 1024;
+constexpr int kResidentLdsReserve = 1024;
+constexpr size_t kLdsElementBytes = 8;
+inline bool on_cu_fits(int dx, int dy, size_t lds_bytes, int max_ppt) {
+    return dx >= 1 && dy >= 1 && lds_bytes + kResidentLdsReserve <= (size_t)kResidentLdsBudget &&
+           (long)dx * dy <= (long)max_ppt * kLoopThreads;
+}
+// pixels of a thread that owns the most
+inline int loop_ppt(int dx, int dy) {
+    return (int)(((long)dx * dy + kLoopThreads - 1) / kLoopThreads);
+}
+
+// option "resident": the iterate's one LDS copy, (dx + 2) x (dy + 2) with its
+// ghost ring; dI, It and the new values of 16 pixels are 80 of the 128
+// registers a lane of such a workgroup may have.  Every level up to 128 x 128
+// fits (135 200 B, 16 pixels); 150 x 120 fails on the pixels and 2 x 6000 on
+// the bytes
+constexpr int kResidentMaxPpt = 16;
+inline size_t resident_lds_bytes(int dx, int dy) {
+    return (size_t)(dx + 2) * (size_t)(dy + 2) * kLdsElementBytes;
+}
+inline bool resident_fits(int dx, int dy) {
+    return on_cu_fits(dx, dy, resident_lds_bytes(dx, dy), kResidentMaxPpt);
+}
+// the instantiation of hs_resident_kernel a fitting level runs
+inline int resident_ppt(int dx, int dy) {
+    const int p = loop_ppt(dx, dy);
+    return p <= 1 ? 1 : p <= 2 ? 2 : p <= 4 ? 4 : p <= 8 ? 8 : kResidentMaxPpt;
+}
+
+// option "conv_lds": the dense plane, dx * dy pixels at pitch dx without ghost
+// lines plus dx + 1 zeroed elements that accumulate_px's unconditional b[1],
+// b[P], b[P + 1] loads reach from the last pixels; the new values of 16 pixels
+// are 32 registers.  Every level up to 128 x 128 fits (132 104 B); 129 x 128
+// fails on the pixels
+constexpr int kConvLdsMaxPpt = 16;
+inline size_t conv_lds_bytes(int dx, int dy) {
+    return ((size_t)dx * (size_t)dy + (size_t)dx + 1) * kLdsElementBytes;
+}
+inline bool conv_lds_fits(int dx, int dy) {
+    return on_cu_fits(dx, dy, conv_lds_bytes(dx, dy), kConvLdsMaxPpt);
+}
+// the instantiation of demons_lds_kernel a fitting level runs
+inline int conv_lds_ppt(int dx, int dy) {
+    const int p = loop_ppt(dx, dy);
+    return p <= 1 ? 1 : p <= 4 ? 4 : kConvLdsMaxPpt;
 }
 
 // nullptr or why the call is refused (the one-pair entries' wording)

@@ -20,9 +20,8 @@
 //
 // The arithmetic is hs_loop_kernel's, expression for expression (the
 // quasi-Laplacian in its operand order, hs::update_px, -ffp-contract=off, IEEE
-// division), and so are the fp64 Logger sums (each thread's pixels ascending,
-// then block_sums over the 16 waves), logger_error's float arithmetic on
-// thread 0 and the break: iterates, errors and iteration counts equal
+// division), and entry, Logger sums, decision, break and exit are the loop
+// frame's (batch_loop.h): iterates, errors and iteration counts equal
 // placement 0's bit for bit.  At the end the last iterate goes to the global
 // buffer u[iterations & 1], pixels only, where launch_accumulate expects it.
 #include "of2d_batch.h"
@@ -63,18 +62,13 @@ __global__ __launch_bounds__(kLoopThreads) void hs_resident_kernel(LoopArgs a) {
     __shared__ int s_stop;
     const long pair = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int *iters = a.iters + pair * a.nloops + a.loop;
-    if (a.status[pair] & kStatusDivZero) {  // an earlier loop's: nothing runs
-        if (tid == 0) *iters = 0;
-        return;
-    }
+    PairSlots ps;
+    if (!loop_entry<CONV>(a, pair, tid, ps)) return;
     float2 *u0 = a.u0 + pair * a.stride, *u1 = a.u1 + pair * a.stride;
     const float2 *__restrict__ dI = a.dI + pair * a.stride;
     const float *__restrict__ It = a.It + pair * a.stride;
-    float *errs = CONV ? a.errs + (pair * a.nloops + a.loop) * (long)a.maxn : nullptr;
     const int dx = a.dx, dy = a.dy, P = a.P, npx = dx * dy;
     const int W = dx + 2, nlds = W * (dy + 2);
-    const float nf = (float)(double)npx;  // logger_error: (float)npx
 
     for (int c = tid; c < nlds; c += T) s_u[c] = make_float2(0.0f, 0.0f);
     __syncthreads();
@@ -133,21 +127,11 @@ __global__ __launch_bounds__(kLoopThreads) void hs_resident_kernel(LoopArgs a) {
             const unsigned c = pixel_word(pk[k >> 1], k) & (kBorderBit - 1);
             if (c) s_u[c] = nw[k];
         }
+        // the decision follows the stores: the order §4.6.5's registers hold for
         if constexpr (CONV) {
-            if (tid == 0) {
-                // logger_error (registration.cpp) on the device
-                const float prevnorm = (float)v[1] / nf;
-                const float diffnorm = (float)v[0] / nf;
-                const float err = prevnorm == 0 ? 0.0f : diffnorm / prevnorm;
-                errs[it] = err;
-                s_stop = (err < 0.001f && it > 1) ? 1 : 0;
-            }
+            if (tid == 0) s_stop = loop_decide(v[0], v[1], ps, it);
         }
-        // the iterate is complete (and the decision published) for every thread
-        __syncthreads();
-        if constexpr (CONV) {
-            if (s_stop) break;
-        }
+        if (loop_break<CONV>(s_stop)) break;
     }
     // the last iterate to the buffer launch_accumulate reads from the count
     float2 *dst = (n & 1) ? u1 : u0;
@@ -163,9 +147,7 @@ __global__ __launch_bounds__(kLoopThreads) void hs_resident_kernel(LoopArgs a) {
             dst[(long)j * P + i] = s_u[(j + 1) * W + (i + 1)];
         }
     }
-    if (tid == 0) *iters = n;
-    // coord2d.h:95-100: a zero denominator on an image pixel, per pair
-    if (__any(bad) && lane == 0) atomicOr(a.status + pair, kStatusDivZero);
+    loop_exit(a, pair, tid, lane, ps, n, (int)bad);
 }
 
 namespace {
@@ -209,17 +191,13 @@ void launch_hs_resident(const LoopArgs &a, int B, bool conv, hipStream_t st) {
     if (!resident_fits(a.dx, a.dy))
         throw std::invalid_argument("launch_hs_resident: the level does not fit");
     const size_t lds = resident_lds_bytes(a.dx, a.dy);
-    const int ppt = ((long)a.dx * a.dy + kLoopThreads - 1) / kLoopThreads;
-    if (ppt <= 1)
-        launch_ppt<1>(a, B, conv, lds, st);
-    else if (ppt <= 2)
-        launch_ppt<2>(a, B, conv, lds, st);
-    else if (ppt <= 4)
-        launch_ppt<4>(a, B, conv, lds, st);
-    else if (ppt <= 8)
-        launch_ppt<8>(a, B, conv, lds, st);
-    else
-        launch_ppt<kResidentMaxPpt>(a, B, conv, lds, st);
+    switch (resident_ppt(a.dx, a.dy)) {
+        case 1: launch_ppt<1>(a, B, conv, lds, st); break;
+        case 2: launch_ppt<2>(a, B, conv, lds, st); break;
+        case 4: launch_ppt<4>(a, B, conv, lds, st); break;
+        case 8: launch_ppt<8>(a, B, conv, lds, st); break;
+        default: launch_ppt<kResidentMaxPpt>(a, B, conv, lds, st); break;
+    }
     OF2D_HIP(hipGetLastError());
 }
 

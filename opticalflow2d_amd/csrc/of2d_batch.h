@@ -1,7 +1,9 @@
 // of2d_batch.h — B independent Horn-Schunck or Thirion's Demons registrations
 // of one size in one call, and the deformation analysis of their motions
-// (batch.cpp, batch_kernels.hip, batch_demons_kernels.hip,
-// batch_analysis_kernels.hip).
+// (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
+// batch_demons_kernels.hip, batch_demons_lds_kernels.hip,
+// batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the host
+// arithmetic: batch_plan.h).
 //
 // Layout: the B fields of a pyramid level live in one allocation, pair k at
 // k * stride elements, each laid out exactly as a Field<T> (of2d_host.h): the
@@ -21,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "batch_loop.h"
 #include "batch_plan.h"
 #include "of2d_device.h"
 
@@ -33,22 +36,13 @@ constexpr int kMaxPairs = 65535;    // the pair is grid dimension z of the passe
 inline long pair_stride(int dimx, int dimy) {
     return (long)(dimy + 2) * pitch_for(dimx) + kPitchAlign;
 }
-// waves of a pair's workgroup in the loop kernel (1024 threads at every level)
-constexpr int kLoopWaves = 16;
-constexpr int kLoopThreads = 64 * kLoopWaves;
+static_assert(sizeof(float2) == kLdsElementBytes, "batch_plan.h counts LDS in float2 elements");
 
-struct LoopArgs {
-    float2 *u0, *u1;      // the iterate's two buffers; iteration t reads u[t & 1]
+// the common arguments (batch_loop.h) and the Horn-Schunck loop's own
+struct LoopArgs : LoopCommon {
     const float2 *dI;
     const float *It;
-    long stride;
-    int dx, dy, P, niter;
     float alphasq;
-    unsigned *status;     // [B]
-    int *iters;           // [B][nloops]: iterations run by this loop
-    int nloops, loop;
-    float *errs;          // [B][nloops][maxn] (convergence on)
-    int maxn;
 };
 // conv: Logger sums, errors and the reference's break (fp64 sums in a fixed
 // order: the logger_fp64 semantics); otherwise exactly niter iterations
@@ -56,27 +50,8 @@ void launch_hs_loop(const LoopArgs &a, int B, bool conv, hipStream_t st);
 
 // ---- option "resident" (batch_resident_kernels.hip): the
 // same loop with the pair's iterate in LDS and dI, It in registers across the
-// iterations.  The fit rule, one predicate on the level's size: the iterate's
-// one LDS copy, (dx + 2) x (dy + 2) float2 with its ghost ring, plus
-// kResidentLdsReserve bytes for the kernel's static LDS (block_sums' scratch
-// and the break flag) fits the CU's 160 KiB, and a thread of the 1024 owns at
-// most kResidentMaxPpt pixels (the largest instantiation; dI, It and the new
-// values of 16 pixels are 80 of the 128 registers a lane of such a workgroup
-// may have).  Every level up to 128 x 128 fits (135 200 B, 16 pixels); 150 x
-// 120 fails on the pixels and 2 x 6000 on the bytes. Batch::estimate chooses
-// the kernel by it and Batch::info reports it (placement 1).
-constexpr int kResidentLdsBudget = 160 * 1024;
-constexpr int kResidentLdsReserve = 1024;
-constexpr int kResidentMaxPpt = 16;
-inline size_t resident_lds_bytes(int dx, int dy) {
-    return (size_t)(dx + 2) * (size_t)(dy + 2) * sizeof(float2);
-}
-inline bool resident_fits(int dx, int dy) {
-    return dx >= 1 && dy >= 1 &&
-           resident_lds_bytes(dx, dy) + kResidentLdsReserve <= (size_t)kResidentLdsBudget &&
-           (long)dx * dy <= (long)kResidentMaxPpt * kLoopThreads;
-}
-// once per device before the first launch: admits the dynamic LDS above the
+// iterations, at the levels that resident_fits (batch_plan.h).
+// Once per device before the first launch: admits the dynamic LDS above the
 // default limit for every instantiation; false when the runtime refuses (the
 // caller then runs launch_hs_loop at every level)
 bool resident_prepare();
@@ -97,15 +72,12 @@ struct DemonsTable {
 // DemonsThirions::get_update, staged through the pair's slices of W, corr and
 // mid with a barrier after each stage; with `diffeomorphic` the loop of
 // DemonsDiffeomorphic::get_update
-struct DemonsLoopArgs {
-    float2 *u0, *u1;      // the iterate's two buffers; iteration t reads u[t & 1]
+struct DemonsLoopArgs : LoopCommon {
     const float *Iref;
     long sref;            // Iref's pair stride, 0 for a shared reference
     const float *Iaux;    // Imov warped by the level's motion
     float *W;             // scratch: Iaux warped by the iterate
     float2 *corr, *mid;   // scratch: the correction; the motion before the last smoothing
-    long stride;
-    int dx, dy, P, niter;
     float sigma_isq, sigma_xsq;  // Demons.cpp:48-49
     DemonsTable fluid, diff;
     int kw;
@@ -113,11 +85,6 @@ struct DemonsLoopArgs {
     // option "diffeomorphic": Motion::exp of the smoothed correction before the
     // update (DemonsDiffeomorphic::get_update); mode is 0
     int diffeomorphic;
-    unsigned *status;
-    int *iters;
-    int nloops, loop;
-    float *errs;
-    int maxn;
 };
 // conv as launch_hs_loop's
 void launch_demons_loop(const DemonsLoopArgs &a, int B, bool conv, hipStream_t st);
@@ -126,25 +93,8 @@ void launch_demons_loop(const DemonsLoopArgs &a, int B, bool conv, hipStream_t s
 // same loop with the field its two convolutions read (the correction, then the
 // motion before the last smoothing; with `diffeomorphic` every squaring of
 // exp() too) in one dense float2 plane in LDS instead of the corr and mid
-// slices.  The fit rule, one predicate on the level's size: the plane, dx * dy
-// pixels at pitch dx without ghost lines plus dx + 1 zeroed elements that
-// accumulate_px's unconditional b[1], b[P], b[P + 1] loads reach from the last
-// pixels, plus kResidentLdsReserve bytes for the kernel's static LDS fits the
-// CU's 160 KiB, and a thread of the 1024 owns at most kConvLdsMaxPpt pixels
-// (the largest instantiation: their new values are 32 registers).  Every level
-// up to 128 x 128 fits (132 104 B); 129 x 128 fails on the pixels.
-// Batch::estimate chooses the kernel by it and Batch::info reports it
-// (placement 1).
-constexpr int kConvLdsMaxPpt = 16;
-inline size_t conv_lds_bytes(int dx, int dy) {
-    return ((size_t)dx * (size_t)dy + (size_t)dx + 1) * sizeof(float2);
-}
-inline bool conv_lds_fits(int dx, int dy) {
-    return dx >= 1 && dy >= 1 &&
-           conv_lds_bytes(dx, dy) + kResidentLdsReserve <= (size_t)kResidentLdsBudget &&
-           (long)dx * dy <= (long)kConvLdsMaxPpt * kLoopThreads;
-}
-// as resident_prepare: false when the runtime refuses the dynamic LDS (the
+// slices, at the levels that conv_lds_fits (batch_plan.h).
+// As resident_prepare: false when the runtime refuses the dynamic LDS (the
 // caller then runs launch_demons_loop at every level)
 bool conv_lds_prepare();
 // a, conv: launch_demons_loop's (corr and mid are not used);
@@ -352,7 +302,29 @@ class Batch {
     void run_invert(int max_iter, double tol);
     void run_quality(bool shared_ref);
     void fetch_words(double *host, int per_pair);
-    DemonsLoopArgs demons_args(BLevel &L, int s, int loop) const;
+    // ---- the boundary copies through d_stage_: f(round) for the rounds that
+    // move npairs pairs (stage_rounds), each followed by a synchronise (the
+    // next round reuses the buffer); and what a round enqueues for a stack of
+    // images or planar motion fields on the host and pitched fields
+    template <class F>
+    void for_rounds(int npairs, F f) {
+        for (const StageRound &r : stage_rounds(npairs, stage_pairs_, lv_[0].stride, dimx_, dimy_)) {
+            f(r);
+            OF2D_HIP(hipStreamSynchronize(st_));
+        }
+    }
+    void images_in(const StageRound &r, const double *host, float *field);
+    void images_out(const StageRound &r, const float *field, double *host);
+    void motion_in(const StageRound &r, const double *host, float2 *field);
+    void motion_out(const StageRound &r, const float2 *field, double *host);
+    // loop `loop` of level s between its two events, by the kernel that reg_
+    // and placement_[s] name
+    void launch_loop(int s, int loop, bool conv);
+    // c and the Demons loop's own arguments at level L
+    DemonsLoopArgs demons_args(const LoopCommon &c, BLevel &L) const;
+    bool on_cu_fits(int s) const {
+        return reg_ == 3 ? conv_lds_fits(ldx_[s], ldy_[s]) : resident_fits(ldx_[s], ldy_[s]);
+    }
     int B_, dimx_, dimy_, nscales_, nrefine_, nloops_ = 0;
     std::vector<int> niter_, ldx_, ldy_;
     int reg_;
@@ -366,15 +338,13 @@ class Batch {
     bool fixed_ = false, shared_ = false, have_images_ = false;
     bool diffeo_ = false;  // option "diffeomorphic" (reg 3, Composition only)
     bool warm_ = false;    // option "warm_start": estimate() resets no motion
-    // option "resident" (reg 0): the levels that resident_fits run
-    // launch_hs_resident.  resident_ok_: resident_prepare's answer on home_,
-    // -1 before it is asked; placement_: per level, what the last estimate ran
-    bool resident_ = false;
-    int resident_ok_ = -1;
-    // option "conv_lds" (reg 3): the levels that conv_lds_fits run
-    // launch_demons_lds; conv_lds_ok_: conv_lds_prepare's answer, as above
-    bool conv_lds_ = false;
-    int conv_lds_ok_ = -1;
+    // option "resident" (reg 0) or "conv_lds" (reg 3), the one a handle of
+    // this kind admits: the levels that fit (on_cu_fits) run launch_hs_resident
+    // or launch_demons_lds.  on_cu_ok_: resident_prepare's or
+    // conv_lds_prepare's answer on home_, -1 before it is asked; placement_:
+    // per level, what the last estimate ran
+    bool on_cu_ = false;
+    int on_cu_ok_ = -1;
     std::vector<int> placement_;
     int device_ = -1, home_ = -1;
     bool ready_ = false;

@@ -1,6 +1,7 @@
 // Stand-alone check of opticalflow2d_amd/csrc/batch_plan.h (host only: no
-// device, no libof2d.so): the staging rounds of the batch's boundary copies and
-// the argument checks of its analysis calls.  The rounds are checked by
+// device, no libof2d.so): the staging rounds of the batch's boundary copies,
+// the argument checks of its analysis calls and the fit rules of the loop's
+// on-CU placements.  The rounds are checked by
 // simulating the copies on host buffers of exactly the sizes the driver
 // allocates, so an offset or a count that is off by one is an out-of-bounds
 // access for AddressSanitizer as well as a failed check.
@@ -148,10 +149,58 @@ static void test_refusals() {
           "max_iter before tol");
 }
 
+// The documented corners of the two on-CU fit rules,
+// the byte counts as the document states them, and the instantiation a level
+// runs: a compiled one that holds the thread's pixels
+static void test_fit_rules() {
+    CHECK(batch::kLoopThreads == 1024, "a pair's workgroup has 1024 threads");
+    // resident: (dx + 2) x (dy + 2) elements of 8 bytes; 1 KiB reserve of 160 KiB
+    CHECK(batch::resident_fits(128, 128), "resident: 128 x 128 fits");
+    CHECK(batch::resident_lds_bytes(128, 128) == 135200, "resident: 128 x 128 is 135 200 B");
+    CHECK(!batch::resident_fits(129, 128), "resident: 129 x 128 fails");
+    CHECK(129 * 128 > 16 * 1024 && batch::resident_lds_bytes(129, 128) + 1024 <= 160 * 1024,
+          "resident: 129 x 128 fails on the pixels, not the bytes");
+    CHECK(!batch::resident_fits(150, 120), "resident: 150 x 120 fails");
+    CHECK(150 * 120 > 16 * 1024 && batch::resident_lds_bytes(150, 120) + 1024 <= 160 * 1024,
+          "resident: 150 x 120 fails on the pixels, not the bytes");
+    CHECK(!batch::resident_fits(2, 6000), "resident: 2 x 6000 fails");
+    CHECK(2 * 6000 <= 16 * 1024 && batch::resident_lds_bytes(2, 6000) + 1024 > 160 * 1024,
+          "resident: 2 x 6000 fails on the bytes, not the pixels");
+    CHECK(batch::resident_fits(1, 1) && batch::resident_lds_bytes(1, 1) == 72,
+          "resident: 1 x 1 fits with its ghost ring");
+    // conv_lds: dx * dy + dx + 1 elements of 8 bytes
+    CHECK(batch::conv_lds_fits(128, 128), "conv_lds: 128 x 128 fits");
+    CHECK(batch::conv_lds_bytes(128, 128) == 132104, "conv_lds: 128 x 128 is 132 104 B");
+    CHECK(!batch::conv_lds_fits(129, 128), "conv_lds: 129 x 128 fails");
+    CHECK(batch::conv_lds_fits(1, 1), "conv_lds: 1 x 1 fits");
+    for (const auto &d : {std::pair<int, int>{0, 4}, {4, 0}, {0, 0}, {-1, 4}, {4, -1}, {-3, -3},
+                          {std::numeric_limits<int>::min(), 1}}) {
+        CHECK(!batch::resident_fits(d.first, d.second), "resident: %d x %d fails", d.first, d.second);
+        CHECK(!batch::conv_lds_fits(d.first, d.second), "conv_lds: %d x %d fails", d.first, d.second);
+    }
+    for (int dy = 1; dy <= 130; dy++)
+        for (int dx = 1; dx <= 130; dx++) {
+            const int need = (dx * dy + 1023) / 1024;  // ceil(dx * dy / 1024)
+            const int r = batch::resident_ppt(dx, dy), c = batch::conv_lds_ppt(dx, dy);
+            CHECK(r == 1 || r == 2 || r == 4 || r == 8 || r == 16,
+                  "resident: %d x %d runs a compiled instantiation (%d)", dx, dy, r);
+            CHECK(c == 1 || c == 4 || c == 16, "conv_lds: %d x %d runs a compiled instantiation (%d)",
+                  dx, dy, c);
+            CHECK(!batch::resident_fits(dx, dy) || r >= need,
+                  "resident: %d x %d, %d pixels per thread hold %d", dx, dy, r, need);
+            CHECK(!batch::conv_lds_fits(dx, dy) || c >= need,
+                  "conv_lds: %d x %d, %d pixels per thread hold %d", dx, dy, c, need);
+            CHECK(batch::resident_fits(dx, dy) == (dx * dy <= 16384) &&
+                      batch::conv_lds_fits(dx, dy) == (dx * dy <= 16384),
+                  "%d x %d: up to 130 x 130 only the pixels decide", dx, dy);
+        }
+}
+
 int main() {
     test_chunk_pairs();
     test_rounds();
     test_refusals();
+    test_fit_rules();
     std::printf("batch_plan_test: %d checked, %d failed\n", g_checked, g_failed);
     return g_failed ? 1 : 0;
 }

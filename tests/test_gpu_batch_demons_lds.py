@@ -36,7 +36,7 @@ def level_dims(dims, nscales):
 
 
 def fits(dx, dy):
-    """The fit rule of of2d_batch.h (conv_lds_fits), restated: the dense plane
+    """The fit rule of batch_plan.h (conv_lds_fits), restated: the dense plane
     and its dx + 1 elements of slack plus 1 KiB of static LDS within the CU's
     160 KiB, and at most 16 pixels for each of the 1024 threads."""
     return (dx * dy + dx + 1) * 8 + 1024 <= 160 * 1024 and dx * dy <= 16 * 1024

@@ -23,7 +23,7 @@ def level_dims(dims, nscales):
 
 
 def fits(dx, dy):
-    """The fit rule of of2d_batch.h (resident_fits), restated: the iterate's one
+    """The fit rule of batch_plan.h (resident_fits), restated: the iterate's one
     LDS copy with its ghost ring plus 1 KiB of reduction scratch within the
     CU's 160 KiB, and at most 16 pixels for each of the 1024 threads."""
     return (dx + 2) * (dy + 2) * 8 + 1024 <= 160 * 1024 and dx * dy <= 16 * 1024
