@@ -235,8 +235,8 @@ int of2d_slab_time_kernel(of2d_slab *s, int nlaunch, double *avg_us);
  * launch, interior/edge split (0/1), triple kernel derives dI from Iaux (0/1),
  * Logger of a convergence-on run (1: the reference's float running sums,
  * 0: fp64 sums — "logger_fp64" resolved), iterations per fused launch of a
- * fixed_iters run (3, or 4: "hs_fixed_quads" resolved)}; returns the number of
- * entries written */
+ * fixed_iters run (3, or 4: "hs_fixed_quads" resolved), "hs_quad_tail_exchange"
+ * (0/1)}; returns the number of entries written */
 int of2d_slab_info(const of2d_slab *s, int *info, int n);
 /* the Logger errors of the last of2d_slab_run's iterations (the global ones:
  * the same on every rank), up to n into out; returns how many there are */
@@ -266,6 +266,10 @@ int of2d_slab_last_run_halo_us(const of2d_slab *s, double *us3, int *nsampled);
  *   that is not split and reads dI advances four iterations per launch
  *   (chunks of 25 launches) instead of three; 0 keeps the triples; the motion
  *   is bit-identical either way, the Logger errors agree to rounding
+ *   "hs_quad_tail_exchange" (1 = default, 0): the wave pairs of the quad kernel
+ *   exchange their end-of-band rows through LDS instead of recomputing them;
+ *   0 launches the instantiation without the exchange; motion and errors are
+ *   bit-identical either way
  *   "hs_gradients_from_image" (-1 auto = default, 0, 1): the triple kernel
  *   derives dI from Iaux in the kernel (24 B/px per launch) instead of reading
  *   dI (28); auto does so when dI + It (12 B/px) exceed the 256 MB MALL;

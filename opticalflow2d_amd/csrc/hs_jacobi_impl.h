@@ -1043,13 +1043,19 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi3_mid_kernel(
 // registers.  A lane touches only its own words (no barrier, 16-B stride
 // across lanes).  4 slots x 2 words x 16 B x 256 threads = 32 KB per block:
 // four blocks per CU fit the 160 KB.
+// XCH: the two waves of an ALT pair, which end their bands at the shared
+// boundary at the same march position, hand each other their last u1, u2 and
+// u3 rows through park slots the drain has freed instead of computing three,
+// two and one rows past their end (4 n + 7 instead of 4 n + 13 stencil steps
+// per wave, 151 instead of 157 at n = 36); the comment at the end of march().
 // the quad's division-range decision on the bits of sc (see its row step)
 constexpr unsigned kQuadRangeLo = 77u << 24, kQuadRangeSpan = (157u - 77u) << 24;
 __device__ __forceinline__ unsigned quad_range_key(float v) {
     return (__float_as_uint(v) << 1) - kQuadRangeLo;
 }
 
-template <int WAVES, bool XCD = true, int MINB = 4, int PRIO = 1, bool ALT = true>
+template <int WAVES, bool XCD = true, int MINB = 4, int PRIO = 1, bool ALT = true,
+          bool XCH = false, bool XSYNC = true>
 __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
     const float2 *__restrict__ uo, float2 *__restrict__ un, const float2 *__restrict__ dI,
     const float *__restrict__ It, int P, int dimx, int nrows, int row0, int dimy, float alphasq,
@@ -1071,6 +1077,17 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
     if (jhi < 0) jhi = nrows;
     const int jbeg = jlo + (by * WAVES + wave) * rows;
     const int jend = min(jbeg + rows, jhi);
+    // XCH: the block's wave pairs exchange their end-of-band rows (below).  One
+    // decision per block: every wave has its `rows` j-lines (so no pair's shared
+    // boundary is jhi or the image's edge, and no wave idles) and rows >= 6.
+    // (xdrop: the row steps such a block leaves to the exchange, 3 or 0, as a
+    // scalar word: a bool here is kept as a lane mask and spills SGPRs)
+    int xdrop = 0;
+    if constexpr (XCH) {
+        static_assert(ALT && WAVES % 2 == 0, "XCH pairs the waves of an ALT block");
+        xdrop = __builtin_amdgcn_readfirstlane(
+            rows >= 6 && jlo + (by + 1) * WAVES * rows <= jhi ? 3 : 0);
+    }
     float s1d = 0.0f, s1p = 0.0f, s2d = 0.0f, s2p = 0.0f, s3d = 0.0f, s3p = 0.0f, s4d = 0.0f,
           s4p = 0.0f;
     auto cl = [&](int j) { return min(max(j, glo), ghi - 1); };
@@ -1306,13 +1323,148 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void jacobi4_kernel(
             zj1 = zj2;
             zj2 = gj3.z;
         };
+        // row steps that run the whole body, and those of them that load a row
+        // ahead (an XCH block stops loading at u0(n) and the gradients of n-1)
+        const int nfull = n - xdrop;
         int sp = 0;
-        for (; sp + 4 < n; sp += 4) {
+        for (; sp + 4 < nfull; sp += 4) {
             progress_prio<PRIO>(sp, n);
 #pragma unroll
             for (int k = 0; k < 4; k++) body(sp + k, true, k);
         }
-        for (; sp < n; ++sp) body(sp, sp + 1 < n, sp & 3);
+        for (; sp < nfull; ++sp) body(sp, sp + 1 < nfull, sp & 3);
+        if constexpr (XCH) {
+            if (sp == n) return;
+            // The last three row steps of an XCH block.  Waves 2k and 2k+1 march
+            // towards their shared boundary and reach it at the same march
+            // position, so the rows a wave lacks past its end are its partner's
+            // own last rows: position n + i of this wave is the j-line of the
+            // partner's position n - 1 - i.  body() would compute u1(n..n+2),
+            // u2(n..n+1) and u3(n) itself (six stencil steps, three u rows and
+            // three gradient rows loaded, three fin/put); of those only u1(n),
+            // u2(n) and u3(n) feed this wave's own rows, and they are the
+            // partner's u1(n-1), u2(n-1), u3(n-1).  The others only fed those
+            // three, so three words per lane are exchanged, not six.
+            // Same bits: the partner marches the same 128-px strip, so lane l
+            // of both waves holds the same two columns, and a row of an iterate
+            // is, lane for lane, one function (stepr) of the three input rows
+            // in j order, the gradient row and the j-line: S() hands stepr the
+            // rows in j order for either direction, DPP gives a lane without a
+            // neighbour 0 in both waves, and the wave-uniform decisions of the
+            // step (range ballot, zero word, border masks) are taken over the
+            // same 64 lanes of the same values.  So the partner's word equals
+            // this wave's own recomputation in every lane, the halo lanes
+            // included, whose values are exact to the same depth (both waves
+            // apply the same number of steps to the same strip of the same
+            // input) and inexact in the same way beyond it.  By induction over
+            // the three rounds: u2(n-1) of the partner is made of its u1(n-2),
+            // u1(n-1) and this wave's u1(n-1), which is what this wave would
+            // have used for u2(n); likewise u3.
+            // Slots: the drain no longer parks the gradient rows n..n+2, so the
+            // slot of row n-4 (e0 = n & 3, last read in step n-4) and of row
+            // n-3 (e1 = (n+1) & 3, last read in step n-3) are free:
+            //   step n-3: u1(n-1) -> e0 word 0, barrier, partner's e0 word 0 =
+            //             u1(n); u2(n-1) -> e0 word 1
+            //   step n-2: barrier, partner's e0 word 1 = u2(n); u3(n-1) -> e1
+            //             word 0
+            //   step n-1: barrier, partner's e1 word 0 = u3(n)
+            // No word is written twice, so a reader can only be too early,
+            // never too late; s_waitcnt lgkmcnt(0) before each s_barrier puts
+            // the wave's writes in LDS before its partner passes the barrier.
+            // All WAVES waves of an XCH block run these three barriers (the
+            // decision is the block's, every wave marches rows j-lines).
+            // XSYNC = false (tools/hs_variants_tail.hip only, never launched by
+            // the product) leaves exchange and barriers out for timing: wrong
+            // results.
+            constexpr int NT = 64 * WAVES;
+            lds_v4f *px = (lds_v4f *)&park[0][0][threadIdx.x ^ 64];
+            auto pack = [](const Row<2> &r) { return v4f{r.v[0].x, r.v[0].y, r.v[1].x, r.v[1].y}; };
+            auto unpack = [](const v4f w) {
+                Row<2> r;
+                r.v[0] = make_float2(w.x, w.y);
+                r.v[1] = make_float2(w.z, w.w);
+                return r;
+            };
+            auto sync = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+            auto out = [&](int p, const Row<2> &z) __attribute__((always_inline)) {
+                norms(z, xj, s4d, s4p);
+                float2 *dst = un + (long)J(p) * P + x;
+                if (x + 2 <= dimx)
+                    st4<true>(reinterpret_cast<float4 *>(dst),
+                              make_float4(z.v[0].x, z.v[0].y, z.v[1].x, z.v[1].y));
+                else
+                    dst[0] = z.v[0];
+            };
+            // the words' LDS addresses as lane values, taken once (sp = n - 3
+            // here; nothing scalar but n stays live for the three steps)
+            const int s0 = sp & 3, e0 = (s0 + 3) & 3;
+            lds_v4f *const g0 = pk + 2 * s0 * NT, *const g1 = pk + 2 * ((s0 + 1) & 3) * NT,
+                           *const g2 = pk + 2 * ((s0 + 2) & 3) * NT;
+            lds_v4f *const me0 = pk + 2 * e0 * NT, *const pe0 = px + 2 * e0 * NT,
+                           *const pe1 = px + 2 * s0 * NT;  // e1 = (n + 1) & 3 = s0: g0's slot
+            auto getp = [&](lds_v4f *p, float2 t, unsigned z) {
+                const v4f a = p[0], b = p[NT];
+                return G{a, b, t, z};
+            };
+            {
+                Row<2> vj3 = vj2;  // u1(n)
+                if constexpr (XSYNC) {
+                    me0[0] = pack(vj2);
+                    sync();
+                    vj3 = unpack(pe0[0]);
+                }
+                const G gj2 = getp(g2, tj2, zj2);
+                const Row<2> wj2 = S(n - 1, vj1, vj2, vj3, gj2);  // u2(n-1)
+                if constexpr (XSYNC) me0[NT] = pack(wj2);
+                const G gj1 = getp(g1, tj1, zj1);
+                const Row<2> xj1 = S(n - 2, wj, wj1, wj2, gj1);  // u3(n-2)
+                const G gj = getp(g0, tj, zj);
+                const Row<2> z = S(n - 3, xm1, xj, xj1, gj);  // u4(n-3)
+                if (own) {
+                    norms(wj2, vj2, s2d, s2p);
+                    norms(xj1, wj1, s3d, s3p);
+                    out(n - 3, z);
+                }
+                wj = wj1;
+                wj1 = wj2;
+                xm1 = xj;
+                xj = xj1;
+                tj = tj1;
+                tj1 = tj2;
+                zj = zj1;
+                zj1 = zj2;
+            }
+            {
+                Row<2> wj2 = wj1;  // u2(n)
+                if constexpr (XSYNC) {
+                    sync();
+                    wj2 = unpack(pe0[NT]);
+                }
+                const G gj1 = getp(g2, tj1, zj1);
+                const Row<2> xj1 = S(n - 1, wj, wj1, wj2, gj1);  // u3(n-1)
+                if constexpr (XSYNC) g0[0] = pack(xj1);
+                const G gj = getp(g1, tj, zj);
+                const Row<2> z = S(n - 2, xm1, xj, xj1, gj);  // u4(n-2)
+                if (own) {
+                    norms(xj1, wj1, s3d, s3p);
+                    out(n - 2, z);
+                }
+                xm1 = xj;
+                xj = xj1;
+                tj = tj1;
+                zj = zj1;
+            }
+            {
+                Row<2> xj1 = xj;  // u3(n)
+                if constexpr (XSYNC) {
+                    sync();
+                    xj1 = unpack(pe1[0]);
+                }
+                const G gj = getp(g2, tj, zj);
+                const Row<2> z = S(n - 1, xm1, xj, xj1, gj);  // u4(n-1)
+                if (own) out(n - 1, z);
+            }
+        }
     };
     if (jbeg < jend) {
         if (ALT && (wave & 1))

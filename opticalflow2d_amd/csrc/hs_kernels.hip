@@ -106,11 +106,16 @@ void launch_hs_jacobi3(const float2 *u_old, float2 *u_new, const float2 *dI, con
 // grid (hs3_rows, the same blocks and partial slots), 4 resident blocks per CU
 // with part of the register window parked in LDS (hs_jacobi_impl.h)
 static const auto kHsJacobi4 = &hs::jacobi4_kernel<kHs3Waves, true, 4, 1, true>;
+// the same with the wave pairs of every full block exchanging their end-of-band
+// rows through LDS instead of recomputing them (XCH: 151 instead of 157 stencil
+// steps per 36-row wave; the same bits)
+static const auto kHsJacobi4X = &hs::jacobi4_kernel<kHs3Waves, true, 4, 1, true, true>;
 
 void launch_hs_jacobi4(const float2 *u_old, float2 *u_new, const float2 *dI, const float *It,
                        int P, int dimx, int dimy, float alphasq, int glo, int ghi,
                        double *partial, double *partial2, double *partial3, double *partial4,
-                       const unsigned *range_flag, hipStream_t st, int slots) {
+                       const unsigned *range_flag, hipStream_t st, int slots,
+                       bool tail_exchange) {
     if (P % kHsStrip != 0 || dimy <= 0 || dimx > P || dimx < 2 || glo > -1 || ghi < dimy + 1)
         throw std::invalid_argument("launch_hs_jacobi4: bad geometry");
     if (!range_flag) throw std::invalid_argument("launch_hs_jacobi4: no range flag");
@@ -121,7 +126,7 @@ void launch_hs_jacobi4(const float2 *u_old, float2 *u_new, const float2 *dI, con
     const int gx = (dimx + kHs3Out - 1) / kHs3Out;
     const int gy = (dimy + kHs3Waves * rows - 1) / (kHs3Waves * rows);
     const dim3 gl(8 * ((gx * gy + 7) / 8));
-    hipLaunchKernelGGL(kHsJacobi4, gl, dim3(64 * kHs3Waves), 0, st, u_old, u_new, dI, It, P, dimx,
+    hipLaunchKernelGGL(tail_exchange ? kHsJacobi4X : kHsJacobi4, gl, dim3(64 * kHs3Waves), 0, st, u_old, u_new, dI, It, P, dimx,
                        dimy, 0, dimy, alphasq, glo, ghi, partial, partial2, partial3, partial4, 0,
                        gx, gy, rows, range_flag, -1, -1);
     OF2D_HIP(hipGetLastError());

@@ -221,10 +221,13 @@ void launch_hs_precheck(const float2 *base, size_t count, int P, int ghost, int 
 // triple's, reused on purpose: the quad's prologue is a row step or two longer,
 // which moves the optimum only where two candidates are that close, and equal
 // rows keep the quad's blocks and Logger partials those of the triple.
+// tail_exchange: the instantiation whose wave pairs exchange their end-of-band
+// rows through LDS (hs_jacobi_impl.h XCH); the same bits either way.
 void launch_hs_jacobi4(const float2 *u_old, float2 *u_new, const float2 *dI, const float *It,
                        int P, int dimx, int dimy, float alphasq, int glo, int ghi,
                        double *partial, double *partial2, double *partial3, double *partial4,
-                       const unsigned *range_flag, hipStream_t st, int slots = 1024);
+                       const unsigned *range_flag, hipStream_t st, int slots = 1024,
+                       bool tail_exchange = true);
 constexpr int kRangeFlagWord = 32;  // word of the 64-word status buffers holding range_flag
 constexpr int kStopWord = 33;  // the exact-Logger loop's break (seqnorm_decide)
 // the Fluid loop's device-side decisions (Registration::loop_fluid, FluidCtl):

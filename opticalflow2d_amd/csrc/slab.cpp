@@ -110,6 +110,10 @@ struct of2d_slab {
     // per launch (hs::jacobi4_kernel, 25 per chunk) unless this is 0 (option
     // "hs_fixed_quads"; the motion is bit-identical either way)
     int quads = 1;
+    // the quad kernel's wave pairs exchange their end-of-band rows through LDS
+    // instead of recomputing them (option "hs_quad_tail_exchange"; 0 launches
+    // the instantiation without the exchange; bit-identical either way)
+    int quad_tail_exchange = 1;
     // rows of the partial buffer: the longest chunk of any run
     int chunk_cap() const {
         namespace sched = of2d::sched;
@@ -1007,7 +1011,7 @@ int of2d_slab_run(of2d_slab *s, int niter, int fixed_iters, int *iters_done) {
                 // ghost j-lines (u three), and none of them feeds an image pixel
                 of2d::launch_hs_jacobi4(uin, s->u[out].p, s->dI.p, s->It.p, s->P, s->dimx,
                                         s->nrows, alphasq, -2, s->nrows + 2, p1, p2, p3, p4,
-                                        range_flag, s->st, G.slots);
+                                        range_flag, s->st, G.slots, s->quad_tail_exchange != 0);
                 return;
             }
             if (K == 3 && G.split) {
@@ -1224,7 +1228,7 @@ int of2d_slab_time_kernel(of2d_slab *s, int nlaunch, double *avg_us) {
                 of2d::launch_hs_jacobi4(s->u[in].p, s->u[out].p, s->dI.p, s->It.p, s->P, s->dimx,
                                         s->nrows, alphasq, -2, s->nrows + 2, p1, p2, p3,
                                         p1 + (size_t)nb * 6, s->d_status + of2d::kRangeFlagWord,
-                                        s->st, G.slots);
+                                        s->st, G.slots, s->quad_tail_exchange != 0);
                 return;
             }
             of2d::launch_hs_jacobi3(s->u[in].p, s->u[out].p, s->dI.p, s->It.p, s->P, s->dimx,
@@ -1251,7 +1255,8 @@ int of2d_slab_info(const of2d_slab *s, int *info, int n) {
     const int halo_lines = s->nranks > 1 ? 3 : 0;
     const int v[] = {s->nranks, rccl, s->grp ? 1 : 0, s->rb, s->re, s->dimx, s->P,
                      halo_lines, slab_geometry(s).split ? 1 : 0, use_gi(s) ? 1 : 0,
-                     exact_logger(s) ? 1 : 0, use_quads(s, slab_geometry(s).split) ? 4 : 3};
+                     exact_logger(s) ? 1 : 0, use_quads(s, slab_geometry(s).split) ? 4 : 3,
+                     s->quad_tail_exchange};
     const int k = std::min(n, (int)(sizeof v / sizeof v[0]));
     for (int i = 0; i < k; i++) info[i] = v[i];
     return k;
@@ -1281,6 +1286,10 @@ int of2d_slab_set_option(of2d_slab *s, const char *key, double value) {
     }
     if (std::strcmp(key, "hs_fixed_quads") == 0) {
         s->quads = value != 0.0;
+        return OF2D_OK;
+    }
+    if (std::strcmp(key, "hs_quad_tail_exchange") == 0) {
+        s->quad_tail_exchange = value != 0.0;
         return OF2D_OK;
     }
     s->err = std::string("slab: unknown option ") + key;

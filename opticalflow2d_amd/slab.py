@@ -119,19 +119,21 @@ class SlabSolver:
         whether the triple kernel derives dI from Iaux, and the Logger a
         convergence-on run takes (1: the reference's float running sums, 0:
         fp64 sums), and the iterations a fixed_iters run advances per fused
-        launch (3, or 4 where it launches the quad kernel)."""
-        buf = (C.c_int * 12)()
-        n = _lib.lib().of2d_slab_info(self._h, buf, 12)
+        launch (3, or 4 where it launches the quad kernel), and whether the quad
+        kernel's wave pairs exchange their end-of-band rows."""
+        buf = (C.c_int * 13)()
+        n = _lib.lib().of2d_slab_info(self._h, buf, 13)
         if n < 0:
             self._chk(-n)
         keys = ["nranks", "rccl_ranks", "in_process_group", "row_begin", "row_end", "dimx",
                 "pitch", "halo_lines", "split", "gradients_from_image", "logger_reference",
-                "iterations_per_launch"]
+                "iterations_per_launch", "quad_tail_exchange"]
         return {k: int(buf[i]) for i, k in enumerate(keys[:n])}
 
     def set_option(self, key: str, value: float) -> None:
         """Tuning switch (include/of2d.h of2d_slab_set_option), e.g.
-        "hs_gradients_from_image" 0/1, "hs_fixed_quads" 0/1; the motion is
+        "hs_gradients_from_image" 0/1, "hs_fixed_quads" 0/1,
+        "hs_quad_tail_exchange" 0/1; the motion is
         bit-identical either way."""
         self._chk(_lib.lib().of2d_slab_set_option(self._h, key.encode(), float(value)))
 
