@@ -7,9 +7,11 @@ stopping on its own iteration) and the per-frame iteration counts are printed.
 With --reg 3 the registrations are Thirion's Demons (parameters 1, 0.25, 1.5,
 2.5, kernel width 5, Composition); --diffeomorphic with it turns on the batch's
 option of that name: Diffeomorphic Demons, every frame with its own number of
-squarings per iteration.
+squarings per iteration.  With --reg 1 they are Curvature registrations (alpha
+0.05, tau 50; --size must then be a power of two from 16 to 512, as must its
+half, the coarser level).
 
-    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 3]
+    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 1|3]
                                   [--diffeomorphic] [--resident] [--conv-lds] [--report]
                                   [--track T]
 
@@ -45,6 +47,10 @@ from opticalflow2d_amd import BatchRegistration  # noqa: E402
 from opticalflow2d_amd import synthetic as S  # noqa: E402
 
 
+# the parameters of --reg 1 and 3; --reg 0 takes --alpha
+REG_PARAMS = {0: None, 1: [0.05, 50.0], 3: [1.0, 0.25, 1.5, 2.5, 5, 0]}
+
+
 def options_of(a):
     options = {"diffeomorphic": 1} if a.diffeomorphic else {}
     if a.resident:
@@ -58,7 +64,7 @@ def track(a):
     """T frames of B slices, frame after frame: warm_start=1 against the default."""
     n, B, T = a.size, a.frames, a.track
     refs, frames, shifts = S.cine_series(n, B, T)
-    params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
+    params = REG_PARAMS[a.reg] or a.alpha
     options = options_of(a)
     rows = []
     with BatchRegistration(B, (n, n), [a.niter], 0, params, reg=a.reg, warm_start=1,
@@ -86,8 +92,8 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--niter", type=int, default=300)
     ap.add_argument("--alpha", type=float, default=0.3)
-    ap.add_argument("--reg", type=int, default=0, choices=[0, 3],
-                    help="0 Horn-Schunck (alpha), 3 Thirion's Demons")
+    ap.add_argument("--reg", type=int, default=0, choices=[0, 1, 3],
+                    help="0 Horn-Schunck (alpha), 1 Curvature, 3 Thirion's Demons")
     ap.add_argument("--diffeomorphic", action="store_true",
                     help="with --reg 3: Diffeomorphic Demons (the option 'diffeomorphic')")
     ap.add_argument("--resident", action="store_true",
@@ -117,7 +123,7 @@ def main():
     # texture_pair's second image is its first (one seed: ref) shifted bilinearly
     frames = np.stack([S.texture_pair(n, seed=3, sigma=3.0, shift=(sx, sy))[1]
                        for sx, sy in shifts])
-    params = a.alpha if a.reg == 0 else [1.0, 0.25, 1.5, 2.5, 5, 0]
+    params = REG_PARAMS[a.reg] or a.alpha
     options = options_of(a)
     with BatchRegistration(B, (n, n), [a.niter, a.niter], 1, params, reg=a.reg, **options) as b:
         b.register(ref, frames)  # one reference shared by every frame

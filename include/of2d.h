@@ -397,14 +397,33 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  *
  * of2d_batch_create refuses with OF2D_ERR_INVALID_ARGUMENT and a message
  * (of2d_batch_last_error(NULL)), before any device work: nbatch < 1 or > 65535,
- * a reg other than OF2D_REG_DIFFUSION and OF2D_REG_THIRIONS_DEMONS, nparams !=
- * 1 (Diffusion) or != 6 (Demons; the reference's message), a Demons
- * kernel_width < 1 (of2d_create's message),
+ * a reg other than OF2D_REG_DIFFUSION, OF2D_REG_CURVATURE and
+ * OF2D_REG_THIRIONS_DEMONS, a Curvature batch with a pyramid level whose side
+ * is not a power of two in [OF2D_DCT_NMIN, OF2D_BATCH_CURV_NMAX] (the same
+ * sentence as for a refused method: it names the three and the rule), nparams
+ * != 1 (Diffusion), != 1 and != 2 (Curvature) or != 6 (Demons; the reference's
+ * message), a Demons kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
  * Options: "fixed_iters", "device" (before first use), "diffeomorphic",
  * "warm_start", "resident", "conv_lds"; an
  * unknown key is refused ("demons_separable" among them: the batch smooths
  * with the direct convolution only).
+ *
+ * Curvature (reg = OF2D_REG_CURVATURE, regparams = {alpha} with tau = 1, or
+ * {alpha, tau}): every pyramid level (dimx / 2^s, dimy / 2^s) must have both
+ * sides a power of two in [OF2D_DCT_NMIN, OF2D_BATCH_CURV_NMAX], so a 64 x 32
+ * batch takes nscales <= 2; the other sizes (the one-pair path's GEMMs) are not
+ * offered.  One workgroup runs a pair's whole loop: per iteration the right-hand
+ * side, the four line-transform passes of the one-pair "curvature_dct" = 1 path
+ * (axis y then x, forward with the eigenvalues, then inverse) and the update,
+ * the fp64 plane pair in a per-pair scratch of 16 bytes per pixel and level.
+ * With "fixed_iters" 1 every pair's motion, warp and iteration counts are those
+ * of of2d_create(reg 1) with "curvature_dct" 1 and "fixed_iters" 1 on that pair
+ * alone, bit for bit.  Curvature has no zero denominator: every pair's status is
+ * OF2D_OK.  "fixed_iters", "device" and "warm_start" apply; "resident",
+ * "conv_lds" and "diffeomorphic" are refused as on any batch of another method.
+ * of2d_batch_info reports placement 0 at every level, 512 threads, and the
+ * launches of a Diffusion batch (4 per loop).
  *
  * "diffeomorphic" (0, the default, or 1): Diffeomorphic Demons.  With 1, a
  * batch created with reg = OF2D_REG_THIRIONS_DEMONS and accumulation 0
@@ -456,7 +475,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * the kernel its LDS, every level runs as with 0 (placement 0) and nothing is
  * reported as an error.  Composes with "fixed_iters", "warm_start" and
  * "device".  Refused with OF2D_ERR_INVALID_ARGUMENT, the handle still usable
- * and the option unchanged: on a Demons batch ("resident: the batch is not a
+ * and the option unchanged: on a Demons or Curvature batch ("resident: the batch is not a
  * Diffusion batch") and for a value other than 0 or 1 ("resident: the value
  * must be 0 or 1").
  *
@@ -476,7 +495,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * (placement 0) and nothing is reported as an error.  Composes with
  * "fixed_iters", "warm_start", "device" and "diffeomorphic".  Refused with
  * OF2D_ERR_INVALID_ARGUMENT, the handle still usable and the option
- * unchanged: on a Diffusion batch ("conv_lds: the batch is not a Thirion's
+ * unchanged: on a Diffusion or Curvature batch ("conv_lds: the batch is not a Thirion's
  * Demons batch") and for a value other than 0 or 1 ("conv_lds: the value must
  * be 0 or 1").
  *
@@ -484,6 +503,8 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * fewer pairs than compute units most of the device idles. */
 typedef struct of2d_batch of2d_batch;
 #define OF2D_BATCH_MAXPX (512 * 512)
+/* the longest side of a Curvature batch's levels */
+#define OF2D_BATCH_CURV_NMAX 512
 int of2d_batch_create(of2d_batch **out, int nbatch, int dimx, int dimy, const int *niter,
                       int nscales, int reg, const float *regparams, unsigned nparams,
                       int nrefine);

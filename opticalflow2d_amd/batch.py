@@ -1,8 +1,8 @@
-"""Batched Horn-Schunck and Thirion's Demons: many small image pairs of one
-size in one call.
+"""Batched Horn-Schunck, Curvature and Thirion's Demons: many small image pairs
+of one size in one call.
 
 :class:`BatchRegistration` is the object-style handle on ``of2d_batch_*``
-(include/of2d.h): ``nbatch`` independent Diffusion or Thirion's Demons
+(include/of2d.h): ``nbatch`` independent Diffusion, Curvature or Thirion's Demons
 registrations with the same parameters, each run by one workgroup with the
 whole iteration loop inside the kernel.  Arrays follow :class:`ImageRegistration`'s convention with a leading
 pair axis: an image is ``[dimx, dimy]`` (x first), a stack of them
@@ -29,7 +29,11 @@ class BatchRegistration:
     ``niter`` (nscales+1 values, finest level first), ``nscales``, ``alpha``
     and ``nrefine`` are :class:`ImageRegistration`'s.  ``reg`` is
     ``Regularisation.Diffusion`` (the default; ``alpha`` is Horn-Schunck's one
-    parameter) or ``Regularisation.ThirionsDemons`` (3), for which ``alpha``
+    parameter), ``Regularisation.Curvature`` (1; ``alpha`` is ``[alpha]`` with
+    tau = 1 or ``[alpha, tau]``, and both sides of every pyramid level must be
+    powers of two from 8 to 512: per pair the one-pair ``curvature_dct=1``
+    registration, bit for bit with ``fixed_iters=1``) or
+    ``Regularisation.ThirionsDemons`` (3), for which ``alpha``
     carries the one-pair path's six parameters ``[sigma_i, sigma_x,
     sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
     method is refused.  The other keyword options map to

@@ -1,7 +1,7 @@
-// batch.cpp — host driver of the batched Horn-Schunck and Thirion's Demons
-// registrations (of2d_batch.h).  The pyramid and refine sequence is that of
-// Registration::estimate / estimate_level for Diffusion and Thirion's Demons
-// (registration.cpp; Demons takes no gradients pass: its loop warps and
+// batch.cpp — host driver of the batched Horn-Schunck, Curvature and Thirion's
+// Demons registrations (of2d_batch.h).  The pyramid and refine sequence is that
+// of Registration::estimate / estimate_level for Diffusion, Curvature and
+// Thirion's Demons (registration.cpp; Demons takes no gradients pass: its loop warps and
 // differentiates the moving image itself),
 // applied to all pairs at once: the host enqueues every level's launches and
 // reads nothing back until the estimate ends; every decision (a pair's break,
@@ -23,10 +23,12 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
     if (nbatch < 1) throw std::invalid_argument("Error: batch needs nbatch >= 1\n");
     if (nbatch > kMaxPairs)
         throw std::invalid_argument("Error: batch takes at most 65535 pairs per call\n");
-    if (reg != 0 && reg != 3)
-        throw std::invalid_argument(
-            "Error: the batched registration supports Diffusion regularisation only, or "
-            "Thirion's Demons\n");
+    // one sentence for every refusal by method; a Curvature batch whose levels
+    // do not all qualify gets it too (below)
+    static const char *const kMethods =
+        "Error: the batched registration supports Diffusion regularisation only, Thirion's "
+        "Demons, or Curvature where every level's sides are powers of two from 8 to 512\n";
+    if (reg != 0 && reg != 1 && reg != 3) throw std::invalid_argument(kMethods);
     if (!valid_regularisation_parameters(reg, nparams))
         throw std::invalid_argument(
             "Invalid number of regularisation parameters for given regularisation method.\n");
@@ -47,6 +49,7 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
         kfluid_ = gaussian_kernel(kw, params[3]);
     } else {
         alpha_ = params[0];
+        if (reg == 1 && nparams == 2) tau_ = params[1];  // else OpticalFlowCurvature.h:8
     }
     // ImageRegistration.cpp:56-61: dim(dimin.x/scale, dimin.y/scale) with float scale
     ldx_.resize(nscales + 1);
@@ -57,6 +60,8 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
         ldy_[s] = (int)(unsigned)((float)(unsigned)dimy / scale);
         if (ldx_[s] <= 0 || ldy_[s] <= 0)
             throw std::invalid_argument("Error: pyramid level with zero size\n");
+        // Curvature runs the fast line transforms on both axes of every level
+        if (reg == 1 && !curv_level_ok(ldx_[s], ldy_[s])) throw std::invalid_argument(kMethods);
     }
     nloops_ = (nscales + 1) * std::max(nrefine, 0);
     for (int n : niter_) maxn_ = std::max(maxn_, n);
@@ -176,6 +181,18 @@ void Batch::allocate_device() {
         L.est[0].alloc(L.dx, L.dy, B_);
         L.est[1].alloc(L.dx, L.dy, B_);
         if (reg_ == 3) L.mid.alloc(L.dx, L.dy, B_);
+        if (reg_ == 1) {
+            // the level's tables by the one-pair path's own builders
+            // (solvers::build_curvature), E dense
+            L.cX.alloc(curv_scratch_doubles(L.dx, L.dy) * B_);
+            auto upload = [](DevArray<double> &d, const std::vector<double> &h) {
+                d.alloc(h.size());
+                OF2D_HIP(hipMemcpy(d.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+            };
+            upload(L.cE, curvature_eigenvalues(L.dx, L.dy, L.dx, alpha_, tau_));
+            upload(L.ctwx, dct_table(L.dx));
+            upload(L.ctwy, dct_table(L.dy));
+        }
     }
     if (reg_ == 3) {
         // both tables once per Batch, sigma_fluid's first (Registration::loop_demons)
@@ -345,7 +362,7 @@ void Batch::estimate() {
             // *Iaux = *Imov; Iaux->warp2d(*motion)
             launch_warp(L.Imov.p, L.motion[L.mcur].p, L.Iaux.p, L.stride, L.dx, L.dy, L.P, B_,
                         d_status_, st_);
-            if (reg_ == 0)
+            if (reg_ == 0 || reg_ == 1)
                 launch_gradients(L.Iref.p, shared_ ? 0 : L.stride, L.Iaux.p, L.dI.p, L.It.p,
                                  L.stride, L.dx, L.dy, L.P, B_, d_status_, st_);
             // motion_est starts at zero
@@ -356,7 +373,7 @@ void Batch::estimate() {
                               L.stride, L.dx, L.dy, L.P, B_, d_iters_, nloops_, loop, d_status_,
                               st_);
             L.mcur ^= 1;
-            launches_ += reg_ == 0 ? 4 : 3;  // Demons: no gradients launch
+            launches_ += reg_ == 3 ? 3 : 4;  // Demons: no gradients launch
         }
         if (s > 0) {
             launch_upsample_motion(L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P,
@@ -418,6 +435,23 @@ void Batch::launch_loop(int s, int loop, bool conv) {
     OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
     if (reg_ == 3) {
         (placement_[s] ? launch_demons_lds : launch_demons_loop)(demons_args(c, L), B_, conv, st_);
+    } else if (reg_ == 1) {
+        CurvLoopArgs a{c};
+        a.dI = L.dI.p;
+        a.It = L.It.p;
+        a.X = L.cX.p;
+        a.sx = (long)curv_scratch_doubles(L.dx, L.dy);
+        a.E = L.cE.p;
+        a.twx = reinterpret_cast<const double2 *>(L.ctwx.p);
+        a.twy = reinterpret_cast<const double2 *>(L.ctwy.p);
+        a.tau = tau_;
+        a.div = 4.0f * (float)((unsigned)L.dx * (unsigned)L.dy);  // 4.0f*sizein
+        a.logx = a.logy = 0;
+        while ((1 << a.logx) < L.dx) a.logx++;
+        while ((1 << a.logy) < L.dy) a.logy++;
+        a.lx = curv_chunk_lines(L.dx, L.dy);
+        a.ly = curv_chunk_lines(L.dy, L.dx);
+        launch_curv_loop(a, B_, conv, st_);
     } else {
         LoopArgs a{c};
         a.dI = L.dI.p;
@@ -716,7 +750,7 @@ std::vector<int> Batch::info() const {
         // 0: every field of the loop in global memory; 1: the iterate
         // (resident) or the convolved field (conv_lds) stays on the CU
         v.push_back(s < (int)placement_.size() ? placement_[s] : 0);
-        v.push_back(kLoopThreads);
+        v.push_back(reg_ == 1 ? kCurvThreads : kLoopThreads);
     }
     return v;
 }

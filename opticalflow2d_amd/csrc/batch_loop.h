@@ -1,7 +1,8 @@
-// batch_loop.h — the frame the batch's four loop kernels share (hs_loop_kernel,
-// hs_resident_kernel, demons_loop_kernel, demons_lds_kernel).
+// batch_loop.h — the frame the batch's five loop kernels share (hs_loop_kernel,
+// hs_resident_kernel, demons_loop_kernel, demons_lds_kernel, curv_loop_kernel;
+// DESIGN.md §4.6).
 //
-// One workgroup of kLoopThreads runs the whole loop of pair blockIdx.x:
+// One workgroup of kLoopThreads (Curvature: kCurvThreads) runs the whole loop of pair blockIdx.x:
 //   entry   loop_entry: the pair's iters and errs slots; a pair whose status
 //           has kStatusDivZero from an earlier loop runs nothing and reports 0
 //           iterations

@@ -108,6 +108,53 @@ inline int conv_lds_ppt(int dx, int dy) {
     return p <= 1 ? 1 : p <= 4 ? 4 : kConvLdsMaxPpt;
 }
 
+// ---- the Curvature loop (batch_curvature_kernels.hip).
+// Both sides of every level are a fast-transform length: a power of two in
+// [kCurvNMin, kCurvNMax] (OF2D_DCT_NMIN, OF2D_BATCH_CURV_NMAX)
+// A pair's workgroup is kCurvThreads, half the other loops': a chunk of lines
+// (below) is 512 radix-4 butterflies per pass, one per thread
+constexpr int kCurvWaves = 8;
+constexpr int kCurvThreads = 64 * kCurvWaves;
+constexpr int kCurvNMin = 8;
+constexpr int kCurvNMax = 512;
+inline bool curv_side_ok(int n) {
+    return n >= kCurvNMin && n <= kCurvNMax && (n & (n - 1)) == 0;
+}
+inline bool curv_level_ok(int dx, int dy) { return curv_side_ok(dx) && curv_side_ok(dy); }
+// A pair's fp64 scratch at a level: the plane pair x | y, dense (element
+// (i, j) of a plane at i + j * dx), 16 B per pixel; no transposed copy
+inline size_t curv_scratch_doubles(int dx, int dy) { return 2 * (size_t)dx * (size_t)dy; }
+// A pass along an axis moves its lines through LDS in chunks of whole lines, a
+// line of n elements being n double2 points (16 B each: n/2 complex points per
+// plane).  A chunk holds at most kCurvChunkPoints points of lines, that is
+// kCurvPointsPerThread per thread: dct_inv_pre keeps a thread's points in
+// registers across its barrier, and more of them (8 were tried) cost more
+// registers than a lane has.  The lines are spread evenly over the fewest
+// chunks that allows.  In LDS a line is followed by kCurvLinePad unused
+// points: along y a wave's lanes walk across the chunk's columns, and a line
+// stride of n points would put them all on one bank.  The largest chunk, 256
+// lines of 8, is 36 KiB: within the 64 KiB a launch gets without asking
+constexpr size_t kCurvPointBytes = 16;
+constexpr int kCurvLinePad = 1;
+constexpr int kCurvPointsPerThread = 4;
+constexpr int kCurvChunkPoints = kCurvPointsPerThread * kCurvThreads;
+inline int curv_chunks(int n, int nlines) {
+    const int most = kCurvChunkPoints / n;  // lines that fit
+    return (nlines + most - 1) / most;
+}
+inline int curv_chunk_lines(int n, int nlines) {
+    const int c = curv_chunks(n, nlines);
+    return (nlines + c - 1) / c;
+}
+inline size_t curv_chunk_bytes(int n, int nlines) {
+    return (size_t)curv_chunk_lines(n, nlines) * (size_t)(n + kCurvLinePad) * kCurvPointBytes;
+}
+// dynamic LDS of a level's launch: the larger of its two axes' chunks (lines
+// along x: dx long, dy of them; along y: dy long, dx of them)
+inline size_t curv_lds_bytes(int dx, int dy) {
+    return std::max(curv_chunk_bytes(dx, dy), curv_chunk_bytes(dy, dx));
+}
+
 // nullptr or why the call is refused (the one-pair entries' wording)
 inline const char *jacobian_refusal(int dimx, int dimy) {
     if (dimx < 2 || dimy < 2) return "jacobian: the field needs dimx >= 2 and dimy >= 2";

@@ -23,7 +23,8 @@
 // parts swapped, so there is a single FFT: in-place decimation in frequency,
 // radix-4 passes (a last radix-2 pass when log2 (n/2) is odd) with one barrier
 // between passes; the result is left in digit-reversed order and the
-// post-processing reads it through dct_pos().
+// post-processing reads it through dct_pos().  The per-line arithmetic itself
+// is dct_px.h's, which the batch's Curvature loop shares.
 //
 // fp64 throughout; the twiddles are a host-built fp64 table (dct_table).
 // Lines are contiguous (element k of line l at l * P + k, the y plane `plane`
@@ -33,6 +34,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "dct_px.h"
 #include "of2d_device.h"
 
 namespace of2d {
@@ -40,48 +42,6 @@ namespace of2d {
 namespace {
 constexpr int kDctPoints = 1024;  // complex points per block below that line length
 constexpr int kDctThreads = 512;  // largest block
-
-// position of frequency k after the in-place passes (radices 4, 4, ..., [2])
-__device__ inline int dct_pos(int k, int N) {
-    int M = N, p = 0;
-    while (M >= 4) {
-        M >>= 2;
-        p += (k & 3) * M;
-        k >>= 2;
-    }
-    if (M == 2) p += k & 1;
-    return p;
-}
-
-__device__ inline double2 cmul(double2 a, double2 w) {
-    return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-
-// REDFT10 output k of one plane from its half-length spectrum zs (digit-
-// reversed): Re(c_k 2 V_k) for k <= n/2, -Im(c_{n-k} 2 V_{n-k}) above
-__device__ inline double dct_fwd_out(const double2 *zs, const double2 *tw, int k, int N) {
-    const int Nh = N >> 1, kk = k <= Nh ? k : N - k;
-    const double2 uk = zs[dct_pos(kk & (Nh - 1), Nh)], un = zs[dct_pos((Nh - kk) & (Nh - 1), Nh)];
-    const double2 a = make_double2(uk.x + un.x, uk.y - un.y);   // U_k + conj U_{n/2-k}
-    const double2 b = make_double2(uk.y + un.y, un.x - uk.x);   // -i (U_k - conj U_{n/2-k})
-    const double2 wb = cmul(b, tw[kk]);
-    const double2 t = cmul(make_double2(a.x + wb.x, a.y + wb.y), tw[N + kk]);
-    return k <= Nh ? t.x : -t.y;
-}
-
-// V_k = conj(c_k) (C_k - i C_{n-k}) of one plane's coefficients C (C_n = 0), 0 <= k <= n/2
-__device__ inline double2 dct_inv_v(const double *C, const double2 *tw, int k, int N) {
-    const double2 c = tw[N + k];
-    const double er = c.x, ei = -c.y, p = C[k], q = k == 0 ? 0.0 : C[N - k];
-    return make_double2(er * p + ei * q, ei * p - er * q);
-}
-
-// REDFT01 sample n of the reordered line v from the FFT of the swapped
-// spectrum (digit-reversed): v_2j = Im, v_{2j+1} = Re of element j
-__device__ inline double dct_inv_out(const double2 *zs, int n, int Nh) {
-    const double2 r = zs[dct_pos(n >> 1, Nh)];
-    return (n & 1) ? r.x : r.y;
-}
 }  // namespace
 
 // KIND 0: REDFT10 (times E[k + line * P] when E != nullptr), 1: REDFT01, in
@@ -95,7 +55,6 @@ __global__ __launch_bounds__(kDctThreads) void dct_lines_kernel(double *X, long 
                                                                 int lpb, const double2 *tw,
                                                                 const double *E) {
     extern __shared__ double2 z[];
-    double *zd = reinterpret_cast<double *>(z);
     const int tid = threadIdx.x, nt = blockDim.x;
     const int T = lpb * N, half = N >> 1;
     const int line0 = blockIdx.x * lpb;
@@ -109,102 +68,21 @@ __global__ __launch_bounds__(kDctThreads) void dct_lines_kernel(double *X, long 
             a = *reinterpret_cast<const double2 *>(pa);
             b = *reinterpret_cast<const double2 *>(pa + plane);
         }
-        if (KIND == 0) {
-            // v_m = x_2m, v_{N-1-m} = x_{2m+1}; u_j = (v_2j, v_{2j+1}) is v itself
-            double *vx = zd + 2 * (long)l * N, *vy = vx + N;
-            vx[m] = a.x;
-            vx[N - 1 - m] = a.y;
-            vy[m] = b.x;
-            vy[N - 1 - m] = b.y;
-        } else {
-            z[l * N + m] = a;  // C in natural order
-            z[l * N + half + m] = b;
-        }
+        dct_put<KIND, 0>(z, l, m, N, a, b);
     }
     __syncthreads();
-    if (KIND == 1) {
-        // U_k of each plane from its C, stored with real and imaginary parts
-        // swapped; every lane reads its inputs before any lane overwrites them
-        constexpr int kPer = kDctMaxN / kDctThreads;  // T / nt at most
-        double2 ur[kPer];
-#pragma unroll
-        for (int q = 0; q < kPer; q++) {
-            const int g = tid + q * nt;
-            if (g < T) {
-                const int l = g >> logN, r = g & (N - 1), pl = r >> (logN - 1), k = r & (half - 1);
-                const double *C = zd + 2 * (long)l * N + (long)pl * N;
-                const double2 vk = dct_inv_v(C, tw, k, N), vh = dct_inv_v(C, tw, half - k, N);
-                const double2 s = make_double2(vk.x + vh.x, vk.y - vh.y);  // V_k + conj V_{N/2-k}
-                const double2 d = make_double2(vk.x - vh.x, vk.y + vh.y);  // V_k - conj V_{N/2-k}
-                const double2 w = tw[k];
-                const double px = d.x * w.x + d.y * w.y, py = d.y * w.x - d.x * w.y;  // d conj(w^k)
-                ur[q] = make_double2(s.y + px, s.x - py);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < kPer; q++) {
-            const int g = tid + q * nt;
-            if (g < T) z[g] = ur[q];  // line l, plane pl, k: l * N + pl * N/2 + k = g
-        }
-        __syncthreads();
-    }
-
-    // forward FFT of every half-length line, in place
-    int M = half, logQ = logN - 3;
-    for (; M >= 4; M >>= 2, logQ -= 2) {
-        const int Q = M >> 2, step = N / M;
-        for (int t = tid; t < (T >> 2); t += nt) {
-            const int j = t & (Q - 1), base = ((t >> logQ) * M) + j;
-            const double2 x0 = z[base], x1 = z[base + Q], x2 = z[base + 2 * Q],
-                          x3 = z[base + 3 * Q];
-            const double2 t0 = make_double2(x0.x + x2.x, x0.y + x2.y);
-            const double2 t1 = make_double2(x0.x - x2.x, x0.y - x2.y);
-            const double2 t2 = make_double2(x1.x + x3.x, x1.y + x3.y);
-            const double2 t3 = make_double2(x1.y - x3.y, x3.x - x1.x);  // -i (x1 - x3)
-            z[base] = make_double2(t0.x + t2.x, t0.y + t2.y);
-            z[base + Q] = cmul(make_double2(t1.x + t3.x, t1.y + t3.y), tw[j * step]);
-            z[base + 2 * Q] = cmul(make_double2(t0.x - t2.x, t0.y - t2.y), tw[2 * j * step]);
-            z[base + 3 * Q] = cmul(make_double2(t1.x - t3.x, t1.y - t3.y), tw[3 * j * step]);
-        }
-        __syncthreads();
-    }
-    if (M == 2) {
-        for (int t = tid; t < (T >> 1); t += nt) {
-            const double2 a = z[2 * t], b = z[2 * t + 1];
-            z[2 * t] = make_double2(a.x + b.x, a.y + b.y);
-            z[2 * t + 1] = make_double2(a.x - b.x, a.y - b.y);
-        }
-        __syncthreads();
-    }
+    constexpr int kPer = kDctMaxN / kDctThreads;  // T / nt at most
+    if (KIND == 1) dct_inv_pre<0, kPer>(z, T, N, logN, tw, tid, nt);
+    dct_fft<0>(z, T, N, logN, tw, tid, nt);
 
     // store two elements per plane per lane
     for (int g = tid; g < (T >> 1); g += nt) {
         const int l = g >> (logN - 1), m = g & (half - 1);
         if (line0 + l >= nlines) continue;
-        const double2 *zx = z + l * N, *zy = zx + half;
         const long off = (long)(line0 + l) * P + 2 * m;
         double ya[2], yb[2];
-        if (KIND == 0) {
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                ya[e] = dct_fwd_out(zx, tw, 2 * m + e, N);
-                yb[e] = dct_fwd_out(zy, tw, 2 * m + e, N);
-            }
-            if (E) {
-                const double2 ev = *reinterpret_cast<const double2 *>(E + off);
-                ya[0] *= ev.x;
-                ya[1] *= ev.y;
-                yb[0] *= ev.x;
-                yb[1] *= ev.y;
-            }
-        } else {
-            // x_2m = v_m, x_{2m+1} = v_{N-1-m}
-            ya[0] = dct_inv_out(zx, m, half);
-            ya[1] = dct_inv_out(zx, N - 1 - m, half);
-            yb[0] = dct_inv_out(zy, m, half);
-            yb[1] = dct_inv_out(zy, N - 1 - m, half);
-        }
+        dct_get<KIND, 0>(z, l, m, N, tw, ya, yb);
+        if (KIND == 0 && E) dct_scale(ya, yb, *reinterpret_cast<const double2 *>(E + off));
         *reinterpret_cast<double2 *>(X + off) = make_double2(ya[0], ya[1]);
         *reinterpret_cast<double2 *>(X + off + plane) = make_double2(yb[0], yb[1]);
     }

@@ -1,8 +1,8 @@
-// of2d_batch.h — B independent Horn-Schunck or Thirion's Demons registrations
-// of one size in one call, and the deformation analysis of their motions
-// (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
-// batch_demons_kernels.hip, batch_demons_lds_kernels.hip,
-// batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the host
+// of2d_batch.h — B independent Horn-Schunck, Curvature or Thirion's Demons
+// registrations of one size in one call, and the deformation analysis of their
+// motions (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
+// batch_curvature_kernels.hip, batch_demons_kernels.hip,
+// batch_demons_lds_kernels.hip, batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the host
 // arithmetic: batch_plan.h).
 //
 // Layout: the B fields of a pyramid level live in one allocation, pair k at
@@ -26,6 +26,7 @@
 #include "batch_loop.h"
 #include "batch_plan.h"
 #include "of2d_device.h"
+#include "of2d_host.h"
 
 namespace of2d {
 namespace batch {
@@ -47,6 +48,25 @@ struct LoopArgs : LoopCommon {
 // conv: Logger sums, errors and the reference's break (fp64 sums in a fixed
 // order: the logger_fp64 semantics); otherwise exactly niter iterations
 void launch_hs_loop(const LoopArgs &a, int B, bool conv, hipStream_t st);
+
+// Curvature (batch_curvature_kernels.hip): the pair's whole
+// loop of OpticalFlowCurvature::get_update with the fast line transforms, the
+// fp64 plane pair in the pair's slice of X.  curv_level_ok(dx, dy) must hold
+struct CurvLoopArgs : LoopCommon {
+    const float2 *dI;
+    const float *It;
+    double *X;           // scratch: [B][curv_scratch_doubles(dx, dy)]
+    long sx;             // X's pair stride in doubles
+    const double *E;     // the level's eigenvalues, element (p, q) at p + q * dx
+    const double2 *twx;  // dct_table(dx), dct_table(dy)
+    const double2 *twy;
+    float tau;
+    float div;           // 4.0f * sizein
+    int logx, logy;      // log2 of dx, dy
+    int lx, ly;          // lines per chunk of a pass along x, along y (curv_chunk_lines)
+};
+// conv as launch_hs_loop's
+void launch_curv_loop(const CurvLoopArgs &a, int B, bool conv, hipStream_t st);
 
 // ---- option "resident" (batch_resident_kernels.hip): the
 // same loop with the pair's iterate in LDS and dI, It in registers across the
@@ -215,6 +235,9 @@ struct BLevel {
     // Demons: It holds the image warped by the iterate and dI the correction;
     // mid (Demons only) the motion before the sigma_diffusion smoothing
     BField<float2> mid;
+    // Curvature only: the pairs' fp64 scratch, and the tables every pair
+    // shares (eigenvalues, dense; dct_table of each axis)
+    DevArray<double> cX, cE, ctwx, ctwy;
     int mcur = 0;
 };
 
@@ -330,6 +353,7 @@ class Batch {
     int reg_;
     std::vector<float> params_;
     float alpha_ = 0.0f;
+    float tau_ = 1.0f;  // Curvature (OpticalFlowCurvature.h:8)
     // Demons: the two Gaussian tables (sigma_fluid, then sigma_diffusion), as
     // Registration's DemonsKernels
     std::vector<double> kfluid_, kdiff_;

@@ -369,6 +369,11 @@ std::vector<float> gaussian_marginals(const std::vector<double> &k, int kw);
 // the weight sum of a pixel whose taps are all valid, in the reference's
 // summation order (Field.tpp:242-256)
 double full_weight(const std::vector<double> &k, int kw);
+// Curvature's eigenvalues 1 / (1 + tau alpha (-4 + 2 cos(p pi / nx) + 2 cos(q pi
+// / ny))^2) in the reference's float/double expression
+// (OpticalFlowCurvature.cpp:6-30), element (p, q) at p + q * ld, the rest 0:
+// the one-pair level's table (ld = its pitch) and the batch's (ld = nx)
+std::vector<double> curvature_eigenvalues(int nx, int ny, int ld, float alpha, float tau);
 // launch_motion_exp's bound on the squaring count for Demons' parameters
 int exp_squarings_bound(float sigma_isq, float sigma_xsq);
 

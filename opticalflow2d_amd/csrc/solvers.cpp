@@ -338,6 +338,19 @@ int Registration::loop_elastic(Level &L, int niter, int &final_buf) {
     return niter;
 }
 
+std::vector<double> curvature_eigenvalues(int nx, int ny, int ld, float alpha, float tau) {
+    const double PI_ = 3.14159265;  // OpticalFlowCurvature.cpp:4
+    std::vector<double> h((size_t)ld * ny, 0.0);
+    const float ta = tau * alpha;
+    for (int p = 0; p < nx; p++)
+        for (int q = 0; q < ny; q++) {
+            const double lam = -4 + 2 * std::cos((unsigned)p * PI_ / (unsigned)nx) +
+                               2 * std::cos((unsigned)q * PI_ / (unsigned)ny);
+            h[p + (size_t)q * ld] = 1.0f / (1.0f + ta * std::pow(lam, 2));
+        }
+    return h;
+}
+
 // Curvature (OpticalFlowCurvature.cpp:144-167) inside the ImageRegistrationOpticalFlow
 // loop.  The transform tables and eigenvalues depend only on the level's
 // dimensions and the parameters, so they are built once per level on the host
@@ -350,7 +363,6 @@ void build_curvature(Level &L, float alpha, float tau, int dct, hipStream_t st) 
     const bool fx = dct && dct_fast_length(n0), fy = dct && dct_fast_length(n1);
     const int path = (fx ? 1 : 0) | (fy ? 2 : 0);
     if (L.cE.p && L.cpath == path) return;
-    const double PI_ = 3.14159265;  // OpticalFlowCurvature.cpp:4
     std::vector<double> h;
     auto upload = [&](DevArray<double> &d) {
         d.alloc(h.size());
@@ -399,15 +411,7 @@ void build_curvature(Level &L, float alpha, float tau, int dct, hipStream_t st) 
         upload(L.cD0);
     }
     if (!L.cE.p) {
-        // eigenvalues 1 / (1 + tau alpha (-4 + 2 cos(p pi / nx) + 2 cos(q pi / ny))^2)
-        h.assign((size_t)P * n1, 0.0);
-        const float ta = tau * alpha;
-        for (int p = 0; p < n0; p++)
-            for (int q = 0; q < n1; q++) {
-                const double lam = -4 + 2 * std::cos((unsigned)p * PI_ / (unsigned)n0) +
-                                   2 * std::cos((unsigned)q * PI_ / (unsigned)n1);
-                h[p + (size_t)q * P] = 1.0f / (1.0f + ta * std::pow(lam, 2));
-            }
+        h = curvature_eigenvalues(n0, n1, P, alpha, tau);
         upload(L.cE);
     }
     L.cpath = path;
