@@ -9,9 +9,10 @@ With --reg 3 the registrations are Thirion's Demons (parameters 1, 0.25, 1.5,
 option of that name: Diffeomorphic Demons, every frame with its own number of
 squarings per iteration.  With --reg 1 they are Curvature registrations (alpha
 0.05, tau 50; --size must then be a power of two from 16 to 512, as must its
-half, the coarser level).
+half, the coarser level).  With --reg 2 they are Elastic registrations (mu
+0.05, lambda 0.02, omega 1.5; any size).
 
-    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 1|3]
+    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 1|2|3]
                                   [--diffeomorphic] [--resident] [--conv-lds] [--report]
                                   [--track T]
 
@@ -47,8 +48,8 @@ from opticalflow2d_amd import BatchRegistration  # noqa: E402
 from opticalflow2d_amd import synthetic as S  # noqa: E402
 
 
-# the parameters of --reg 1 and 3; --reg 0 takes --alpha
-REG_PARAMS = {0: None, 1: [0.05, 50.0], 3: [1.0, 0.25, 1.5, 2.5, 5, 0]}
+# the parameters of --reg 1, 2 and 3; --reg 0 takes --alpha
+REG_PARAMS = {0: None, 1: [0.05, 50.0], 2: [0.05, 0.02, 1.5], 3: [1.0, 0.25, 1.5, 2.5, 5, 0]}
 
 
 def options_of(a):
@@ -92,8 +93,8 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--niter", type=int, default=300)
     ap.add_argument("--alpha", type=float, default=0.3)
-    ap.add_argument("--reg", type=int, default=0, choices=[0, 1, 3],
-                    help="0 Horn-Schunck (alpha), 1 Curvature, 3 Thirion's Demons")
+    ap.add_argument("--reg", type=int, default=0, choices=[0, 1, 2, 3],
+                    help="0 Horn-Schunck (alpha), 1 Curvature, 2 Elastic, 3 Thirion's Demons")
     ap.add_argument("--diffeomorphic", action="store_true",
                     help="with --reg 3: Diffeomorphic Demons (the option 'diffeomorphic')")
     ap.add_argument("--resident", action="store_true",

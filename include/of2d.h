@@ -367,6 +367,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
 
 /* ---- batched Horn-Schunck and Thirion's Demons: many small pairs of one
  * size in one call ----
+ * (Curvature and Elastic: their own paragraphs below.)
  * nbatch independent registrations with the same parameters, reg =
  * OF2D_REG_DIFFUSION (regparams = {alpha}) or OF2D_REG_THIRIONS_DEMONS
  * (regparams = {sigma_i, sigma_x, sigma_diffusion, sigma_fluid, kernel_width,
@@ -397,10 +398,11 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  *
  * of2d_batch_create refuses with OF2D_ERR_INVALID_ARGUMENT and a message
  * (of2d_batch_last_error(NULL)), before any device work: nbatch < 1 or > 65535,
- * a reg other than OF2D_REG_DIFFUSION, OF2D_REG_CURVATURE and
+ * a reg other than OF2D_REG_DIFFUSION, OF2D_REG_CURVATURE, OF2D_REG_ELASTIC and
  * OF2D_REG_THIRIONS_DEMONS, a Curvature batch with a pyramid level whose side
- * is not a power of two in [OF2D_DCT_NMIN, OF2D_BATCH_CURV_NMAX] (the same
- * sentence as for a refused method: it names the three and the rule), nparams
+ * is not a power of two in [OF2D_DCT_NMIN, OF2D_BATCH_CURV_NMAX] and an Elastic
+ * batch with nparams != 3 (the same sentence as for a refused method: it names
+ * the four and their rules), nparams
  * != 1 (Diffusion), != 1 and != 2 (Curvature) or != 6 (Demons; the reference's
  * message), a Demons kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
@@ -424,6 +426,28 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * "conv_lds" and "diffeomorphic" are refused as on any batch of another method.
  * of2d_batch_info reports placement 0 at every level, 512 threads, and the
  * launches of a Diffusion batch (4 per loop).
+ *
+ * Elastic (reg = OF2D_REG_ELASTIC, regparams = {mu, lambda, omega}, nparams =
+ * 3): at every size the batch takes, with no rule of its own (a level with a
+ * side below 3 has no interior pixel and its sweep changes nothing, as in the
+ * one-pair path).  One workgroup runs a pair's whole loop of
+ * OpticalFlowElastic::get_update: per iteration the force into a per-pair
+ * scratch field, and the SOR sweep in place in the reference's order (column
+ * after column, row after row within a column), run as the wavefront 2 i + j =
+ * t with one thread per column and one workgroup barrier per step, none at a
+ * level of 64 columns or fewer.  With "fixed_iters" 1 every pair's motion, warp
+ * and iteration counts are those of of2d_create(reg 2) with "fixed_iters" 1 on
+ * that pair alone, bit for bit.  of2d_create's two-parameter form {mu, lambda}
+ * (omega = 0.66f, OpticalFlowElastic.h:9) stays refused here, with the sentence
+ * that refuses a method: the batch has refused reg 2 with two parameters by
+ * that sentence since it exists, and a caller writes the third one out
+ * (opticalflow2d_amd.BatchRegistration appends it).  Elastic has no division:
+ * every pair's status is OF2D_OK.  "fixed_iters", "device" and "warm_start"
+ * apply; "resident", "conv_lds" and "diffeomorphic" are refused as on any batch
+ * of another method.  of2d_batch_info reports placement 0 at every level, per
+ * level min(roundup(dx, 64), 512) threads, and the launches of a Diffusion
+ * batch (4 per loop).  OF2D_REG_FLUID and OF2D_REG_DIFFEOMORPHIC_DEMONS are not
+ * batched.
  *
  * "diffeomorphic" (0, the default, or 1): Diffeomorphic Demons.  With 1, a
  * batch created with reg = OF2D_REG_THIRIONS_DEMONS and accumulation 0
@@ -475,7 +499,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * the kernel its LDS, every level runs as with 0 (placement 0) and nothing is
  * reported as an error.  Composes with "fixed_iters", "warm_start" and
  * "device".  Refused with OF2D_ERR_INVALID_ARGUMENT, the handle still usable
- * and the option unchanged: on a Demons or Curvature batch ("resident: the batch is not a
+ * and the option unchanged: on a Demons, Curvature or Elastic batch ("resident: the batch is not a
  * Diffusion batch") and for a value other than 0 or 1 ("resident: the value
  * must be 0 or 1").
  *
@@ -495,7 +519,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * (placement 0) and nothing is reported as an error.  Composes with
  * "fixed_iters", "warm_start", "device" and "diffeomorphic".  Refused with
  * OF2D_ERR_INVALID_ARGUMENT, the handle still usable and the option
- * unchanged: on a Diffusion or Curvature batch ("conv_lds: the batch is not a Thirion's
+ * unchanged: on a Diffusion, Curvature or Elastic batch ("conv_lds: the batch is not a Thirion's
  * Demons batch") and for a value other than 0 or 1 ("conv_lds: the value must
  * be 0 or 1").
  *

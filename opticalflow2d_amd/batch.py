@@ -1,8 +1,8 @@
-"""Batched Horn-Schunck, Curvature and Thirion's Demons: many small image pairs
-of one size in one call.
+"""Batched Horn-Schunck, Curvature, Elastic and Thirion's Demons: many small
+image pairs of one size in one call.
 
 :class:`BatchRegistration` is the object-style handle on ``of2d_batch_*``
-(include/of2d.h): ``nbatch`` independent Diffusion, Curvature or Thirion's Demons
+(include/of2d.h): ``nbatch`` independent Diffusion, Curvature, Elastic or Thirion's Demons
 registrations with the same parameters, each run by one workgroup with the
 whole iteration loop inside the kernel.  Arrays follow :class:`ImageRegistration`'s convention with a leading
 pair axis: an image is ``[dimx, dimy]`` (x first), a stack of them
@@ -32,7 +32,12 @@ class BatchRegistration:
     parameter), ``Regularisation.Curvature`` (1; ``alpha`` is ``[alpha]`` with
     tau = 1 or ``[alpha, tau]``, and both sides of every pyramid level must be
     powers of two from 8 to 512: per pair the one-pair ``curvature_dct=1``
-    registration, bit for bit with ``fixed_iters=1``) or
+    registration, bit for bit with ``fixed_iters=1``),
+    ``Regularisation.Elastic`` (2; ``alpha`` is ``[mu, lambda, omega]``, or
+    ``[mu, lambda]``, to which this class appends the reference's default
+    omega ``np.float32(0.66)`` itself: ``of2d_batch_create`` takes the three
+    only; per pair the one-pair Elastic registration, bit for bit with
+    ``fixed_iters=1``, at any size the batch takes) or
     ``Regularisation.ThirionsDemons`` (3), for which ``alpha``
     carries the one-pair path's six parameters ``[sigma_i, sigma_x,
     sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
@@ -73,6 +78,8 @@ class BatchRegistration:
         if nit.size < nscales + 1:
             raise ValueError("niter needs nscales+1 entries")
         p = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32).reshape(-1))
+        if self.reg == Regularisation.Elastic and p.size == 2:
+            p = np.append(p, np.float32(0.66))  # OpticalFlowElastic.h:9
         self._h = None
         h = C.c_void_p()
         st = L.of2d_batch_create(C.byref(h), self.nbatch, self.dimx, self.dimy, nit,

@@ -1,6 +1,6 @@
-// batch.cpp — host driver of the batched Horn-Schunck, Curvature and Thirion's
-// Demons registrations (of2d_batch.h).  The pyramid and refine sequence is that
-// of Registration::estimate / estimate_level for Diffusion, Curvature and
+// batch.cpp — host driver of the batched Horn-Schunck, Curvature, Elastic and
+// Thirion's Demons registrations (of2d_batch.h).  The pyramid and refine sequence is that
+// of Registration::estimate / estimate_level for Diffusion, Curvature, Elastic and
 // Thirion's Demons (registration.cpp; Demons takes no gradients pass: its loop warps and
 // differentiates the moving image itself),
 // applied to all pairs at once: the host enqueues every level's launches and
@@ -24,11 +24,15 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
     if (nbatch > kMaxPairs)
         throw std::invalid_argument("Error: batch takes at most 65535 pairs per call\n");
     // one sentence for every refusal by method; a Curvature batch whose levels
-    // do not all qualify gets it too (below)
+    // do not all qualify gets it too (below), and Elastic without its omega:
+    // the reference's two-parameter form (omega = 0.66f) is the caller's to
+    // spell out (include/of2d.h)
     static const char *const kMethods =
         "Error: the batched registration supports Diffusion regularisation only, Thirion's "
-        "Demons, or Curvature where every level's sides are powers of two from 8 to 512\n";
-    if (reg != 0 && reg != 1 && reg != 3) throw std::invalid_argument(kMethods);
+        "Demons, Curvature where every level's sides are powers of two from 8 to 512, or "
+        "Elastic with its three parameters [mu, lambda, omega]\n";
+    if (reg != 0 && reg != 1 && reg != 2 && reg != 3) throw std::invalid_argument(kMethods);
+    if (reg == 2 && nparams != 3) throw std::invalid_argument(kMethods);
     if (!valid_regularisation_parameters(reg, nparams))
         throw std::invalid_argument(
             "Invalid number of regularisation parameters for given regularisation method.\n");
@@ -47,6 +51,8 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
         if (kw < 1) throw std::invalid_argument("Error: Demons kernel width must be >= 1\n");
         kdiff_ = gaussian_kernel(kw, params[2]);
         kfluid_ = gaussian_kernel(kw, params[3]);
+    } else if (reg == 2) {
+        sor_ = sor_coef(params[0], params[1], params[2]);
     } else {
         alpha_ = params[0];
         if (reg == 1 && nparams == 2) tau_ = params[1];  // else OpticalFlowCurvature.h:8
@@ -181,6 +187,7 @@ void Batch::allocate_device() {
         L.est[0].alloc(L.dx, L.dy, B_);
         L.est[1].alloc(L.dx, L.dy, B_);
         if (reg_ == 3) L.mid.alloc(L.dx, L.dy, B_);
+        if (reg_ == 2) L.force.alloc(L.dx, L.dy, B_);
         if (reg_ == 1) {
             // the level's tables by the one-pair path's own builders
             // (solvers::build_curvature), E dense
@@ -362,7 +369,7 @@ void Batch::estimate() {
             // *Iaux = *Imov; Iaux->warp2d(*motion)
             launch_warp(L.Imov.p, L.motion[L.mcur].p, L.Iaux.p, L.stride, L.dx, L.dy, L.P, B_,
                         d_status_, st_);
-            if (reg_ == 0 || reg_ == 1)
+            if (reg_ != 3)
                 launch_gradients(L.Iref.p, shared_ ? 0 : L.stride, L.Iaux.p, L.dI.p, L.It.p,
                                  L.stride, L.dx, L.dy, L.P, B_, d_status_, st_);
             // motion_est starts at zero
@@ -452,6 +459,13 @@ void Batch::launch_loop(int s, int loop, bool conv) {
         a.lx = curv_chunk_lines(L.dx, L.dy);
         a.ly = curv_chunk_lines(L.dy, L.dx);
         launch_curv_loop(a, B_, conv, st_);
+    } else if (reg_ == 2) {
+        ElasticLoopArgs a{c};
+        a.dI = L.dI.p;
+        a.It = L.It.p;
+        a.f = L.force.p;
+        a.k = sor_;
+        launch_elastic_loop(a, B_, conv, st_);
     } else {
         LoopArgs a{c};
         a.dI = L.dI.p;
@@ -750,7 +764,7 @@ std::vector<int> Batch::info() const {
         // 0: every field of the loop in global memory; 1: the iterate
         // (resident) or the convolved field (conv_lds) stays on the CU
         v.push_back(s < (int)placement_.size() ? placement_[s] : 0);
-        v.push_back(reg_ == 1 ? kCurvThreads : kLoopThreads);
+        v.push_back(reg_ == 1 ? kCurvThreads : reg_ == 2 ? elastic_threads(ldx_[s]) : kLoopThreads);
     }
     return v;
 }

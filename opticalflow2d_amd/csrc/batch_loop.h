@@ -1,8 +1,9 @@
-// batch_loop.h — the frame the batch's five loop kernels share (hs_loop_kernel,
-// hs_resident_kernel, demons_loop_kernel, demons_lds_kernel, curv_loop_kernel;
-// DESIGN.md §4.6).
+// batch_loop.h — the frame the batch's six loop kernels share (hs_loop_kernel,
+// hs_resident_kernel, demons_loop_kernel, demons_lds_kernel, curv_loop_kernel,
+// elastic_loop_kernel).
 //
-// One workgroup of kLoopThreads (Curvature: kCurvThreads) runs the whole loop of pair blockIdx.x:
+// One workgroup of kLoopThreads (Curvature: kCurvThreads; Elastic:
+// elastic_threads(dx)) runs the whole loop of pair blockIdx.x:
 //   entry   loop_entry: the pair's iters and errs slots; a pair whose status
 //           has kStatusDivZero from an earlier loop runs nothing and reports 0
 //           iterations

@@ -155,6 +155,40 @@ inline size_t curv_lds_bytes(int dx, int dy) {
     return std::max(curv_chunk_bytes(dx, dy), curv_chunk_bytes(dy, dx));
 }
 
+// ---- the Elastic loop (batch_elastic_kernels.hip).  The
+// SOR sweep relaxes i-outer, j-inner in place, so pixel (i, j) depends on
+// pixels of smaller 2 i + j only and every pixel with 2 i + j = t can be
+// relaxed at once: step t of the sweep.  A pair's workgroup has one thread per
+// column up to kElasticMaxWaves waves; in a wider level thread tid takes the
+// columns tid, tid + T, ...  (constexpr: the kernel calls these too)
+constexpr int kElasticMaxWaves = 8;
+constexpr int elastic_waves(int dx) {
+    const int w = (dx + 63) / 64;
+    return w < 1 ? 1 : (w > kElasticMaxWaves ? kElasticMaxWaves : w);
+}
+constexpr int elastic_threads(int dx) { return 64 * elastic_waves(dx); }
+// the sweep's steps are t = kElasticFirstStep (pixel (1, 1)) ...
+// elastic_last_step (pixel (dx - 2, dy - 2)); none when a side is below 3
+constexpr int kElasticFirstStep = 3;
+constexpr int elastic_last_step(int dx, int dy) {
+    return (dx < 3 || dy < 3) ? kElasticFirstStep - 1 : 2 * (dx - 2) + (dy - 2);
+}
+// the columns with an interior row at step t: 1 <= t - 2 i <= dy - 2 and
+// 1 <= i <= dx - 2, that is [elastic_col_lo, elastic_col_hi] (empty when lo > hi)
+constexpr int elastic_col_lo(int t, int dy) {
+    const int lo = (t - dy + 3) >> 1;  // ceil((t - (dy - 2)) / 2), an arithmetic shift
+    return lo < 1 ? 1 : lo;
+}
+constexpr int elastic_col_hi(int t, int dx) {
+    const int hi = (t - 1) >> 1;
+    return hi > dx - 2 ? dx - 2 : hi;
+}
+// thread tid's first column at or after lo: the next ones are T further on
+constexpr int elastic_first_col(int tid, int lo, int T) {
+    const int r = tid - lo % T;
+    return lo + (r < 0 ? r + T : r);
+}
+
 // nullptr or why the call is refused (the one-pair entries' wording)
 inline const char *jacobian_refusal(int dimx, int dimy) {
     if (dimx < 2 || dimy < 2) return "jacobian: the field needs dimx >= 2 and dimy >= 2";

@@ -484,6 +484,8 @@ __global__ __launch_bounds__(kInc ? 256 : 64) void sor_strip_kernel(float4 *__re
         LU = v2f{SOR_SHR(G.x, D.x), SOR_SHR(G.y, D.y)};
         G = Gn;
         // OpticalFlowFluid.cpp:27-35, same association, no contraction
+        // (sor_px.h holds these lines for the kernels without this window:
+        // keep the two the same)
         const v2f RL = R + L;
         const v2f s1v = (RL + U) + D;
         const v2f t = ((RU - LU) - RD) + LD;

@@ -1,7 +1,7 @@
-// of2d_batch.h — B independent Horn-Schunck, Curvature or Thirion's Demons
-// registrations of one size in one call, and the deformation analysis of their
-// motions (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
-// batch_curvature_kernels.hip, batch_demons_kernels.hip,
+// of2d_batch.h — B independent Horn-Schunck, Curvature, Elastic or Thirion's
+// Demons registrations of one size in one call, and the deformation analysis of
+// their motions (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
+// batch_curvature_kernels.hip, batch_elastic_kernels.hip, batch_demons_kernels.hip,
 // batch_demons_lds_kernels.hip, batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the host
 // arithmetic: batch_plan.h).
 //
@@ -27,6 +27,7 @@
 #include "batch_plan.h"
 #include "of2d_device.h"
 #include "of2d_host.h"
+#include "sor_px.h"
 
 namespace of2d {
 namespace batch {
@@ -67,6 +68,20 @@ struct CurvLoopArgs : LoopCommon {
 };
 // conv as launch_hs_loop's
 void launch_curv_loop(const CurvLoopArgs &a, int B, bool conv, hipStream_t st);
+
+// Elastic (batch_elastic_kernels.hip): the pair's whole loop
+// of OpticalFlowElastic::get_update, the force in the pair's slice of f and the
+// SOR sweep in place on the iterate's output buffer, step after step of the
+// reference's order (batch_plan.h, elastic_last_step).  The workgroup has
+// elastic_threads(dx) threads
+struct ElasticLoopArgs : LoopCommon {
+    const float2 *dI;
+    const float *It;
+    float2 *f;  // scratch: the force, a field per pair
+    SorCoef k;  // sor_coef(mu, lambda, omega)
+};
+// conv as launch_hs_loop's
+void launch_elastic_loop(const ElasticLoopArgs &a, int B, bool conv, hipStream_t st);
 
 // ---- option "resident" (batch_resident_kernels.hip): the
 // same loop with the pair's iterate in LDS and dI, It in registers across the
@@ -238,6 +253,8 @@ struct BLevel {
     // Curvature only: the pairs' fp64 scratch, and the tables every pair
     // shares (eigenvalues, dense; dct_table of each axis)
     DevArray<double> cX, cE, ctwx, ctwy;
+    // Elastic only: the force of the iteration under way
+    BField<float2> force;
     int mcur = 0;
 };
 
@@ -354,6 +371,7 @@ class Batch {
     std::vector<float> params_;
     float alpha_ = 0.0f;
     float tau_ = 1.0f;  // Curvature (OpticalFlowCurvature.h:8)
+    SorCoef sor_{};     // Elastic: the sweep's constants of {mu, lambda, omega}
     // Demons: the two Gaussian tables (sigma_fluid, then sigma_diffusion), as
     // Registration's DemonsKernels
     std::vector<double> kfluid_, kdiff_;
