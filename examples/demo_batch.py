@@ -10,9 +10,12 @@ option of that name: Diffeomorphic Demons, every frame with its own number of
 squarings per iteration.  With --reg 1 they are Curvature registrations (alpha
 0.05, tau 50; --size must then be a power of two from 16 to 512, as must its
 half, the coarser level).  With --reg 2 they are Elastic registrations (mu
-0.05, lambda 0.02, omega 1.5; any size).
+0.05, lambda 0.02, omega 1.5; any size).  With --reg 5 they are viscous-fluid
+registrations (mu 0.25, lambda 0, omega 0.9; the option "fluid" of an Elastic
+batch, which the class sets): the regrids of every frame are counted from the
+batch's log, and the reference's printed lines of the last frame are shown.
 
-    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 1|2|3]
+    python examples/demo_batch.py [--size 128] [--frames 64] [--niter 300] [--reg 1|2|3|5]
                                   [--diffeomorphic] [--resident] [--conv-lds] [--report]
                                   [--track T]
 
@@ -49,7 +52,8 @@ from opticalflow2d_amd import synthetic as S  # noqa: E402
 
 
 # the parameters of --reg 1, 2 and 3; --reg 0 takes --alpha
-REG_PARAMS = {0: None, 1: [0.05, 50.0], 2: [0.05, 0.02, 1.5], 3: [1.0, 0.25, 1.5, 2.5, 5, 0]}
+REG_PARAMS = {0: None, 1: [0.05, 50.0], 2: [0.05, 0.02, 1.5], 3: [1.0, 0.25, 1.5, 2.5, 5, 0],
+              5: [0.25, 0.0, 0.9]}
 
 
 def options_of(a):
@@ -93,8 +97,9 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--niter", type=int, default=300)
     ap.add_argument("--alpha", type=float, default=0.3)
-    ap.add_argument("--reg", type=int, default=0, choices=[0, 1, 2, 3],
-                    help="0 Horn-Schunck (alpha), 1 Curvature, 2 Elastic, 3 Thirion's Demons")
+    ap.add_argument("--reg", type=int, default=0, choices=[0, 1, 2, 3, 5],
+                    help="0 Horn-Schunck (alpha), 1 Curvature, 2 Elastic, 3 Thirion's Demons, "
+                         "5 Fluid")
     ap.add_argument("--diffeomorphic", action="store_true",
                     help="with --reg 3: Diffeomorphic Demons (the option 'diffeomorphic')")
     ap.add_argument("--resident", action="store_true",
@@ -132,6 +137,9 @@ def main():
         iters = b.iterations()
         warped = b.warp(frames)
         info = b.info()
+        if a.reg == 5:
+            logs = [b.fluid_log(k) for k in range(B)]
+            last_lines = b.fluid_lines(B - 1)
         if a.report:
             _, stats = b.jacobian(jac=False)
             _, inv = b.inverse_motion()
@@ -151,6 +159,12 @@ def main():
     for k in range(B):
         print(f"{k + 1:5d}  ({shifts[k, 0]:5.2f}, {shifts[k, 1]:5.2f})  {str(iters[k].tolist()):>24}  "
               f"({mean[k, 0]:5.2f}, {mean[k, 1]:5.2f})     {before[k]:.4f} -> {after[k]:.4f}")
+    if a.reg == 5:
+        regrids = [int(sum(loop[:, 3].sum() for loop in log)) for log in logs]
+        print(f"regrids per frame: {regrids}")
+        print(f"frame {B}: the reference's lines, the last 3 of {len(last_lines)}")
+        for line in last_lines[-3:]:
+            print("  " + line)
     if a.report:
         folded = sum(s["folded"] > 0 for s in stats)
         print(f"folded pairs {folded} of {B}, worst min Jacobian {min(s['min'] for s in stats):.4f}")

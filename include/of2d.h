@@ -367,7 +367,7 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
 
 /* ---- batched Horn-Schunck and Thirion's Demons: many small pairs of one
  * size in one call ----
- * (Curvature and Elastic: their own paragraphs below.)
+ * (Curvature, Elastic and Fluid: their own paragraphs below.)
  * nbatch independent registrations with the same parameters, reg =
  * OF2D_REG_DIFFUSION (regparams = {alpha}) or OF2D_REG_THIRIONS_DEMONS
  * (regparams = {sigma_i, sigma_x, sigma_diffusion, sigma_fluid, kernel_width,
@@ -402,12 +402,12 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * OF2D_REG_THIRIONS_DEMONS, a Curvature batch with a pyramid level whose side
  * is not a power of two in [OF2D_DCT_NMIN, OF2D_BATCH_CURV_NMAX] and an Elastic
  * batch with nparams != 3 (the same sentence as for a refused method: it names
- * the four and their rules), nparams
+ * the four and their rules, and points to the option "fluid"), nparams
  * != 1 (Diffusion), != 1 and != 2 (Curvature) or != 6 (Demons; the reference's
  * message), a Demons kernel_width < 1 (of2d_create's message),
  * dimx * dimy > OF2D_BATCH_MAXPX, the sizes of2d_create refuses, NULL arrays.
  * Options: "fixed_iters", "device" (before first use), "diffeomorphic",
- * "warm_start", "resident", "conv_lds"; an
+ * "fluid", "warm_start", "resident", "conv_lds"; an
  * unknown key is refused ("demons_separable" among them: the batch smooths
  * with the direct convolution only).
  *
@@ -446,8 +446,47 @@ int of2d_quality(of2d_ctx *ctx, const double *Iref, const double *Imov, double *
  * apply; "resident", "conv_lds" and "diffeomorphic" are refused as on any batch
  * of another method.  of2d_batch_info reports placement 0 at every level, per
  * level min(roundup(dx, 64), 512) threads, and the launches of a Diffusion
- * batch (4 per loop).  OF2D_REG_FLUID and OF2D_REG_DIFFEOMORPHIC_DEMONS are not
- * batched.
+ * batch (4 per loop).  reg = OF2D_REG_FLUID and OF2D_REG_DIFFEOMORPHIC_DEMONS
+ * stay refused at create: each is an option of the batch whose parameters and
+ * loop it shares, "fluid" of an Elastic batch and "diffeomorphic" of a
+ * Thirion's Demons batch (below).
+ *
+ * "fluid" (0, the default, or 1): viscous fluid.  With 1, a batch created with
+ * reg = OF2D_REG_ELASTIC is per pair the one-pair of2d_create(OF2D_REG_FLUID,
+ * {mu, lambda, omega}) registration (omega = 0.66f is OpticalFlowFluid.h:10's
+ * default as it is Elastic's): ImageRegistrationFluid::
+ * estimate_motion_at_current_resolution with OpticalFlowFluid::get_update.  One
+ * workgroup runs the pair's whole loop: per iteration the force, the Elastic
+ * batch's SOR sweep on the pair's velocity, the increment with its maximum,
+ * the time step dt = 0.65f / maxabs, the integration (skipped where dt >=
+ * 65), the Logger sums, the minimum Jacobian of the new estimate, and, where
+ * that is below 0.5f, the regrid (the motion accumulates the estimate, the
+ * moving image is warped again and differentiated, the next iteration starts
+ * from a zero estimate) inside the kernel.  With "fixed_iters" 1 every pair's
+ * motion, warp, iteration counts and Dumax / Regridding record are those of
+ * that pair alone on the one-pair path, bit for bit; the break is off and the
+ * regrid stays on.  The next of2d_batch_estimate takes the value; with 0 the
+ * batch is the Elastic batch, bit for bit.  Fluid has no division: every
+ * pair's status is OF2D_OK.  "fixed_iters", "warm_start" and "device" compose
+ * with it; "resident", "conv_lds" and "diffeomorphic" stay refused as on any
+ * Elastic batch; of2d_batch_info reports what an Elastic batch reports.
+ * The velocity is a field per pair and pyramid level that outlives an
+ * estimate, as OpticalFlowFluid::velocity does: allocated by the first
+ * estimate that runs with "fluid" 1 (8 bytes per pixel, pair and level),
+ * carried across the refines of a level, zeroed at the start of every estimate
+ * with "warm_start" 0 (a fresh handle's bits) and carried over with
+ * "warm_start" 1 (a reused one-pair context, bit for bit), zeroed by
+ * of2d_batch_reset_motion and by a change of the option's value.
+ * of2d_batch_set_motion leaves it as it is, as of2d_set_motion does on the
+ * one-pair path (only of2d_reset_motion touches the velocity there).
+ * The batch prints nothing; the reference's lines are the record
+ * of2d_batch_fluid_log returns (below).
+ * Refused with OF2D_ERR_INVALID_ARGUMENT, the handle still usable and the
+ * option unchanged: on a batch of another method ("fluid: the batch is not an
+ * Elastic batch"), for a value other than 0 or 1 ("fluid: the value must be 0
+ * or 1"), and when a pyramid level has a side below 2 ("fluid: every level
+ * needs sides of at least 2": the Jacobian's one-sided differences need a
+ * neighbour).
  *
  * "diffeomorphic" (0, the default, or 1): Diffeomorphic Demons.  With 1, a
  * batch created with reg = OF2D_REG_THIRIONS_DEMONS and accumulation 0
@@ -548,8 +587,8 @@ int of2d_batch_get_motion(of2d_batch *b, double *out);
  * "warm_start" 1 and ignores it with 0.  No images are needed; the status of
  * the last estimate stays. */
 int of2d_batch_set_motion(of2d_batch *b, const double *motion);
-/* every level's motion back to zero: the next estimate, warm or not, gives a
- * fresh handle's bits */
+/* every level's motion back to zero, and with it the velocity of option
+ * "fluid": the next estimate, warm or not, gives a fresh handle's bits */
 int of2d_batch_reset_motion(of2d_batch *b);
 /* pair k's image (Imov: nbatch images) warped by pair k's motion */
 int of2d_batch_warp(of2d_batch *b, const double *Imov, double *out);
@@ -560,6 +599,16 @@ int of2d_batch_status(const of2d_batch *b, int *out);
 int of2d_batch_iterations(const of2d_batch *b, int *out, int cap);
 /* the errors of the pair's last loop (none with "fixed_iters"); returns their count */
 int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap);
+/* option "fluid": one record {maxabs, dt, jmin, regridded (0 or 1)} per
+ * iteration that pair's loop `loop` ran in the last estimate (loops in
+ * execution order, as of2d_batch_iterations'), up to cap records (4 floats
+ * each) into out; returns the number of records, 0 on a batch without "fluid"
+ * or before an estimate, -1 for a pair or loop outside the batch.  The
+ * reference prints "Dumax: 0.650\tMaxabs increment: maxabs\t Timestep: dt" per
+ * iteration and, after an iteration that regridded, "Regridding on iteration:
+ * it\tMin Jacobian: jmin".  The device buffer behind it is nbatch * loops *
+ * max(niter) records of 16 bytes and exists only with "fluid" 1. */
+int of2d_batch_fluid_log(const of2d_batch *b, int pair, int loop, float *out, int cap);
 /* info = {kernel launches of the last estimate, loops per pair, levels, device
  * time of the last estimate's loop kernels in microseconds, then per level from
  * level 0: the placement in the last estimate (0: global memory; 1: on the

@@ -114,6 +114,7 @@ PRODUCT_SIGNATURES = {
     "of2d_batch_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "of2d_batch_iterations": (C.c_int, [C.c_void_p, _i32p, C.c_int]),
     "of2d_batch_last_errors": (C.c_int, [C.c_void_p, C.c_int, _f32p, C.c_int]),
+    "of2d_batch_fluid_log": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _f32p, C.c_int]),
     "of2d_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "of2d_batch_destroy": (C.c_int, [C.c_void_p]),
     "of2d_batch_last_error": (C.c_char_p, [C.c_void_p]),

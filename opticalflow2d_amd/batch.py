@@ -1,8 +1,8 @@
-"""Batched Horn-Schunck, Curvature, Elastic and Thirion's Demons: many small
-image pairs of one size in one call.
+"""Batched Horn-Schunck, Curvature, Elastic, Fluid and Thirion's Demons: many
+small image pairs of one size in one call.
 
 :class:`BatchRegistration` is the object-style handle on ``of2d_batch_*``
-(include/of2d.h): ``nbatch`` independent Diffusion, Curvature, Elastic or Thirion's Demons
+(include/of2d.h): ``nbatch`` independent Diffusion, Curvature, Elastic, Fluid or Thirion's Demons
 registrations with the same parameters, each run by one workgroup with the
 whole iteration loop inside the kernel.  Arrays follow :class:`ImageRegistration`'s convention with a leading
 pair axis: an image is ``[dimx, dimy]`` (x first), a stack of them
@@ -37,13 +37,20 @@ class BatchRegistration:
     ``[mu, lambda]``, to which this class appends the reference's default
     omega ``np.float32(0.66)`` itself: ``of2d_batch_create`` takes the three
     only; per pair the one-pair Elastic registration, bit for bit with
-    ``fixed_iters=1``, at any size the batch takes) or
+    ``fixed_iters=1``, at any size the batch takes),
+    ``Regularisation.Fluid`` (5; ``alpha`` as Elastic's, the default omega
+    ``np.float32(0.66)`` appended likewise: the class creates the Elastic
+    handle, sets its option ``fluid=1`` and keeps ``reg == 5``; ``reg=2,
+    fluid=1`` is the same handle; every pyramid level needs sides of at least
+    2; per pair the one-pair Fluid registration with its regrids, bit for bit
+    with ``fixed_iters=1``; the batch prints nothing, :meth:`fluid_log` and
+    :meth:`fluid_lines` give the reference's Dumax / Regridding lines) or
     ``Regularisation.ThirionsDemons`` (3), for which ``alpha``
     carries the one-pair path's six parameters ``[sigma_i, sigma_x,
     sigma_diffusion, sigma_fluid, kernel_width, accumulation]``; every other
     method is refused.  The other keyword options map to
     ``of2d_batch_set_option``: ``fixed_iters``, ``device``, ``diffeomorphic``,
-    ``warm_start``, ``resident``, ``conv_lds``.  ``resident=1`` (Diffusion only, refused with
+    ``fluid``, ``warm_start``, ``resident``, ``conv_lds``.  ``resident=1`` (Diffusion only, refused with
     ``InvalidArgument`` otherwise) keeps a pair's iterate in LDS and its
     gradients in registers across the iterations at every pyramid level that
     fits (all up to 128 x 128; :meth:`info` reports ``placement`` 1 there);
@@ -78,12 +85,17 @@ class BatchRegistration:
         if nit.size < nscales + 1:
             raise ValueError("niter needs nscales+1 entries")
         p = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32).reshape(-1))
-        if self.reg == Regularisation.Elastic and p.size == 2:
-            p = np.append(p, np.float32(0.66))  # OpticalFlowElastic.h:9
+        # Fluid is the option "fluid" of an Elastic handle (include/of2d.h)
+        create_reg = self.reg
+        if self.reg == Regularisation.Fluid:
+            create_reg = int(Regularisation.Elastic)
+            options = dict(options, fluid=1)
+        if create_reg == Regularisation.Elastic and p.size == 2:
+            p = np.append(p, np.float32(0.66))  # OpticalFlowElastic.h:9, OpticalFlowFluid.h:10
         self._h = None
         h = C.c_void_p()
         st = L.of2d_batch_create(C.byref(h), self.nbatch, self.dimx, self.dimy, nit,
-                                 self.nscales, self.reg,
+                                 self.nscales, create_reg,
                                  p if p.size else np.zeros(1, np.float32),
                                  int(p.size), self.nrefine)
         check(st, L.of2d_batch_last_error(None).decode())
@@ -91,8 +103,12 @@ class BatchRegistration:
         self._device = None  # option "device": where motion_device allocates
         self.loops = (self.nscales + 1) * max(self.nrefine, 0)
         self._maxn = max(int(nit.max()), 1)  # a loop records at most niter errors
-        for k, v in options.items():
-            self.set_option(k, v)
+        try:
+            for k, v in options.items():
+                self.set_option(k, v)
+        except Exception:
+            self.close()
+            raise
 
     def _chk(self, st):
         check(st, _lib.lib().of2d_batch_last_error(self._h).decode())
@@ -188,8 +204,9 @@ class BatchRegistration:
         self._chk(_lib.lib().of2d_batch_set_motion(self._h, buf.ctypes.data))
 
     def reset_motion(self) -> None:
-        """Every pair's motion back to zero at every level: the next
-        :meth:`register`, warm or not, gives a fresh handle's result."""
+        """Every pair's motion back to zero at every level (Fluid: the velocity
+        too): the next :meth:`register`, warm or not, gives a fresh handle's
+        result."""
         self._chk(_lib.lib().of2d_batch_reset_motion(self._h))
 
     def warp(self, Imov, out=None):
@@ -317,6 +334,25 @@ class BatchRegistration:
         n = _lib.lib().of2d_batch_last_errors(self._h, int(pair), buf, buf.size)
         return buf[: max(n, 0)].copy()
 
+    def fluid_log(self, pair: int) -> list:
+        """Option ``fluid``: one ``float32 [n, 4]`` array per loop (execution
+        order, as :meth:`iterations`), a row ``[maxabs, dt, jmin, regridded]``
+        per iteration the pair's loop ran in the last :meth:`register`
+        (of2d_batch_fluid_log).  Empty arrays without the option."""
+        if not 0 <= int(pair) < self.nbatch:
+            raise ValueError(f"pair {pair} outside [0, {self.nbatch})")
+        out = []
+        for loop in range(self.loops):
+            buf = np.zeros(4 * self._maxn, np.float32)
+            n = _lib.lib().of2d_batch_fluid_log(self._h, int(pair), loop, buf, self._maxn)
+            out.append(buf[: 4 * max(n, 0)].reshape(-1, 4).copy())
+        return out
+
+    def fluid_lines(self, pair: int) -> list:
+        """The lines the reference prints for the pair, in its order, without
+        the newline (:func:`fluid_lines` of :meth:`fluid_log`)."""
+        return fluid_lines(self.fluid_log(pair))
+
     def status(self) -> np.ndarray:
         """``[nbatch]`` OF2D_OK (0) or OF2D_ERR_RUNTIME (2) per pair."""
         out = (C.c_int * self.nbatch)()
@@ -359,4 +395,30 @@ class BatchRegistration:
             pass
 
 
-__all__ = ["BatchRegistration", "BATCH_MAXPX"]
+def _c_float(v: float) -> str:
+    """``printf("%.3f", v)``: Python's ``%`` prints infinities and NaN as C does
+    ('inf', '-inf', 'nan')."""
+    return "%.3f" % float(v)
+
+
+def fluid_lines(log) -> list:
+    """The reference's printed lines from a Fluid log (a list with one ``[n, 4]``
+    array of ``[maxabs, dt, jmin, regridded]`` rows per loop, as
+    :meth:`BatchRegistration.fluid_log` returns): per iteration
+    ``"Dumax: %.3f\\tMaxabs increment: %.3f\\t Timestep: %.3f"`` with
+    ``(double)0.65f`` (OpticalFlowFluid.cpp), and after the Dumax line of an
+    iteration that regridded ``"Regridding on iteration: %d\\tMin Jacobian:
+    %.3f"`` with the iteration counted from 0 within its loop
+    (ImageRegistrationFluid.cpp:107-124).  A pure function of the log."""
+    dumax = float(np.float32(0.65))
+    lines = []
+    for rows in log:
+        for it, (maxabs, dt, jmin, regridded) in enumerate(np.asarray(rows, np.float32).reshape(-1, 4)):
+            lines.append("Dumax: %s\tMaxabs increment: %s\t Timestep: %s"
+                         % (_c_float(dumax), _c_float(maxabs), _c_float(dt)))
+            if regridded != 0:
+                lines.append("Regridding on iteration: %d\tMin Jacobian: %s" % (it, _c_float(jmin)))
+    return lines
+
+
+__all__ = ["BatchRegistration", "BATCH_MAXPX", "fluid_lines"]

@@ -1,4 +1,4 @@
-// batch.cpp — host driver of the batched Horn-Schunck, Curvature, Elastic and
+// batch.cpp — host driver of the batched Horn-Schunck, Curvature, Elastic, Fluid and
 // Thirion's Demons registrations (of2d_batch.h).  The pyramid and refine sequence is that
 // of Registration::estimate / estimate_level for Diffusion, Curvature, Elastic and
 // Thirion's Demons (registration.cpp; Demons takes no gradients pass: its loop warps and
@@ -30,7 +30,8 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
     static const char *const kMethods =
         "Error: the batched registration supports Diffusion regularisation only, Thirion's "
         "Demons, Curvature where every level's sides are powers of two from 8 to 512, or "
-        "Elastic with its three parameters [mu, lambda, omega]\n";
+        "Elastic with its three parameters [mu, lambda, omega] (Fluid is the option \"fluid\" of "
+        "such an Elastic batch)\n";
     if (reg != 0 && reg != 1 && reg != 2 && reg != 3) throw std::invalid_argument(kMethods);
     if (reg == 2 && nparams != 3) throw std::invalid_argument(kMethods);
     if (!valid_regularisation_parameters(reg, nparams))
@@ -87,6 +88,9 @@ void Batch::release_device() {
     if (d_status_) (void)hipFree(d_status_);
     if (d_iters_) (void)hipFree(d_iters_);
     if (d_errs_) (void)hipFree(d_errs_);
+    if (d_flog_) (void)hipFree(d_flog_);
+    d_flog_ = nullptr;
+    have_vel_ = false;
     if (d_kf_) (void)hipFree(d_kf_);
     if (d_kd_) (void)hipFree(d_kd_);
     d_kf_ = nullptr;
@@ -133,6 +137,25 @@ void Batch::set_option(const std::string &key, double v) {
         diffeo_ = flag_value(key, v);
     } else if (key == "warm_start") {
         warm_ = flag_value(key, v);
+    } else if (key == "fluid") {
+        // OpticalFlowFluid takes Elastic's parameters and relaxes its velocity
+        // with Elastic's sweep: an option of such a batch
+        if (reg_ != 2) throw std::invalid_argument("fluid: the batch is not an Elastic batch");
+        const bool on = flag_value(key, v);
+        // the Jacobian's one-sided differences need a neighbour
+        for (int s = 0; on && s <= nscales_; s++)
+            if (ldx_[s] < 2 || ldy_[s] < 2)
+                throw std::invalid_argument("fluid: every level needs sides of at least 2");
+        // a change of the value: the next estimate with it starts from a zero
+        // velocity
+        if (on != fluid_ && ready_ && have_vel_) {
+            DeviceScope scope;
+            OF2D_HIP(hipSetDevice(home_));
+            zero_velocity();
+            OF2D_HIP(hipStreamSynchronize(st_));
+        }
+        if (on != fluid_) h_flog_.clear();  // the log is the option's
+        fluid_ = on;
     } else if (key == "resident") {
         // the Horn-Schunck loop with the iterate on the CU at the levels that
         // fit (resident_fits)
@@ -338,6 +361,21 @@ void Batch::estimate() {
     if (!fixed_ && !d_errs_ && maxn_ > 0 && nloops_ > 0)
         OF2D_HIP(hipMalloc(&d_errs_, sizeof(float) * (size_t)B_ * nloops_ * maxn_));
     const bool conv = !fixed_;
+    const bool fluid = fluid_;
+    if (fluid) {
+        // the velocity, a field per pair and level that outlives the estimate
+        // (OpticalFlowFluid::velocity), and the log
+        if (!have_vel_) {
+            for (BLevel &L : lv_) L.vel.alloc(L.dx, L.dy, B_);
+            OF2D_HIP(hipDeviceSynchronize());  // null-stream memsets, as allocate_device's
+            have_vel_ = true;
+        }
+        if (!d_flog_ && maxn_ > 0 && nloops_ > 0)
+            OF2D_HIP(hipMalloc(&d_flog_, sizeof(float) * kFluidLogFloats * (size_t)B_ * nloops_ * maxn_));
+        // a fresh handle's velocity; with warm_start it carries over, as a
+        // reused one-pair object's
+        if (!warm_) zero_velocity();
+    }
     launches_ = 0;
     pair_err_.clear();
     OF2D_HIP(hipMemsetAsync(d_status_, 0, sizeof(unsigned) * B_, st_));
@@ -407,6 +445,12 @@ void Batch::estimate() {
         OF2D_HIP(hipMemcpyAsync(h_errs_.data(), d_errs_, sizeof(float) * h_errs_.size(),
                                 hipMemcpyDeviceToHost, st_));
     }
+    h_flog_.clear();
+    if (fluid && d_flog_) {
+        h_flog_.resize((size_t)kFluidLogFloats * B_ * nloops_ * maxn_);
+        OF2D_HIP(hipMemcpyAsync(h_flog_.data(), d_flog_, sizeof(float) * h_flog_.size(),
+                                hipMemcpyDeviceToHost, st_));
+    }
     OF2D_HIP(hipStreamSynchronize(st_));
     loop_us_ = 0.0;
     for (int l = 0; l < nloops_; l++) {
@@ -459,6 +503,21 @@ void Batch::launch_loop(int s, int loop, bool conv) {
         a.lx = curv_chunk_lines(L.dx, L.dy);
         a.ly = curv_chunk_lines(L.dy, L.dx);
         launch_curv_loop(a, B_, conv, st_);
+    } else if (reg_ == 2 && fluid_) {
+        FluidLoopArgs a{c};
+        a.dI = L.dI.p;
+        a.It = L.It.p;
+        a.f = L.force.p;
+        a.vel = L.vel.p;
+        a.m_cur = L.motion[L.mcur].p;
+        a.m_other = L.motion[1 - L.mcur].p;
+        a.Iref = L.Iref.p;
+        a.sref = shared_ ? 0 : L.stride;
+        a.Imov = L.Imov.p;
+        a.Iaux = L.Iaux.p;
+        a.log = d_flog_;
+        a.k = sor_;
+        launch_fluid_loop(a, B_, conv, st_);
     } else if (reg_ == 2) {
         ElasticLoopArgs a{c};
         a.dI = L.dI.p;
@@ -541,7 +600,14 @@ void Batch::motion_in_place() {
     OF2D_HIP(hipStreamSynchronize(st_));
 }
 
-// every level as allocate_device left it
+// option "fluid": every level's velocity <- 0 (enqueued)
+void Batch::zero_velocity() {
+    for (BLevel &L : lv_)
+        if (L.vel.base) OF2D_HIP(hipMemsetAsync(L.vel.base, 0, L.vel.bytes(), st_));
+}
+
+// every level as allocate_device left it; the velocity of option "fluid" too,
+// as Registration::reset_motion's
 void Batch::reset_motion() {
     DeviceScope scope;
     ensure_device();
@@ -549,6 +615,7 @@ void Batch::reset_motion() {
         L.mcur = 0;
         for (BField<float2> &m : L.motion) OF2D_HIP(hipMemsetAsync(m.base, 0, m.bytes(), st_));
     }
+    zero_velocity();
     OF2D_HIP(hipStreamSynchronize(st_));
 }
 
@@ -755,6 +822,16 @@ std::vector<float> Batch::last_errors(int pair) const {
     const size_t loop = (size_t)pair * nloops_ + (nloops_ - 1);
     const int n = std::min(h_iters_[loop], maxn_);
     v.assign(h_errs_.begin() + loop * maxn_, h_errs_.begin() + loop * maxn_ + n);
+    return v;
+}
+
+std::vector<float> Batch::fluid_log(int pair, int loop) const {
+    std::vector<float> v;
+    if (pair < 0 || pair >= B_ || loop < 0 || loop >= nloops_ || h_flog_.empty()) return v;
+    const size_t l = (size_t)pair * nloops_ + loop;
+    const int n = std::min(h_iters_[l], maxn_);
+    const float *p = h_flog_.data() + l * maxn_ * kFluidLogFloats;
+    v.assign(p, p + (size_t)n * kFluidLogFloats);
     return v;
 }
 

@@ -1,8 +1,8 @@
-// batch_loop.h — the frame the batch's six loop kernels share (hs_loop_kernel,
+// batch_loop.h — the frame the batch's seven loop kernels share (hs_loop_kernel,
 // hs_resident_kernel, demons_loop_kernel, demons_lds_kernel, curv_loop_kernel,
-// elastic_loop_kernel).
+// elastic_loop_kernel, fluid_loop_kernel).
 //
-// One workgroup of kLoopThreads (Curvature: kCurvThreads; Elastic:
+// One workgroup of kLoopThreads (Curvature: kCurvThreads; Elastic and Fluid:
 // elastic_threads(dx)) runs the whole loop of pair blockIdx.x:
 //   entry   loop_entry: the pair's iters and errs slots; a pair whose status
 //           has kStatusDivZero from an earlier loop runs nothing and reports 0

@@ -477,6 +477,16 @@ int of2d_batch_last_errors(const of2d_batch *b, int pair, float *out, int cap) {
     return (int)v.size();
 }
 
+int of2d_batch_fluid_log(const of2d_batch *b, int pair, int loop, float *out, int cap) {
+    if (!b || pair < 0 || pair >= b->b->nbatch() || loop < 0 || loop >= b->b->nloops()) return -1;
+    const std::vector<float> v = b->b->fluid_log(pair, loop);
+    constexpr int R = of2d::batch::kFluidLogFloats;
+    const int n = (int)v.size() / R;
+    for (int i = 0; i < n && i < cap; i++)
+        for (int q = 0; q < R; q++) out[R * i + q] = v[R * i + q];
+    return n;
+}
+
 int of2d_batch_info(const of2d_batch *b, int *info, int n) {
     if (!b) return -1;
     const std::vector<int> v = b->b->info();

@@ -8,6 +8,9 @@
 //   if dt < 65: u += R*dt                             :97-121, :135-139
 // plus the Logger (Logger.cpp:32-51) and the regridding test
 // min(det(I + grad u)) < 0.5 (Image.cpp:189-218, ImageRegistrationFluid.cpp:107-124).
+// (fluid_px.h holds the force, the increment, the time step and the
+// integration per pixel for the batch's Fluid loop, batch_fluid_kernels.hip:
+// keep the lines here and there the same operations in the same association.)
 //
 // The SOR sweep is Gauss-Seidel IN PLACE with i (x) outer and j (y) inner, so
 // v(i,j) reads the NEW v at (i-1,j-1), (i-1,j), (i-1,j+1), (i,j-1) and the OLD

@@ -1,7 +1,8 @@
-// of2d_batch.h — B independent Horn-Schunck, Curvature, Elastic or Thirion's
+// of2d_batch.h — B independent Horn-Schunck, Curvature, Elastic, Fluid or Thirion's
 // Demons registrations of one size in one call, and the deformation analysis of
 // their motions (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
-// batch_curvature_kernels.hip, batch_elastic_kernels.hip, batch_demons_kernels.hip,
+// batch_curvature_kernels.hip, batch_elastic_kernels.hip, batch_fluid_kernels.hip,
+// batch_demons_kernels.hip,
 // batch_demons_lds_kernels.hip, batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the host
 // arithmetic: batch_plan.h).
 //
@@ -82,6 +83,31 @@ struct ElasticLoopArgs : LoopCommon {
 };
 // conv as launch_hs_loop's
 void launch_elastic_loop(const ElasticLoopArgs &a, int B, bool conv, hipStream_t st);
+
+// Fluid, option "fluid" of an Elastic batch (batch_fluid_kernels.hip, DESIGN.md
+// §4.6.9): the pair's whole loop of ImageRegistrationFluid::
+// estimate_motion_at_current_resolution with OpticalFlowFluid::get_update, the
+// regrid inside.  The sweep is the Elastic loop's on the pair's velocity; the
+// workgroup has elastic_threads(dx) threads; dx, dy >= 2.
+// A record of the log: {maxabs, dt, jmin, regridded (0 or 1)}
+constexpr int kFluidLogFloats = 4;
+struct FluidLoopArgs : LoopCommon {
+    float2 *dI;  // a regrid rewrites both
+    float *It;
+    float2 *f;    // scratch: the force, then the increment, a field per pair
+    float2 *vel;  // the level's velocity, a field per pair; outlives the launch
+    // the level's motion: the current buffer of every pair before and after
+    // the launch, and the other one, which a regrid accumulates into
+    float2 *m_cur, *m_other;
+    const float *Iref;
+    long sref;  // Iref's pair stride, 0 for a shared reference
+    const float *Imov;
+    float *Iaux;
+    float *log;  // [B][nloops][maxn] records
+    SorCoef k;   // sor_coef(mu, lambda, omega)
+};
+// conv as launch_hs_loop's; without it the break is off and the regrid stays on
+void launch_fluid_loop(const FluidLoopArgs &a, int B, bool conv, hipStream_t st);
 
 // ---- option "resident" (batch_resident_kernels.hip): the
 // same loop with the pair's iterate in LDS and dI, It in registers across the
@@ -255,6 +281,9 @@ struct BLevel {
     DevArray<double> cX, cE, ctwx, ctwy;
     // Elastic only: the force of the iteration under way
     BField<float2> force;
+    // option "fluid" only: the velocity (OpticalFlowFluid::velocity), allocated
+    // by the first estimate that runs with it
+    BField<float2> vel;
     int mcur = 0;
 };
 
@@ -315,6 +344,9 @@ class Batch {
     const std::vector<unsigned> &status() const { return h_status_; }
     const std::vector<int> &iterations() const { return h_iters_; }
     std::vector<float> last_errors(int pair) const;
+    // option "fluid": the records {maxabs, dt, jmin, regridded} of the
+    // iterations pair's loop `loop` ran in the last estimate; empty without it
+    std::vector<float> fluid_log(int pair, int loop) const;
     // launches of an estimate: max(nscales - 1, 0) downsamples + nloops * (4,
     // Demons 3) + nscales upsamples + 1 zeroing of failed pairs; with
     // warm_start nscales + 1 zeroings, one per level
@@ -380,6 +412,13 @@ class Batch {
     bool fixed_ = false, shared_ = false, have_images_ = false;
     bool diffeo_ = false;  // option "diffeomorphic" (reg 3, Composition only)
     bool warm_ = false;    // option "warm_start": estimate() resets no motion
+    // option "fluid" (reg 2): the loop is launch_fluid_loop.  The velocity and
+    // the log exist from the first estimate that runs with it
+    bool fluid_ = false;
+    bool have_vel_ = false;
+    void zero_velocity();
+    float *d_flog_ = nullptr;
+    std::vector<float> h_flog_;
     // option "resident" (reg 0) or "conv_lds" (reg 3), the one a handle of
     // this kind admits: the levels that fit (on_cu_fits) run launch_hs_resident
     // or launch_demons_lds.  on_cu_ok_: resident_prepare's or

@@ -1,8 +1,8 @@
 // sor_px.h — one pixel of the SOR sweep of OpticalFlowElastic::SOR_iteration
 // (OpticalFlowElastic.cpp:37-50; OpticalFlowFluid.cpp:27-35 is the same
 // expression on the velocity), for the kernels that hold the pixel's nine
-// values themselves: the batch's Elastic loop (batch_elastic_kernels.hip), and
-// a batched Fluid velocity sweep when there is one.  The one-pair sweep
+// values themselves: the batch's Elastic loop (batch_elastic_kernels.hip) and
+// its Fluid loop's velocity sweep (batch_fluid_kernels.hip).  The one-pair sweep
 // (fluid_kernels.hip, sor_strip_kernel) keeps its own copy of these lines in
 // its register window; the two must stay the same operations in the same
 // association, compiled with -ffp-contract=off:
