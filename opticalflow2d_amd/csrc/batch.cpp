@@ -78,27 +78,18 @@ Batch::Batch(int nbatch, int dimx, int dimy, const int *niter, int nscales, int 
 
 Batch::~Batch() { release_device(); }
 
+// every owner lets go (the levels' fields with lv_), then the events and the stream
 void Batch::release_device() {
     lv_.clear();
-    if (d_stage_) (void)hipFree(d_stage_);
-    if (d_words_) (void)hipFree(d_words_);
-    d_words_ = nullptr;
     qref_.release();
-    qref_pairs_ = 0;
-    if (d_status_) (void)hipFree(d_status_);
-    if (d_iters_) (void)hipFree(d_iters_);
-    if (d_errs_) (void)hipFree(d_errs_);
-    if (d_flog_) (void)hipFree(d_flog_);
-    d_flog_ = nullptr;
-    have_vel_ = false;
-    if (d_kf_) (void)hipFree(d_kf_);
-    if (d_kd_) (void)hipFree(d_kd_);
-    d_kf_ = nullptr;
-    d_kd_ = nullptr;
-    d_stage_ = nullptr;
-    d_status_ = nullptr;
-    d_iters_ = nullptr;
-    d_errs_ = nullptr;
+    d_stage_.release();
+    d_words_.release();
+    d_status_.release();
+    d_iters_.release();
+    d_errs_.release();
+    d_flog_.release();
+    d_kf_.release();
+    d_kd_.release();
     for (hipEvent_t e : ev_)
         if (e) (void)hipEventDestroy(e);
     ev_.clear();
@@ -108,7 +99,7 @@ void Batch::release_device() {
     }
     if (st_) (void)hipStreamDestroy(st_);
     st_ = nullptr;
-    ref_pairs_ = 0;
+    ref_pairs_ = qref_pairs_ = 0;
     on_cu_ok_ = -1;
     ready_ = false;
 }
@@ -130,7 +121,7 @@ void Batch::set_option(const std::string &key, double v) {
     } else if (key == "diffeomorphic") {
         // DemonsDiffeomorphic::get_update is DemonsThirions' with Composition
         // plus exp(): an option of such a batch
-        if (reg_ != 3)
+        if (kind() != LoopKind::Demons)
             throw std::invalid_argument("diffeomorphic: the batch is not a Thirion's Demons batch");
         if ((int)params_[5] != 0)
             throw std::invalid_argument("diffeomorphic: accumulation must be Composition (0)");
@@ -140,7 +131,8 @@ void Batch::set_option(const std::string &key, double v) {
     } else if (key == "fluid") {
         // OpticalFlowFluid takes Elastic's parameters and relaxes its velocity
         // with Elastic's sweep: an option of such a batch
-        if (reg_ != 2) throw std::invalid_argument("fluid: the batch is not an Elastic batch");
+        if (!loop_sweeps(kind()))
+            throw std::invalid_argument("fluid: the batch is not an Elastic batch");
         const bool on = flag_value(key, v);
         // the Jacobian's one-sided differences need a neighbour
         for (int s = 0; on && s <= nscales_; s++)
@@ -148,7 +140,7 @@ void Batch::set_option(const std::string &key, double v) {
                 throw std::invalid_argument("fluid: every level needs sides of at least 2");
         // a change of the value: the next estimate with it starts from a zero
         // velocity
-        if (on != fluid_ && ready_ && have_vel_) {
+        if (on != fluid_ && ready_ && have_velocity()) {
             DeviceScope scope;
             OF2D_HIP(hipSetDevice(home_));
             zero_velocity();
@@ -156,23 +148,18 @@ void Batch::set_option(const std::string &key, double v) {
         }
         if (on != fluid_) h_flog_.clear();  // the log is the option's
         fluid_ = on;
-    } else if (key == "resident") {
-        // the Horn-Schunck loop with the iterate on the CU at the levels that
-        // fit (resident_fits)
-        if (reg_ != 0) throw std::invalid_argument("resident: the batch is not a Diffusion batch");
-        on_cu_ = flag_value(key, v);
-    } else if (key == "conv_lds") {
-        // the Demons loop with the convolved field in LDS at the levels that
-        // fit (conv_lds_fits)
-        if (reg_ != 3)
-            throw std::invalid_argument("conv_lds: the batch is not a Thirion's Demons batch");
+    } else if (key == "resident" || key == "conv_lds") {
+        // the Horn-Schunck loop with the iterate on the CU, the Demons loop
+        // with the convolved field in LDS, at the levels that fit (on_cu_fits)
+        const char *own = on_cu_option(kind());
+        if (!own || key != own)
+            throw std::invalid_argument(key == "resident"
+                                            ? "resident: the batch is not a Diffusion batch"
+                                            : "conv_lds: the batch is not a Thirion's Demons batch");
         on_cu_ = flag_value(key, v);
     } else
         throw std::invalid_argument("unknown option: " + key);
 }
-
-// pairs per staging round of the boundary copies (64 MiB of doubles at most)
-size_t Batch::chunk_pairs() const { return stage_chunk_pairs(B_, dimx_, dimy_); }
 
 void Batch::ensure_device() {
     if (ready_) {
@@ -187,6 +174,13 @@ void Batch::ensure_device() {
         throw;
     }
     ready_ = true;
+}
+
+// a table on the device
+template <class T>
+static void upload(DevArray<T> &d, const std::vector<T> &h) {
+    d.alloc(h.size());
+    OF2D_HIP(hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
 }
 
 void Batch::allocate_device() {
@@ -209,43 +203,34 @@ void Batch::allocate_device() {
         L.dI.alloc(L.dx, L.dy, B_);
         L.est[0].alloc(L.dx, L.dy, B_);
         L.est[1].alloc(L.dx, L.dy, B_);
-        if (reg_ == 3) L.mid.alloc(L.dx, L.dy, B_);
-        if (reg_ == 2) L.force.alloc(L.dx, L.dy, B_);
-        if (reg_ == 1) {
-            // the level's tables by the one-pair path's own builders
-            // (solvers::build_curvature), E dense
-            L.cX.alloc(curv_scratch_doubles(L.dx, L.dy) * B_);
-            auto upload = [](DevArray<double> &d, const std::vector<double> &h) {
-                d.alloc(h.size());
-                OF2D_HIP(hipMemcpy(d.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-            };
-            upload(L.cE, curvature_eigenvalues(L.dx, L.dy, L.dx, alpha_, tau_));
-            upload(L.ctwx, dct_table(L.dx));
-            upload(L.ctwy, dct_table(L.dy));
+        // the kind's own scratch (option "fluid" can change an Elastic batch's
+        // kind later: both take the force)
+        switch (kind()) {
+            case LoopKind::HornSchunck: break;
+            case LoopKind::Demons: L.mid.alloc(L.dx, L.dy, B_); break;
+            case LoopKind::Elastic:
+            case LoopKind::Fluid: L.force.alloc(L.dx, L.dy, B_); break;
+            case LoopKind::Curvature:
+                // the level's tables by the one-pair path's own builders
+                // (solvers::build_curvature), E dense
+                L.cX.alloc(curv_scratch_doubles(L.dx, L.dy) * B_);
+                upload(L.cE, curvature_eigenvalues(L.dx, L.dy, L.dx, alpha_, tau_));
+                upload(L.ctwx, dct_table(L.dx));
+                upload(L.ctwy, dct_table(L.dy));
+                break;
         }
     }
-    if (reg_ == 3) {
+    if (kind() == LoopKind::Demons) {
         // both tables once per Batch, sigma_fluid's first (Registration::loop_demons)
-        const size_t n = kfluid_.size();
-        std::vector<float> kf(2 * n);
-        std::vector<double> kd(2 * n);
-        for (size_t t = 0; t < n; t++) {
-            kf[t] = (float)kfluid_[t];
-            kd[t] = kfluid_[t];
-            kf[n + t] = (float)kdiff_[t];
-            kd[n + t] = kdiff_[t];
-        }
-        OF2D_HIP(hipMalloc(&d_kf_, sizeof(float) * 2 * n));
-        OF2D_HIP(hipMalloc(&d_kd_, sizeof(double) * 2 * n));
-        OF2D_HIP(hipMemcpy(d_kf_, kf.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-        OF2D_HIP(hipMemcpy(d_kd_, kd.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+        std::vector<double> kd(kfluid_);
+        kd.insert(kd.end(), kdiff_.begin(), kdiff_.end());
+        upload(d_kd_, kd);
+        upload(d_kf_, std::vector<float>(kd.begin(), kd.end()));
     }
-    stage_pairs_ = chunk_pairs();
-    OF2D_HIP(hipMalloc(&d_stage_, stage_pairs_ * 2 * (size_t)dimx_ * dimy_ * sizeof(double)));
-    OF2D_HIP(hipMalloc(&d_status_, sizeof(unsigned) * B_));
-    OF2D_HIP(hipMemset(d_status_, 0, sizeof(unsigned) * B_));
-    OF2D_HIP(hipMalloc(&d_iters_, sizeof(int) * std::max<size_t>(1, (size_t)B_ * nloops_)));
-    OF2D_HIP(hipMemset(d_iters_, 0, sizeof(int) * std::max<size_t>(1, (size_t)B_ * nloops_)));
+    stage_pairs_ = stage_chunk_pairs(B_, dimx_, dimy_);  // 64 MiB of doubles at most
+    d_stage_.alloc(stage_pairs_ * 2 * (size_t)dimx_ * dimy_);
+    d_status_.alloc(B_);
+    d_iters_.alloc((size_t)B_ * nloops_);
     ev_.assign(2 * (size_t)nloops_, nullptr);
     for (hipEvent_t &e : ev_) OF2D_HIP(hipEventCreate(&e));
     for (hipEvent_t &e : ev_io_) OF2D_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -283,29 +268,29 @@ void Batch::set_images(const double *ref, bool shared_ref, const double *mov) {
 // ---- one staging round's launches (of2d_batch.h, for_rounds)
 void Batch::images_in(const StageRound &r, const double *host, float *field) {
     const BLevel &L0 = lv_[0];
-    OF2D_HIP(hipMemcpyAsync(d_stage_, host + r.image,
+    OF2D_HIP(hipMemcpyAsync(d_stage_.p, host + r.image,
                             sizeof(double) * r.nk * (size_t)dimx_ * dimy_, hipMemcpyHostToDevice,
                             st_));
-    launch_d2f(d_stage_, r.nk, dimx_, dimy_, field + r.field, L0.stride, L0.P, st_);
+    launch_d2f(d_stage_.p, r.nk, dimx_, dimy_, field + r.field, L0.stride, L0.P, st_);
 }
 void Batch::images_out(const StageRound &r, const float *field, double *host) {
     const BLevel &L0 = lv_[0];
-    launch_f2d(field + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_, r.nk, st_);
-    OF2D_HIP(hipMemcpyAsync(host + r.image, d_stage_,
+    launch_f2d(field + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_.p, r.nk, st_);
+    OF2D_HIP(hipMemcpyAsync(host + r.image, d_stage_.p,
                             sizeof(double) * r.nk * (size_t)dimx_ * dimy_, hipMemcpyDeviceToHost,
                             st_));
 }
 void Batch::motion_in(const StageRound &r, const double *host, float2 *field) {
     const BLevel &L0 = lv_[0];
-    OF2D_HIP(hipMemcpyAsync(d_stage_, host + r.motion,
+    OF2D_HIP(hipMemcpyAsync(d_stage_.p, host + r.motion,
                             sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
                             hipMemcpyHostToDevice, st_));
-    launch_planar_to_motion(d_stage_, r.nk, dimx_, dimy_, field + r.field, L0.stride, L0.P, st_);
+    launch_planar_to_motion(d_stage_.p, r.nk, dimx_, dimy_, field + r.field, L0.stride, L0.P, st_);
 }
 void Batch::motion_out(const StageRound &r, const float2 *field, double *host) {
     const BLevel &L0 = lv_[0];
-    launch_motion_to_planar(field + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_, r.nk, st_);
-    OF2D_HIP(hipMemcpyAsync(host + r.motion, d_stage_,
+    launch_motion_to_planar(field + r.field, L0.stride, L0.P, dimx_, dimy_, d_stage_.p, r.nk, st_);
+    OF2D_HIP(hipMemcpyAsync(host + r.motion, d_stage_.p,
                             sizeof(double) * 2 * r.nk * (size_t)dimx_ * dimy_,
                             hipMemcpyDeviceToHost, st_));
 }
@@ -358,34 +343,24 @@ void Batch::estimate() {
     DeviceScope scope;
     ensure_device();
     if (!have_images_) throw std::invalid_argument("of2d_batch_estimate: no images set");
-    if (!fixed_ && !d_errs_ && maxn_ > 0 && nloops_ > 0)
-        OF2D_HIP(hipMalloc(&d_errs_, sizeof(float) * (size_t)B_ * nloops_ * maxn_));
+    const LoopKind kind = this->kind();
     const bool conv = !fixed_;
-    const bool fluid = fluid_;
-    if (fluid) {
-        // the velocity, a field per pair and level that outlives the estimate
-        // (OpticalFlowFluid::velocity), and the log
-        if (!have_vel_) {
-            for (BLevel &L : lv_) L.vel.alloc(L.dx, L.dy, B_);
-            OF2D_HIP(hipDeviceSynchronize());  // null-stream memsets, as allocate_device's
-            have_vel_ = true;
-        }
-        if (!d_flog_ && maxn_ > 0 && nloops_ > 0)
-            OF2D_HIP(hipMalloc(&d_flog_, sizeof(float) * kFluidLogFloats * (size_t)B_ * nloops_ * maxn_));
-        // a fresh handle's velocity; with warm_start it carries over, as a
-        // reused one-pair object's
-        if (!warm_) zero_velocity();
-    }
+    const bool fluid = kind == LoopKind::Fluid;
+    if (conv && !d_errs_.p && maxn_ > 0 && nloops_ > 0)
+        d_errs_.alloc((size_t)B_ * nloops_ * maxn_);
+    if (fluid) prepare_fluid();
     launches_ = 0;
     pair_err_.clear();
-    OF2D_HIP(hipMemsetAsync(d_status_, 0, sizeof(unsigned) * B_, st_));
+    OF2D_HIP(hipMemsetAsync(d_status_.p, 0, sizeof(unsigned) * B_, st_));
     // option "resident" or "conv_lds": asked of the runtime once per handle; a
-    // refusal there is "no level fits", not an error
+    // refusal there is "no level fits", not an error.  (on_cu_ is set for the
+    // two kinds of on_cu_option only; a third needs its prepare named here)
     if (on_cu_ && on_cu_ok_ < 0)
-        on_cu_ok_ = (reg_ == 3 ? conv_lds_prepare() : resident_prepare()) ? 1 : 0;
+        on_cu_ok_ = (kind == LoopKind::Demons ? conv_lds_prepare() : resident_prepare()) ? 1 : 0;
     placement_.assign(nscales_ + 1, 0);
     if (on_cu_ && on_cu_ok_ == 1)
-        for (int s = 0; s <= nscales_; s++) placement_[s] = on_cu_fits(s) ? 1 : 0;
+        for (int s = 0; s <= nscales_; s++)
+            placement_[s] = on_cu_fits(kind, ldx_[s], ldy_[s]) ? 1 : 0;
     const bool warm = warm_;
     if (!warm)
         for (BLevel &L : lv_) {
@@ -398,7 +373,7 @@ void Batch::estimate() {
         BLevel &L = lv_[s];
         if (s > 0 && s < nscales_) {
             launch_downsample_motion(L0.motion[L0.mcur].p, L0.stride, L0.dx, L0.dy, L0.P,
-                                     L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P, B_, d_status_,
+                                     L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P, B_, d_status_.p,
                                      st_);
             launches_++;
         }
@@ -406,24 +381,24 @@ void Batch::estimate() {
         for (int refine = 0; refine < nrefine_; refine++, loop++) {
             // *Iaux = *Imov; Iaux->warp2d(*motion)
             launch_warp(L.Imov.p, L.motion[L.mcur].p, L.Iaux.p, L.stride, L.dx, L.dy, L.P, B_,
-                        d_status_, st_);
-            if (reg_ != 3)
+                        d_status_.p, st_);
+            if (loop_takes_gradients(kind))
                 launch_gradients(L.Iref.p, shared_ ? 0 : L.stride, L.Iaux.p, L.dI.p, L.It.p,
-                                 L.stride, L.dx, L.dy, L.P, B_, d_status_, st_);
+                                 L.stride, L.dx, L.dy, L.P, B_, d_status_.p, st_);
             // motion_est starts at zero
             OF2D_HIP(hipMemsetAsync(L.est[0].base, 0, L.est[0].bytes(), st_));
             launch_loop(s, loop, conv);
             // motion->accumulate(*motion_est)
             launch_accumulate(L.motion[L.mcur].p, L.est[0].p, L.est[1].p, L.motion[1 - L.mcur].p,
-                              L.stride, L.dx, L.dy, L.P, B_, d_iters_, nloops_, loop, d_status_,
+                              L.stride, L.dx, L.dy, L.P, B_, d_iters_.p, nloops_, loop, d_status_.p,
                               st_);
             L.mcur ^= 1;
-            launches_ += reg_ == 3 ? 3 : 4;  // Demons: no gradients launch
+            launches_ += loop_launches(kind);
         }
         if (s > 0) {
             launch_upsample_motion(L.motion[L.mcur].p, L.stride, L.dx, L.dy, L.P,
                                    L0.motion[L0.mcur].p, L0.stride, L0.dx, L0.dy, L0.P, B_,
-                                   d_status_, st_);
+                                   d_status_.p, st_);
             launches_++;
         }
     }
@@ -431,26 +406,22 @@ void Batch::estimate() {
     // level, so that the pair's next estimate starts as a fresh handle's
     for (int s = 0; s <= (warm ? nscales_ : 0); s++) {
         BLevel &L = lv_[s];
-        launch_zero_failed(L.motion[L.mcur].base, L.stride, B_, d_status_, st_);
+        launch_zero_failed(L.motion[L.mcur].base, L.stride, B_, d_status_.p, st_);
         launches_++;
     }
-    OF2D_HIP(hipMemcpyAsync(h_status_.data(), d_status_, sizeof(unsigned) * B_,
+    OF2D_HIP(hipMemcpyAsync(h_status_.data(), d_status_.p, sizeof(unsigned) * B_,
                             hipMemcpyDeviceToHost, st_));
     if (nloops_ > 0)
-        OF2D_HIP(hipMemcpyAsync(h_iters_.data(), d_iters_, sizeof(int) * h_iters_.size(),
+        OF2D_HIP(hipMemcpyAsync(h_iters_.data(), d_iters_.p, sizeof(int) * h_iters_.size(),
                                 hipMemcpyDeviceToHost, st_));
-    h_errs_.clear();
-    if (conv && d_errs_) {
-        h_errs_.resize((size_t)B_ * nloops_ * maxn_);
-        OF2D_HIP(hipMemcpyAsync(h_errs_.data(), d_errs_, sizeof(float) * h_errs_.size(),
-                                hipMemcpyDeviceToHost, st_));
-    }
-    h_flog_.clear();
-    if (fluid && d_flog_) {
-        h_flog_.resize((size_t)kFluidLogFloats * B_ * nloops_ * maxn_);
-        OF2D_HIP(hipMemcpyAsync(h_flog_.data(), d_flog_, sizeof(float) * h_flog_.size(),
-                                hipMemcpyDeviceToHost, st_));
-    }
+    // a lazy buffer's content where this estimate wrote it, else nothing
+    auto fetch = [&](std::vector<float> &h, const DevArray<float> &d, bool on) {
+        h.resize(on ? d.n : 0);
+        if (!h.empty())
+            OF2D_HIP(hipMemcpyAsync(h.data(), d.p, sizeof(float) * d.n, hipMemcpyDeviceToHost, st_));
+    };
+    fetch(h_errs_, d_errs_, conv);
+    fetch(h_flog_, d_flog_, fluid);
     OF2D_HIP(hipStreamSynchronize(st_));
     loop_us_ = 0.0;
     for (int l = 0; l < nloops_; l++) {
@@ -465,8 +436,22 @@ void Batch::estimate() {
         }
 }
 
+// option "fluid", before an estimate: the velocity, a field per pair and level
+// that outlives the estimate (OpticalFlowFluid::velocity), and the log
+void Batch::prepare_fluid() {
+    if (!have_velocity()) {
+        for (BLevel &L : lv_) L.vel.alloc(L.dx, L.dy, B_);
+        OF2D_HIP(hipDeviceSynchronize());  // null-stream memsets, as allocate_device's
+    }
+    if (!d_flog_.p && maxn_ > 0 && nloops_ > 0)
+        d_flog_.alloc((size_t)kFluidLogFloats * B_ * nloops_ * maxn_);
+    // a fresh handle's velocity; with warm_start it carries over, as a
+    // reused one-pair object's
+    if (!warm_) zero_velocity();
+}
+
 // loop `loop` of level s, the iterate in est[]: the common arguments, the
-// regulariser's own, the kernel by placement_[s], between the loop's events
+// kind's own, the kernel by placement_[s], between the loop's events
 void Batch::launch_loop(int s, int loop, bool conv) {
     BLevel &L = lv_[s];
     LoopCommon c;
@@ -477,62 +462,83 @@ void Batch::launch_loop(int s, int loop, bool conv) {
     c.dy = L.dy;
     c.P = L.P;
     c.niter = niter_[s];
-    c.status = d_status_;
-    c.iters = d_iters_;
+    c.status = d_status_.p;
+    c.iters = d_iters_.p;
     c.nloops = nloops_;
     c.loop = loop;
-    c.errs = d_errs_;
+    c.errs = d_errs_.p;
     c.maxn = maxn_;
+    const bool on_cu = placement_[s] != 0;
     OF2D_HIP(hipEventRecord(ev_[2 * loop], st_));
-    if (reg_ == 3) {
-        (placement_[s] ? launch_demons_lds : launch_demons_loop)(demons_args(c, L), B_, conv, st_);
-    } else if (reg_ == 1) {
-        CurvLoopArgs a{c};
-        a.dI = L.dI.p;
-        a.It = L.It.p;
-        a.X = L.cX.p;
-        a.sx = (long)curv_scratch_doubles(L.dx, L.dy);
-        a.E = L.cE.p;
-        a.twx = reinterpret_cast<const double2 *>(L.ctwx.p);
-        a.twy = reinterpret_cast<const double2 *>(L.ctwy.p);
-        a.tau = tau_;
-        a.div = 4.0f * (float)((unsigned)L.dx * (unsigned)L.dy);  // 4.0f*sizein
-        a.logx = a.logy = 0;
-        while ((1 << a.logx) < L.dx) a.logx++;
-        while ((1 << a.logy) < L.dy) a.logy++;
-        a.lx = curv_chunk_lines(L.dx, L.dy);
-        a.ly = curv_chunk_lines(L.dy, L.dx);
-        launch_curv_loop(a, B_, conv, st_);
-    } else if (reg_ == 2 && fluid_) {
-        FluidLoopArgs a{c};
-        a.dI = L.dI.p;
-        a.It = L.It.p;
-        a.f = L.force.p;
-        a.vel = L.vel.p;
-        a.m_cur = L.motion[L.mcur].p;
-        a.m_other = L.motion[1 - L.mcur].p;
-        a.Iref = L.Iref.p;
-        a.sref = shared_ ? 0 : L.stride;
-        a.Imov = L.Imov.p;
-        a.Iaux = L.Iaux.p;
-        a.log = d_flog_;
-        a.k = sor_;
-        launch_fluid_loop(a, B_, conv, st_);
-    } else if (reg_ == 2) {
-        ElasticLoopArgs a{c};
-        a.dI = L.dI.p;
-        a.It = L.It.p;
-        a.f = L.force.p;
-        a.k = sor_;
-        launch_elastic_loop(a, B_, conv, st_);
-    } else {
-        LoopArgs a{c};
-        a.dI = L.dI.p;
-        a.It = L.It.p;
-        a.alphasq = alpha_ * alpha_;  // OpticalFlowDiffusion.cpp:70
-        (placement_[s] ? launch_hs_resident : launch_hs_loop)(a, B_, conv, st_);
+    switch (kind()) {
+        case LoopKind::HornSchunck:
+            (on_cu ? launch_hs_resident : launch_hs_loop)(hs_args(c, L), B_, conv, st_);
+            break;
+        case LoopKind::Curvature: launch_curv_loop(curv_args(c, L), B_, conv, st_); break;
+        case LoopKind::Elastic: launch_elastic_loop(elastic_args(c, L), B_, conv, st_); break;
+        case LoopKind::Fluid: launch_fluid_loop(fluid_args(c, L), B_, conv, st_); break;
+        case LoopKind::Demons:
+            (on_cu ? launch_demons_lds : launch_demons_loop)(demons_args(c, L), B_, conv, st_);
+            break;
     }
     OF2D_HIP(hipEventRecord(ev_[2 * loop + 1], st_));
+}
+
+// ---- c and a kind's own arguments at level L
+LoopArgs Batch::hs_args(const LoopCommon &c, BLevel &L) const {
+    LoopArgs a{c};
+    a.dI = L.dI.p;
+    a.It = L.It.p;
+    a.alphasq = alpha_ * alpha_;  // OpticalFlowDiffusion.cpp:70
+    return a;
+}
+
+CurvLoopArgs Batch::curv_args(const LoopCommon &c, BLevel &L) const {
+    CurvLoopArgs a{c};
+    a.dI = L.dI.p;
+    a.It = L.It.p;
+    a.X = L.cX.p;
+    a.sx = (long)curv_scratch_doubles(L.dx, L.dy);
+    a.E = L.cE.p;
+    a.twx = reinterpret_cast<const double2 *>(L.ctwx.p);
+    a.twy = reinterpret_cast<const double2 *>(L.ctwy.p);
+    a.tau = tau_;
+    a.div = 4.0f * (float)((unsigned)L.dx * (unsigned)L.dy);  // 4.0f*sizein
+    a.logx = a.logy = 0;
+    while ((1 << a.logx) < L.dx) a.logx++;
+    while ((1 << a.logy) < L.dy) a.logy++;
+    a.lx = curv_chunk_lines(L.dx, L.dy);
+    a.ly = curv_chunk_lines(L.dy, L.dx);
+    return a;
+}
+
+// what the Elastic and the Fluid loop share: the derivatives, the force plane
+// and the sweep's constants
+template <class Args>
+static Args sweep_args(const LoopCommon &c, BLevel &L, const SorCoef &k) {
+    Args a{c};
+    a.dI = L.dI.p;
+    a.It = L.It.p;
+    a.f = L.force.p;
+    a.k = k;
+    return a;
+}
+
+ElasticLoopArgs Batch::elastic_args(const LoopCommon &c, BLevel &L) const {
+    return sweep_args<ElasticLoopArgs>(c, L, sor_);
+}
+
+FluidLoopArgs Batch::fluid_args(const LoopCommon &c, BLevel &L) const {
+    FluidLoopArgs a = sweep_args<FluidLoopArgs>(c, L, sor_);
+    a.vel = L.vel.p;
+    a.m_cur = L.motion[L.mcur].p;
+    a.m_other = L.motion[1 - L.mcur].p;
+    a.Iref = L.Iref.p;
+    a.sref = shared_ ? 0 : L.stride;
+    a.Imov = L.Imov.p;
+    a.Iaux = L.Iaux.p;
+    a.log = d_flog_.p;
+    return a;
 }
 
 // c and Thirion's Demons' own arguments at level L: It as the warped image, dI
@@ -550,8 +556,8 @@ DemonsLoopArgs Batch::demons_args(const LoopCommon &c, BLevel &L) const {
     // Demons.cpp:48-49
     a.sigma_isq = params_[0] * params_[0];
     a.sigma_xsq = params_[1] * params_[1];
-    a.fluid = DemonsTable{d_kf_, d_kd_, full_weight(kfluid_, kw)};
-    a.diff = DemonsTable{d_kf_ + n, d_kd_ + n, full_weight(kdiff_, kw)};
+    a.fluid = DemonsTable{d_kf_.p, d_kd_.p, full_weight(kfluid_, kw)};
+    a.diff = DemonsTable{d_kf_.p + n, d_kd_.p + n, full_weight(kdiff_, kw)};
     a.kw = kw;
     // static_cast<MotionAccumulation>((int) regparams[5]), as loop_demons
     const int accum = (int)params_[5];
@@ -666,12 +672,12 @@ void Batch::warp_device(const DArrayView &in, const DArrayView &out, hipStream_t
 // before every loop and writes est[1] before reading it, and nothing reads
 // either after an estimate).  The stored images and the motion are only read.
 double *Batch::analysis_words() {
-    if (!d_words_) OF2D_HIP(hipMalloc(&d_words_, sizeof(double) * 5 * (size_t)B_));
-    return d_words_;
+    if (!d_words_.p) d_words_.alloc(5 * (size_t)B_);
+    return d_words_.p;
 }
 
 void Batch::fetch_words(double *host, int per_pair) {
-    OF2D_HIP(hipMemcpyAsync(host, d_words_, sizeof(double) * per_pair * (size_t)B_,
+    OF2D_HIP(hipMemcpyAsync(host, d_words_.p, sizeof(double) * per_pair * (size_t)B_,
                             hipMemcpyDeviceToHost, st_));
     OF2D_HIP(hipStreamSynchronize(st_));
 }
@@ -841,7 +847,7 @@ std::vector<int> Batch::info() const {
         // 0: every field of the loop in global memory; 1: the iterate
         // (resident) or the convolved field (conv_lds) stays on the CU
         v.push_back(s < (int)placement_.size() ? placement_[s] : 0);
-        v.push_back(reg_ == 1 ? kCurvThreads : reg_ == 2 ? elastic_threads(ldx_[s]) : kLoopThreads);
+        v.push_back(loop_threads(kind(), ldx_[s]));
     }
     return v;
 }

@@ -8,20 +8,15 @@
 // An iteration, the iterate ping-ponging between the pair's two buffers as in
 // the other loops (iteration t reads u[t & 1]):
 //   1. force and copy, in for_pixels order: b = dI * ((It + u.x dI.x) + u.y
-//      dI.y) (OpticalFlow.cpp:15-39, the floats of sor_pack_kernel) into the
+//      dI.y) (OpticalFlow.cpp:15-39; force_px's lines, sor_px.h) into the
 //      pair's slice of the scratch plane f, and u_out <- u_in: the sweep never
 //      writes the border, which keeps its values
-//   2. the SOR sweep in place on u_out, in the reference's order.  The
-//      reference relaxes i-outer, j-inner, so pixel (i, j) reads NEW values at
-//      (i-1, j-1), (i-1, j), (i-1, j+1), (i, j-1) and OLD ones at (i, j+1) and
-//      (i+1, .): every pixel with 2 i + j = t depends on smaller t only.  Step
-//      t relaxes them all, thread tid the columns tid, tid + T, ... that have
-//      an interior row j = t - 2 i at this step (batch_plan.h, elastic_col_lo /
-//      _hi), with the per-pixel arithmetic of sor_px.h.  A step's pixels are no
-//      neighbours of each other, so the order inside a step is free; between
-//      steps stands one workgroup barrier, which a level of one wave (dx <= 64)
-//      does not need: the wave's loads and stores reach memory in program
-//      order
+//   2. the SOR sweep in place on u_out in the reference's order (sor_sweep,
+//      batch_sweep.h, which the Fluid loop runs on its velocity): step t
+//      relaxes every pixel with 2 i + j = t, which read NEW values of smaller
+//      t and OLD ones of larger t only (batch_plan.h, sor_px.h).  A step's
+//      pixels are no neighbours of each other, so the order inside a step is
+//      free; between steps stands step_sync
 //   3. with convergence on, the fp64 Logger sums of (u_out - u_in) and u_in in
 //      for_pixels order, block_sums and the decision, as hs_loop_kernel's
 //
@@ -33,27 +28,10 @@
 // the oracle's bit for bit.
 #include "of2d_batch.h"
 
-#include "sor_px.h"
+#include "batch_sweep.h"
 
 namespace of2d {
 namespace batch {
-
-namespace {
-// what orders a stage or a sweep step before the next.  One wave: its lanes
-// exchange values through memory, which its vector-memory instructions reach in
-// program order; the wavefront-scope fences keep the compiler from moving a
-// load across the stores of the step before it, and cost no instruction
-template <int WAVES>
-__device__ __forceinline__ void step_sync() {
-    if constexpr (WAVES == 1) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-}  // namespace
 
 template <int WAVES, bool CONV>
 __global__ __launch_bounds__(64 * WAVES) void elastic_loop_kernel(ElasticLoopArgs a) {
@@ -76,22 +54,13 @@ __global__ __launch_bounds__(64 * WAVES) void elastic_loop_kernel(ElasticLoopArg
         float2 *dst = (it & 1) ? u0 : u1;
         for_pixels<T>(tid, npx, dx, P, [&](int, int, int, long o) {
             const float2 m = src[o], g = dI[o];
+            // force_px's lines (sor_px.h), kept: the call moves the kernel's code
             const float sc = (It[o] + m.x * g.x) + m.y * g.y;
             f[o] = make_float2(g.x * sc, g.y * sc);
             dst[o] = m;
         });
         step_sync<WAVES>();
-        for (int t = kElasticFirstStep; t <= tlast; ++t) {
-            const int lo = elastic_col_lo(t, dy), hi = elastic_col_hi(t, dx);
-            for (int i = elastic_first_col(tid, lo, T); i <= hi; i += T) {
-                const int j = t - 2 * i;  // interior: 1 <= j <= dy - 2
-                const float2 *c = dst + (long)j * P + i;
-                const float2 nw = sor_px(k, c[0], f[(long)j * P + i], c[-1], c[1], c[P], c[-P],
-                                         c[P - 1], c[-P - 1], c[P + 1], c[-P + 1]);
-                dst[(long)j * P + i] = nw;
-            }
-            step_sync<WAVES>();
-        }
+        sor_sweep<WAVES>(dst, f, k, dx, dy, P, tid, tlast);
         n = it + 1;
         if constexpr (CONV) {
             double v[2] = {0.0, 0.0};
@@ -105,30 +74,11 @@ __global__ __launch_bounds__(64 * WAVES) void elastic_loop_kernel(ElasticLoopArg
     loop_exit(a, pair, tid, lane, ps, n, 0);
 }
 
-namespace {
-template <int WAVES>
-void launch_waves(const ElasticLoopArgs &a, int B, bool conv, hipStream_t st) {
-    if (conv)
-        hipLaunchKernelGGL((elastic_loop_kernel<WAVES, true>), dim3(B), dim3(64 * WAVES), 0, st, a);
-    else
-        hipLaunchKernelGGL((elastic_loop_kernel<WAVES, false>), dim3(B), dim3(64 * WAVES), 0, st,
-                           a);
-}
-}  // namespace
-
 void launch_elastic_loop(const ElasticLoopArgs &a, int B, bool conv, hipStream_t st) {
-    static_assert(kElasticMaxWaves == 8, "one instantiation per workgroup size below");
-    switch (elastic_waves(a.dx)) {
-        case 1: launch_waves<1>(a, B, conv, st); break;
-        case 2: launch_waves<2>(a, B, conv, st); break;
-        case 3: launch_waves<3>(a, B, conv, st); break;
-        case 4: launch_waves<4>(a, B, conv, st); break;
-        case 5: launch_waves<5>(a, B, conv, st); break;
-        case 6: launch_waves<6>(a, B, conv, st); break;
-        case 7: launch_waves<7>(a, B, conv, st); break;
-        default: launch_waves<8>(a, B, conv, st); break;
-    }
-    OF2D_HIP(hipGetLastError());
+    launch_by_waves(a, B, st, [conv](auto w) -> void (*)(ElasticLoopArgs) {
+        constexpr int W = decltype(w)::value;
+        return conv ? elastic_loop_kernel<W, true> : elastic_loop_kernel<W, false>;
+    });
 }
 
 }  // namespace batch

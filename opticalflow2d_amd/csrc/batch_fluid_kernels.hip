@@ -12,9 +12,8 @@
 // other).  An iteration, with a step_sync or a workgroup barrier between stages:
 //   1. force, in for_pixels order: b = dI ((It + u.x dI.x) + u.y dI.y) of the
 //      estimate u into the pair's slice of f
-//   2. the SOR sweep of the pair's VELOCITY in place, the Elastic batch's steps
-//      (batch_plan.h) with the arithmetic of sor_px.h; the border is never
-//      written and stays 0
+//   2. the SOR sweep of the pair's VELOCITY in place, the Elastic batch's
+//      (sor_sweep, batch_sweep.h); the border is never written and stays 0
 //   3. the increment R = (v - dudx v.x) - dudy v.y into f (the force is spent;
 //      pixel o is written and read back by the same thread) and the workgroup's
 //      maximum of Motion::maxabs' term; maxabs = sqrt(max), dt = 0.65f / maxabs
@@ -44,30 +43,15 @@
 // the oracle's bit for bit.
 #include "of2d_batch.h"
 
+#include "batch_sweep.h"
 #include "field_px.h"
 #include "fluid_px.h"
-#include "sor_px.h"
 
 namespace of2d {
 namespace batch {
 
-namespace {
-// as batch_elastic_kernels.hip's: what orders a stage or a sweep step before
-// the next.  The stages added here read neighbours that other lanes wrote (the
-// increment reads u, the Jacobian u', the gradients Iaux), which is a sweep
-// step's pattern
-template <int WAVES>
-__device__ __forceinline__ void step_sync() {
-    if constexpr (WAVES == 1) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-}  // namespace
-
+// the stages read neighbours that other lanes wrote (the increment u, the
+// Jacobian u', the gradients Iaux), a sweep step's pattern: step_sync orders them
 template <int WAVES, bool CONV>
 __global__ __launch_bounds__(64 * WAVES) void fluid_loop_kernel(FluidLoopArgs a) {
     constexpr int T = 64 * WAVES;
@@ -98,21 +82,11 @@ __global__ __launch_bounds__(64 * WAVES) void fluid_loop_kernel(FluidLoopArgs a)
         float2 *dst = (it & 1) ? u0 : u1;
         // 1. force
         for_pixels<T>(tid, npx, dx, P, [&](int, int, int, long o) {
-            f[o] = fluid_force_px(zu ? zero : src[o], dI[o], It[o]);
+            f[o] = force_px(zu ? zero : src[o], dI[o], It[o]);
         });
         step_sync<WAVES>();
         // 2. the sweep of the velocity
-        for (int t = kElasticFirstStep; t <= tlast; ++t) {
-            const int lo = elastic_col_lo(t, dy), hi = elastic_col_hi(t, dx);
-            for (int i = elastic_first_col(tid, lo, T); i <= hi; i += T) {
-                const int j = t - 2 * i;  // interior: 1 <= j <= dy - 2
-                const float2 *c = vel + (long)j * P + i;
-                const float2 nw = sor_px(k, c[0], f[(long)j * P + i], c[-1], c[1], c[P], c[-P],
-                                         c[P - 1], c[-P - 1], c[P + 1], c[-P + 1]);
-                vel[(long)j * P + i] = nw;
-            }
-            step_sync<WAVES>();
-        }
+        sor_sweep<WAVES>(vel, f, k, dx, dy, P, tid, tlast);
         // 3. increment, maximum, time step
         float m = 0.0f;
         for_pixels<T>(tid, npx, dx, P, [&](int, int i, int j, long o) {
@@ -194,29 +168,11 @@ __global__ __launch_bounds__(64 * WAVES) void fluid_loop_kernel(FluidLoopArgs a)
     loop_exit(a, pair, tid, lane, ps, n, 0);
 }
 
-namespace {
-template <int WAVES>
-void launch_waves(const FluidLoopArgs &a, int B, bool conv, hipStream_t st) {
-    if (conv)
-        hipLaunchKernelGGL((fluid_loop_kernel<WAVES, true>), dim3(B), dim3(64 * WAVES), 0, st, a);
-    else
-        hipLaunchKernelGGL((fluid_loop_kernel<WAVES, false>), dim3(B), dim3(64 * WAVES), 0, st, a);
-}
-}  // namespace
-
 void launch_fluid_loop(const FluidLoopArgs &a, int B, bool conv, hipStream_t st) {
-    static_assert(kElasticMaxWaves == 8, "one instantiation per workgroup size below");
-    switch (elastic_waves(a.dx)) {
-        case 1: launch_waves<1>(a, B, conv, st); break;
-        case 2: launch_waves<2>(a, B, conv, st); break;
-        case 3: launch_waves<3>(a, B, conv, st); break;
-        case 4: launch_waves<4>(a, B, conv, st); break;
-        case 5: launch_waves<5>(a, B, conv, st); break;
-        case 6: launch_waves<6>(a, B, conv, st); break;
-        case 7: launch_waves<7>(a, B, conv, st); break;
-        default: launch_waves<8>(a, B, conv, st); break;
-    }
-    OF2D_HIP(hipGetLastError());
+    launch_by_waves(a, B, st, [conv](auto w) -> void (*)(FluidLoopArgs) {
+        constexpr int W = decltype(w)::value;
+        return conv ? fluid_loop_kernel<W, true> : fluid_loop_kernel<W, false>;
+    });
 }
 
 }  // namespace batch

@@ -23,6 +23,8 @@
 //           which a thread met a zero denominator (bad != 0; coord2d.h:95-100),
 //           one atomicOr per wave
 // All of it is force-inlined: the kernels compile to what their own copies did.
+// The sweep that elastic_loop_kernel and fluid_loop_kernel run in their body,
+// with what orders its steps, is batch_sweep.h.
 #pragma once
 
 #include "of2d_device.h"

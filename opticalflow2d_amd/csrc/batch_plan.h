@@ -1,7 +1,8 @@
 // batch_plan.h — the host arithmetic of the batch's boundary copies and of its
 // analysis calls (batch.cpp, capi.cpp) that needs no device: the staging
-// rounds, a pair's offsets in them, the argument checks, and the fit rules of
-// the loop's on-CU placements with the instantiation a level runs.  Plain C++ (no
+// rounds, a pair's offsets in them, the argument checks, the fit rules of the
+// loop's on-CU placements with the instantiation a level runs, and what each
+// kind of loop needs of the driver (LoopKind).  Plain C++ (no
 // HIP header), so that tests/host/batch_plan_test.cpp exercises it on the CPU,
 // with sanitizers too.
 #pragma once
@@ -187,6 +188,34 @@ constexpr int elastic_col_hi(int t, int dx) {
 constexpr int elastic_first_col(int tid, int lo, int T) {
     const int r = tid - lo % T;
     return lo + (r < 0 ? r + T : r);
+}
+
+// ---- what a kind of loop needs of the driver (batch.cpp): the one place that
+// knows.  The kind follows from of2d_batch_create's method (0 Diffusion, 1
+// Curvature, 2 Elastic, 3 Thirion's Demons) and option "fluid" of an Elastic batch
+enum class LoopKind { HornSchunck, Curvature, Elastic, Fluid, Demons };
+constexpr LoopKind loop_kind(int reg, bool fluid) {
+    if (reg == 2) return fluid ? LoopKind::Fluid : LoopKind::Elastic;
+    return reg == 3 ? LoopKind::Demons : reg == 1 ? LoopKind::Curvature : LoopKind::HornSchunck;
+}
+// Elastic's sweep, which Fluid runs on its velocity: the force plane, elastic_threads
+constexpr bool loop_sweeps(LoopKind k) { return k == LoopKind::Elastic || k == LoopKind::Fluid; }
+// threads of a pair's workgroup at a dx-wide level (Batch::info)
+constexpr int loop_threads(LoopKind k, int dx) {
+    if (loop_sweeps(k)) return elastic_threads(dx);
+    return k == LoopKind::Curvature ? kCurvThreads : kLoopThreads;
+}
+// the gradients pass before a loop (Demons differentiates the image it warps
+// itself), and with it a loop's launches: warp, gradients, loop, accumulate
+constexpr bool loop_takes_gradients(LoopKind k) { return k != LoopKind::Demons; }
+constexpr int loop_launches(LoopKind k) { return loop_takes_gradients(k) ? 4 : 3; }
+// the on-CU option a handle of the kind admits (nullptr: none) and its fit rule
+constexpr const char *on_cu_option(LoopKind k) {
+    return k == LoopKind::HornSchunck ? "resident" : k == LoopKind::Demons ? "conv_lds" : nullptr;
+}
+inline bool on_cu_fits(LoopKind k, int dx, int dy) {
+    if (k == LoopKind::HornSchunck) return resident_fits(dx, dy);
+    return k == LoopKind::Demons && conv_lds_fits(dx, dy);
 }
 
 // nullptr or why the call is refused (the one-pair entries' wording)

@@ -8,9 +8,13 @@
 //   if dt < 65: u += R*dt                             :97-121, :135-139
 // plus the Logger (Logger.cpp:32-51) and the regridding test
 // min(det(I + grad u)) < 0.5 (Image.cpp:189-218, ImageRegistrationFluid.cpp:107-124).
-// (fluid_px.h holds the force, the increment, the time step and the
-// integration per pixel for the batch's Fluid loop, batch_fluid_kernels.hip:
-// keep the lines here and there the same operations in the same association.)
+// The per-pixel expressions are sor_px.h's (the force, the sweep's pixel) and
+// fluid_px.h's (the gradients, the increment, maxabs' term, the time step),
+// which the batch's loops share.  sor_strip_kernel, sor_increment_worker and
+// fluid_step_kernel keep their own lines of them (hand-scheduled around a
+// register window or an LDS tile; benchmark configuration 4 runs them), and
+// sor_pack_kernel its force (the call changes its measured instruction
+// stream): the same operations in the same association.
 //
 // The SOR sweep is Gauss-Seidel IN PLACE with i (x) outer and j (y) inner, so
 // v(i,j) reads the NEW v at (i-1,j-1), (i-1,j), (i-1,j+1), (i,j-1) and the OLD
@@ -36,6 +40,9 @@
 //     word.
 #include "of2d_device.h"
 
+#include "fluid_px.h"
+#include "sor_px.h"
+
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -50,38 +57,6 @@ typedef unsigned long long u64;
 // rows per block of the element-wise field kernels (64 x 4 threads, 8 rows
 // each): few enough partials that the single-block final reductions are short
 constexpr int kFieldRows = 32;
-
-struct Grad2 {
-    float2 dx, dy;
-};
-// partial_x / partial_y of the motion on coord2d (gradients.h:9-32): one-sided
-// at the borders, (a - b) / 2 inside
-__device__ __forceinline__ Grad2 motion_gradients(const float2 *__restrict__ u, long idx, int i,
-                                                  int j, int dimx, int dimy, int P) {
-    Grad2 d;
-    if (i == 0) {
-        const float2 a = u[idx + 1], b = u[idx];
-        d.dx = make_float2(a.x - b.x, a.y - b.y);
-    } else if (i == dimx - 1) {
-        const float2 a = u[idx], b = u[idx - 1];
-        d.dx = make_float2(a.x - b.x, a.y - b.y);
-    } else {
-        const float2 a = u[idx + 1], b = u[idx - 1];
-        d.dx = make_float2((a.x - b.x) / 2.0f, (a.y - b.y) / 2.0f);
-    }
-    if (j == 0) {
-        const float2 a = u[idx + P], b = u[idx];
-        d.dy = make_float2(a.x - b.x, a.y - b.y);
-    } else if (j == dimy - 1) {
-        const float2 a = u[idx], b = u[idx - P];
-        d.dy = make_float2(a.x - b.x, a.y - b.y);
-    } else {
-        const float2 a = u[idx + P], b = u[idx - P];
-        d.dy = make_float2((a.x - b.x) / 2.0f, (a.y - b.y) / 2.0f);
-    }
-    return d;
-}
-
 }  // namespace
 
 // The sweep works on the array vb of the field being relaxed (v) and its
@@ -348,7 +323,8 @@ __device__ __attribute__((noinline)) void sor_increment_worker(const float4 *__r
             if (i < dimx && j < dimy) {
                 const long idx = (long)j * P + i;
                 const float2 v = vt[rr][lane];
-                // motion_gradients (gradients.h:9-32) from the rows loaded up front
+                // fluid_gradients_px (fluid_px.h; gradients.h:9-32) from the rows
+                // loaded up front: a kept copy, as the two expressions below
                 const float2 c = uc[rr + 1];
                 float2 dx, dy;
                 if (i == 0)
@@ -364,7 +340,7 @@ __device__ __attribute__((noinline)) void sor_increment_worker(const float4 *__r
                 else
                     dy = make_float2((uc[rr + 2].x - uc[rr].x) / 2.0f,
                                      (uc[rr + 2].y - uc[rr].y) / 2.0f);
-                // (v - dudx*v.x) - dudy*v.y (OpticalFlowFluid.cpp:84), as increment_kernel
+                // fluid_increment_px and fluid_maxabs_px (OpticalFlowFluid.cpp:84)
                 const float2 r = make_float2((v.x - dx.x * v.x) - dy.x * v.y,
                                              (v.y - dx.y * v.x) - dy.y * v.y);
                 w.R[idx] = r;
@@ -486,9 +462,9 @@ __global__ __launch_bounds__(kInc ? 256 : 64) void sor_strip_kernel(float4 *__re
         const v2f Gn = v2f{SOR_SHL(G.x), SOR_SHL(G.y)};  // next step's ghost row in lane 0
         LU = v2f{SOR_SHR(G.x, D.x), SOR_SHR(G.y, D.y)};
         G = Gn;
-        // OpticalFlowFluid.cpp:27-35, same association, no contraction
-        // (sor_px.h holds these lines for the kernels without this window:
-        // keep the two the same)
+        // OpticalFlowFluid.cpp:27-35, same association, no contraction: a
+        // kept copy of sor_px (sor_px.h) on packed fp32 in this register
+        // window; keep the two the same
         const v2f RL = R + L;
         const v2f s1v = (RL + U) + D;
         const v2f t = ((RU - LU) - RD) + LD;
@@ -602,13 +578,10 @@ void launch_sor_traced(float4 *vb, int dimx, int dimy, int P, float mu, float la
                        unsigned long long *trace, hipStream_t st, FluidCtl ctl = {}) {
     if (dimx < 3 || dimy < 3) return;  // no interior (OpticalFlowFluid.cpp:23-24)
     const int ns = sor_nstrips(dimx);
-    // per-pixel constants of OpticalFlowFluid.cpp:27 evaluated once, same float ops
-    const float A = 1.0f - omega;
-    const float B = omega / (-6 * mu - 2 * lambda);
-    const float ML = mu + lambda;
-    hipLaunchKernelGGL(sor_strip_kernel<false>, dim3(ns), dim3(64), 0, st, vb, dimx, dimy, P, A,
-                       B, mu, ML, (v4u *)H, sor_granule_stride(dimy), epoch, ticket, ns, status,
-                       trace, SorInc{}, ctl);
+    const SorCoef k = sor_coef(mu, lambda, omega);
+    hipLaunchKernelGGL(sor_strip_kernel<false>, dim3(ns), dim3(64), 0, st, vb, dimx, dimy, P, k.A,
+                       k.B, k.M, k.ML, (v4u *)H, sor_granule_stride(dimy), epoch, ticket, ns,
+                       status, trace, SorInc{}, ctl);
     OF2D_HIP(hipGetLastError());
 }
 void launch_sor(float4 *vb, int dimx, int dimy, int P, float mu, float lambda, float omega,
@@ -675,6 +648,8 @@ __global__ __launch_bounds__(256) void sor_pack_kernel(float4 *__restrict__ vb,
         const int j = j0 + r;
         if (i >= dimx || j >= dimy) break;
         const long idx = (long)j * P + i;
+        // force_px's lines, kept: through the call the two products become
+        // one packed multiply, another instruction stream than the measured one
         const float2 m = u[idx], g = dI[idx];
         const float sc = (It[idx] + m.x * g.x) + m.y * g.y;
         float2 x = v ? v[idx] : make_float2(0.0f, 0.0f);
@@ -757,9 +732,8 @@ __global__ __launch_bounds__(256) void regrid_pack_kernel(
         const float t = io[k] - ir[k];
         dI[idx] = make_float2(gx, gy);
         It[idx] = t;
-        const float z = 0.0f;  // the estimate after the regrid
-        const float sc = (t + z * gx) + z * gy;
-        fo[rr][threadIdx.x] = make_float2(gx * sc, gy * sc);
+        // the estimate after the regrid is +0
+        fo[rr][threadIdx.x] = force_px(make_float2(0.0f, 0.0f), make_float2(gx, gy), t);
         if (i == 0 && H) {
             const float2 x = reinterpret_cast<const float2 *>(vb)[sor_v(0, j, P)];
             H[kSorPadRows + j] = v4u{__float_as_uint(x.x), __float_as_uint(x.y), epoch, epoch};
@@ -796,9 +770,7 @@ __global__ void force_kernel(const float2 *__restrict__ u, const float2 *__restr
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y;
     if (i >= dimx || j >= dimy) return;
     const long idx = (long)j * P + i;
-    const float2 m = u[idx], g = dI[idx];
-    const float sc = (It[idx] + m.x * g.x) + m.y * g.y;
-    f[idx] = make_float2(g.x * sc, g.y * sc);
+    f[idx] = force_px(u[idx], dI[idx], It[idx]);
 }
 void launch_force(const float2 *u, const float2 *dI, const float *It, float2 *f, int dimx,
                   int dimy, int P, hipStream_t st) {
@@ -832,15 +804,11 @@ __global__ __launch_bounds__(256) void increment_kernel(const float2 *__restrict
         const long idx = (long)j * P + i;
         const float2 v = vt[4 * k + threadIdx.y][threadIdx.x];
         // the zero estimate of a regrid: gradients +0, as from a zeroed buffer
-        const Grad2 d = zu ? Grad2{make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)}
-                           : motion_gradients(u, idx, i, j, dimx, dimy, P);
-        // (v - dudx*v.x) - dudy*v.y
-        const float2 r = make_float2((v.x - d.dx.x * v.x) - d.dy.x * v.y,
-                                     (v.y - d.dx.y * v.x) - d.dy.y * v.y);
+        const FluidGrad d =
+            zu ? fluid_gradients_zero() : fluid_gradients_px(u, idx, i, j, dimx, dimy, P);
+        const float2 r = fluid_increment_px(v, d);
         R[idx] = r;
-        const double y = (double)r.y;
-        const float q = (float)(y * y + y * y);
-        m = (m < q) ? q : m;
+        m = fluid_maxabs_px(m, r);
     }
     m = block_max<4>(m, threadIdx.y, threadIdx.x);
     if (threadIdx.x == 0 && threadIdx.y == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = m;
@@ -854,10 +822,9 @@ __global__ __launch_bounds__(1024) void timestep_kernel(const float *__restrict_
     for (int k = threadIdx.x; k < n; k += 1024) m = (m < part[k]) ? part[k] : m;
     m = block_max<16>(m, threadIdx.x >> 6, threadIdx.x & 63);
     if (threadIdx.x == 0) {
-        const float maxabs = sqrtf(m);
-        const float dumax = 0.65f;  // OpticalFlowFluid.h:32
-        scal[0] = maxabs;
-        scal[1] = dumax / maxabs;
+        const float2 ts = fluid_timestep(m);
+        scal[0] = ts.x;
+        scal[1] = ts.y;
     }
 }
 
@@ -923,13 +890,11 @@ void launch_sor_increment(float4 *vb, int dimx, int dimy, int P, float mu, float
         launch_increment(u, vb, R, dimx, dimy, P, part, scal, st, ctl);
         return;
     }
-    const float A = 1.0f - omega;
-    const float B = omega / (-6 * mu - 2 * lambda);
-    const float ML = mu + lambda;
+    const SorCoef k = sor_coef(mu, lambda, omega);
     const SorInc inc{u, R, part, ticket + 1, ctr, nwg, ntiles, (int)g.y};
     hipLaunchKernelGGL(sor_strip_kernel<true>, dim3(ns + nwg), dim3(256), 0, st, vb, dimx, dimy,
-                       P, A, B, mu, ML, (v4u *)H, sor_granule_stride(dimy), epoch, nullptr, ns,
-                       status, nullptr, inc, ctl);
+                       P, k.A, k.B, k.M, k.ML, (v4u *)H, sor_granule_stride(dimy), epoch, nullptr,
+                       ns, status, nullptr, inc, ctl);
     hipLaunchKernelGGL(timestep_kernel, dim3(1), dim3(1024), 0, st, part, ntiles, scal, ctl);
     OF2D_HIP(hipGetLastError());
 }
@@ -1023,7 +988,8 @@ __global__ __launch_bounds__(256) void fluid_step_kernel(
         const float2 pv = pvk[k];
         uo[idx] = m;
         logger_add(m, pv, sd, sp);
-        // motion_gradients of the new u (gradients.h:9-32)
+        // fluid_gradients_px of the new u (gradients.h:9-32) from the LDS tile,
+        // then jacobian_px's expression and force_px: kept copies
         float2 dx, dy;
         if (i == 0) {
             const float2 a = un[r][c + 1], b = m;

@@ -1,26 +1,21 @@
 // fluid_px.h — the per-pixel expressions of one iteration of
 // OpticalFlowFluid::get_update (OpticalFlowFluid.cpp:123-140) around the
-// velocity sweep (sor_px.h), for the kernels that hold the pixel's values
-// themselves: the batch's Fluid loop (batch_fluid_kernels.hip).  The one-pair
-// kernels (fluid_kernels.hip: sor_pack_kernel, regrid_pack_kernel,
-// increment_kernel, sor_increment_worker, timestep_kernel, fluid_step_kernel)
-// keep their own copies of these lines next to their tiles and register
-// windows; the two must stay the same operations in the same association,
-// compiled with -ffp-contract=off.  The Jacobian of the integrated estimate is
-// jacobian_px (field_px.h), the expression fluid_step_kernel evaluates from its
-// LDS tile.
+// velocity sweep, for every kernel that holds the pixel's values itself: the
+// batch's Fluid loop (batch_fluid_kernels.hip) and the plain one-pair kernels
+// (fluid_kernels.hip: increment_kernel, timestep_kernel).  The force and the
+// sweep's pixel are sor_px.h's, which Elastic shares; the Jacobian of the
+// integrated estimate is jacobian_px (field_px.h).  -ffp-contract=off.
+//
+// The copies that remain, in fluid_kernels.hip, the same operations in the
+// same association: sor_increment_worker (the gradients, the increment and
+// maxabs' term from the rows it loads before its wait) and fluid_step_kernel
+// (the integration and the new estimate's gradients from its LDS tile), both
+// hand-scheduled and run by benchmark configuration 4.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace of2d {
-
-// OpticalFlow::get_force (OpticalFlow.cpp:15-39): f = dI ((It + u.x dI.x) +
-// u.y dI.y).  After a regrid u is +0 (regrid_pack_kernel's z)
-__device__ __forceinline__ float2 fluid_force_px(float2 u, float2 g, float it) {
-    const float sc = (it + u.x * g.x) + u.y * g.y;
-    return make_float2(g.x * sc, g.y * sc);
-}
 
 struct FluidGrad {
     float2 dx, dy;

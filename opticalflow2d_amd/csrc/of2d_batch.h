@@ -2,9 +2,10 @@
 // Demons registrations of one size in one call, and the deformation analysis of
 // their motions (batch.cpp, batch_kernels.hip, batch_resident_kernels.hip,
 // batch_curvature_kernels.hip, batch_elastic_kernels.hip, batch_fluid_kernels.hip,
-// batch_demons_kernels.hip,
-// batch_demons_lds_kernels.hip, batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the host
-// arithmetic: batch_plan.h).
+// batch_demons_kernels.hip, batch_demons_lds_kernels.hip,
+// batch_analysis_kernels.hip; the loop kernels' frame: batch_loop.h; the sweep
+// of the Elastic and Fluid loops: batch_sweep.h; the host arithmetic and what
+// each kind of loop needs: batch_plan.h).
 //
 // Layout: the B fields of a pyramid level live in one allocation, pair k at
 // k * stride elements, each laid out exactly as a Field<T> (of2d_host.h): the
@@ -367,7 +368,6 @@ class Batch {
     void downsample_levels(int which, int npairs);
     void images_in_place(bool shared_ref);
     void motion_in_place();
-    size_t chunk_pairs() const;
     double *analysis_words();
     void ensure_quality_reference(int npairs);
     void run_jacobian(bool map);
@@ -389,14 +389,17 @@ class Batch {
     void images_out(const StageRound &r, const float *field, double *host);
     void motion_in(const StageRound &r, const double *host, float2 *field);
     void motion_out(const StageRound &r, const float2 *field, double *host);
-    // loop `loop` of level s between its two events, by the kernel that reg_
+    // loop `loop` of level s between its two events, by the kernel that kind()
     // and placement_[s] name
     void launch_loop(int s, int loop, bool conv);
-    // c and the Demons loop's own arguments at level L
+    // c and the kind's own arguments at level L
+    LoopArgs hs_args(const LoopCommon &c, BLevel &L) const;
+    CurvLoopArgs curv_args(const LoopCommon &c, BLevel &L) const;
+    ElasticLoopArgs elastic_args(const LoopCommon &c, BLevel &L) const;
+    FluidLoopArgs fluid_args(const LoopCommon &c, BLevel &L) const;
     DemonsLoopArgs demons_args(const LoopCommon &c, BLevel &L) const;
-    bool on_cu_fits(int s) const {
-        return reg_ == 3 ? conv_lds_fits(ldx_[s], ldy_[s]) : resident_fits(ldx_[s], ldy_[s]);
-    }
+    // what the loops need of the driver follows from the kind (batch_plan.h)
+    LoopKind kind() const { return loop_kind(reg_, fluid_); }
     int B_, dimx_, dimy_, nscales_, nrefine_, nloops_ = 0;
     std::vector<int> niter_, ldx_, ldy_;
     int reg_;
@@ -407,20 +410,22 @@ class Batch {
     // Demons: the two Gaussian tables (sigma_fluid, then sigma_diffusion), as
     // Registration's DemonsKernels
     std::vector<double> kfluid_, kdiff_;
-    float *d_kf_ = nullptr;
-    double *d_kd_ = nullptr;
+    DevArray<float> d_kf_;
+    DevArray<double> d_kd_;
     bool fixed_ = false, shared_ = false, have_images_ = false;
-    bool diffeo_ = false;  // option "diffeomorphic" (reg 3, Composition only)
+    bool diffeo_ = false;  // option "diffeomorphic" (Demons, Composition only)
     bool warm_ = false;    // option "warm_start": estimate() resets no motion
-    // option "fluid" (reg 2): the loop is launch_fluid_loop.  The velocity and
-    // the log exist from the first estimate that runs with it
+    // option "fluid" (an Elastic batch): the kind is Fluid.  The velocity
+    // (BLevel::vel) and the log exist from the first estimate that runs with
+    // it (prepare_fluid); the last level's is allocated last
     bool fluid_ = false;
-    bool have_vel_ = false;
+    bool have_velocity() const { return !lv_.empty() && lv_.back().vel.base; }
+    void prepare_fluid();
     void zero_velocity();
-    float *d_flog_ = nullptr;
+    DevArray<float> d_flog_;
     std::vector<float> h_flog_;
-    // option "resident" (reg 0) or "conv_lds" (reg 3), the one a handle of
-    // this kind admits: the levels that fit (on_cu_fits) run launch_hs_resident
+    // option "resident" or "conv_lds", the one a handle of this kind admits
+    // (on_cu_option): the levels that fit (on_cu_fits) run launch_hs_resident
     // or launch_demons_lds.  on_cu_ok_: resident_prepare's or
     // conv_lds_prepare's answer on home_, -1 before it is asked; placement_:
     // per level, what the last estimate ran
@@ -432,17 +437,17 @@ class Batch {
     int ref_pairs_ = 0;  // images Iref holds at every level: 0, 1 (shared) or B
     hipStream_t st_ = nullptr;
     std::vector<BLevel> lv_;
-    double *d_stage_ = nullptr;
+    DevArray<double> d_stage_;
     // analysis: 5 doubles per pair (allocated on first use), and quality's
     // copy of the reference images (qref_pairs_ of them; the stored Iref stays
     // as set_images left it)
-    double *d_words_ = nullptr;
+    DevArray<double> d_words_;
     BField<float> qref_;
     int qref_pairs_ = 0;
     size_t stage_pairs_ = 0;
-    unsigned *d_status_ = nullptr;
-    int *d_iters_ = nullptr;
-    float *d_errs_ = nullptr;
+    DevArray<unsigned> d_status_;
+    DevArray<int> d_iters_;
+    DevArray<float> d_errs_;  // allocated by the first estimate with convergence on
     int maxn_ = 0;
     std::vector<hipEvent_t> ev_;
     hipEvent_t ev_io_[2] = {};  // the caller's stream before / after the device-array launches

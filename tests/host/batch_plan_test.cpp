@@ -1,7 +1,7 @@
 // Stand-alone check of opticalflow2d_amd/csrc/batch_plan.h (host only: no
 // device, no libof2d.so): the staging rounds of the batch's boundary copies,
-// the argument checks of its analysis calls and the fit rules of the loop's
-// on-CU placements.  The rounds are checked by
+// the argument checks of its analysis calls, the fit rules of the loop's
+// on-CU placements and what each kind of loop needs.  The rounds are checked by
 // simulating the copies on host buffers of exactly the sizes the driver
 // allocates, so an offset or a count that is off by one is an out-of-bounds
 // access for AddressSanitizer as well as a failed check.
@@ -196,11 +196,58 @@ static void test_fit_rules() {
         }
 }
 
+// What each kind of loop needs of the driver: the kind from the method and
+// option "fluid", the workgroup at the widths where elastic_waves steps, the
+// launches per loop, and the one on-CU option a kind admits with its fit rule
+static void test_loop_kinds() {
+    using K = batch::LoopKind;
+    CHECK(batch::loop_kind(0, false) == K::HornSchunck && batch::loop_kind(1, false) == K::Curvature &&
+              batch::loop_kind(2, false) == K::Elastic && batch::loop_kind(2, true) == K::Fluid &&
+              batch::loop_kind(3, false) == K::Demons,
+          "the kind follows the method, Fluid is an Elastic batch with its option");
+    const K kinds[] = {K::HornSchunck, K::Curvature, K::Elastic, K::Fluid, K::Demons};
+    const int waves[][2] = {{1, 1}, {64, 1}, {65, 2}, {512, 8}, {513, 8}, {1024, 8}};
+    for (const auto &w : waves) {
+        const int dx = w[0];
+        CHECK(batch::elastic_threads(dx) == 64 * w[1], "dx %d: %d waves sweep", dx, w[1]);
+        CHECK(batch::loop_threads(K::HornSchunck, dx) == batch::kLoopThreads &&
+                  batch::loop_threads(K::Demons, dx) == batch::kLoopThreads,
+              "dx %d: Horn-Schunck and Demons run kLoopThreads", dx);
+        CHECK(batch::loop_threads(K::Curvature, dx) == batch::kCurvThreads,
+              "dx %d: Curvature runs kCurvThreads", dx);
+        CHECK(batch::loop_threads(K::Elastic, dx) == batch::elastic_threads(dx) &&
+                  batch::loop_threads(K::Fluid, dx) == batch::elastic_threads(dx),
+              "dx %d: Elastic and Fluid run elastic_threads", dx);
+    }
+    for (K k : kinds) {
+        const bool demons = k == K::Demons;
+        CHECK(batch::loop_takes_gradients(k) == !demons, "only Demons skips the gradients pass");
+        CHECK(batch::loop_launches(k) == (demons ? 3 : 4), "launches per loop: Demons 3, else 4");
+        CHECK(batch::loop_sweeps(k) == (k == K::Elastic || k == K::Fluid), "Elastic and Fluid sweep");
+    }
+    CHECK(std::strcmp(batch::on_cu_option(K::HornSchunck), "resident") == 0 &&
+              std::strcmp(batch::on_cu_option(K::Demons), "conv_lds") == 0,
+          "Horn-Schunck admits resident, Demons conv_lds");
+    for (K k : {K::Curvature, K::Elastic, K::Fluid}) {
+        CHECK(batch::on_cu_option(k) == nullptr, "no on-CU option for the other kinds");
+        CHECK(!batch::on_cu_fits(k, 16, 16) && !batch::on_cu_fits(k, 1, 1), "and no level fits");
+    }
+    for (const auto &d : {std::pair<int, int>{1, 1}, {128, 128}, {129, 128}, {2, 6000}, {0, 4}}) {
+        CHECK(batch::on_cu_fits(K::HornSchunck, d.first, d.second) ==
+                  batch::resident_fits(d.first, d.second),
+              "Horn-Schunck fits by resident_fits (%d x %d)", d.first, d.second);
+        CHECK(batch::on_cu_fits(K::Demons, d.first, d.second) ==
+                  batch::conv_lds_fits(d.first, d.second),
+              "Demons fits by conv_lds_fits (%d x %d)", d.first, d.second);
+    }
+}
+
 int main() {
     test_chunk_pairs();
     test_rounds();
     test_refusals();
     test_fit_rules();
+    test_loop_kinds();
     std::printf("batch_plan_test: %d checked, %d failed\n", g_checked, g_failed);
     return g_failed ? 1 : 0;
 }
